@@ -39,7 +39,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E: 8.0 TB/s spec
 KERNEL_NAME = {1: "k_spmv_stream", 2: "k_spmv_vector", 3: "k_spmv_rows", 4: "matrix_free", 5: "k_spmv_wave"}
 KERNEL_KEY = {1: "stream", 2: "vector", 3: "rows", 4: "matrix_free", 5: "wave"}
 
@@ -259,6 +259,66 @@ def _slab_sample(A, dim, budget_rows, n_slabs=16):
         vals.append(val)
         rows.append(np.arange(r0, r0 + per, dtype=np.int64))
     return np.concatenate(ias), np.concatenate(jas), np.concatenate(vals), np.concatenate(rows)
+
+
+DUMP_SAMPLE = 1 << 20          # vector entries kept per Lanczos slot by --dump-outputs (<= 40 MB with their indices)
+
+
+def dump_outputs(path, A, v, packed, m, hess):
+    """--dump-outputs: what a caller of qbh_lanczos_dev / qbh_lanczos_real_dev holds after the last timed step, as float64
+    .npy files under `path`:
+      lanczos_m.npy     [m], the step count the last call returned
+      hessenberg.npy    the whole hessenberg array (b_j at [j], a_j at [maxit + j])
+      v.npy             d_v, slot j % 2 holding v_j (so v_{m-1} and v_m), in the caller's basis order; shape (2, S, 2)
+                        (re, im) for complex vectors, (2, S) for packed doubles
+      v_index.npy       the S row indices kept in v.npy
+    S = n when n <= DUMP_SAMPLE; otherwise 16 slabs of consecutive rows at fixed seeded offsets (the same for every run on
+    an operator of the same size), so that two builds can be compared entry by entry."""
+    import ctypes
+    n = int(A.dim)
+    if n <= DUMP_SAMPLE:
+        starts, per = [0], n
+    else:
+        n_slabs, per = 16, DUMP_SAMPLE // 16
+        region = n // n_slabs
+        rng = np.random.default_rng(20240601)
+        starts = [s * region + int(rng.integers(0, region - per + 1)) for s in range(n_slabs)]
+    index = np.concatenate([np.arange(s, s + per, dtype=np.int64) for s in starts])
+    if packed:
+        if int(A.info().basis_internal) != 0:
+            raise SystemExit("--dump-outputs: packed vectors held in an internal basis order have no caller-order download")
+        if len(starts) == 1:            # both slots at once: n complex words are exactly the 2 n doubles of d_v
+            out = v.download(0, n).view(np.float64).reshape(2, n)
+        else:                           # per (even) doubles from row s of slot j: per / 2 complex words at that byte address
+            out = np.empty((2, index.size))
+            for j in range(2):
+                for i, s in enumerate(starts):
+                    h = np.empty(per // 2, dtype=np.complex128)
+                    addr = ctypes.c_void_p(v.ptr.value + 8 * (j * n + s))
+                    _download_words(A, h, addr)
+                    out[j, i * per:(i + 1) * per] = h.view(np.float64)
+    else:
+        out = np.empty((2, index.size, 2))
+        for j in range(2):
+            if int(A.info().basis_internal) != 0 or len(starts) == 1:
+                # an operator with a basis map downloads whole vectors only (mapped back to the caller's order)
+                z = v.download(j * n, n)[index]
+            else:
+                z = np.concatenate([v.download(j * n + s, per) for s in starts])
+            out[j, :, 0], out[j, :, 1] = z.real, z.imag
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "lanczos_m.npy"), np.array([m], dtype=np.float64))
+    np.save(os.path.join(path, "hessenberg.npy"), np.ascontiguousarray(hess, dtype=np.float64))
+    np.save(os.path.join(path, "v.npy"), np.ascontiguousarray(out, dtype=np.float64))
+    np.save(os.path.join(path, "v_index.npy"), index.astype(np.float64))
+
+
+def _download_words(A, h, addr):
+    """qbh_vec_download of h.size complex words from device address addr (a plain copy for an operator without a basis map)."""
+    import ctypes
+    from quantum_basis_amd import _lib
+    _lib.check(_lib.lib().qbh_vec_download(A.handle, h.ctypes.data_as(ctypes.c_void_p), addr, ctypes.c_int64(h.size)),
+               "qbh_vec_download")
 
 
 def _time_loop(fn, min_reps, budget_s, max_reps):
@@ -596,10 +656,18 @@ def main():
                          "process to process: DESIGN-history 5.0c).  1: this process only")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-locate", action="store_true", help="skip the timing of the user call locate_E0_lanczos(nev=1, ncv=1) = Lanczos + CG eigenvector")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps, write what the timed Lanczos call left its caller (step count, hessenberg array, "
+                         "a fixed sample of both Lanczos vectors) as float64 DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is a one-GPU option")
     if args.child:
         args.no_cpu_baseline = args.no_fast_path = args.no_matrix_free = args.no_converge = args.no_locate = True
         args.processes = 1
+        args.dump_outputs = None             # children only time: the parent writes the outputs of its own timed steps
     if args.format is None:                  # workloads whose complex128 CSR cannot be stored name their own default
         args.format = workloads()[args.workload].get("format", "complex128")
     fmt_fast = args.format == "fast"
@@ -632,6 +700,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         args.gpus = world
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs is a one-GPU option")
     children, child_failures = [], []
     if args.processes > 1 and ("rocprofiler" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROFILER_") or k.startswith("ROCPROF_") for k in os.environ)):
         # under rocprofv3 this process has already been GPU-initialised by the profiler's preload and its children would inherit
@@ -703,10 +773,11 @@ def main():
             dist.all_reduce(t, op=op)
         return [float(z) for z in t.tolist()]
 
-    def timed_lanczos(A, packed):
+    def timed_lanczos(A, packed, dump=None):
         """Wm untimed + exactly K timed Lanczos steps on operator A.  lanczos() cannot make a single step from k = 0 (the
         reference's do-while runs once more after the bootstrap step, src/lanczos.cc:167-193), so the recurrence is always
-        started by at least two untimed steps.  Returns dict(elapsed, steps, ms_spmv, n_spmv, n_real)."""
+        started by at least two untimed steps.  dump: a directory for dump_outputs, written after the timed region.
+        Returns dict(elapsed, steps, ms_spmv, n_spmv, n_real)."""
         n = A.dim
         v = A.vec(1 if packed else 2)           # packed doubles: n complex128 = the two slots of n doubles
         hess = np.zeros(2 * maxit)
@@ -761,6 +832,8 @@ def main():
             slots = allreduce_host(slots, dist.ReduceOp.SUM)
             per_rank = [(slots[2 * r], slots[2 * r + 1]) for r in range(world)]
         elapsed, ms_spmv, ms_gather = allreduce_host([elapsed] + mine, dist.ReduceOp.MAX)
+        if dump:
+            dump_outputs(dump, A, v, packed, k, hess)
         e0 = steps_e0 = None
         if not args.no_converge:      # untimed: the same solver to convergence (E0 parity across N / formats / vs the oracle tests)
             maxit2 = 1000
@@ -892,7 +965,7 @@ def main():
                     best = cand
             A.set_option("comm_reserve", best)
             reserve_cal = {"ms_per_step_by_workgroups_left_out": {str(c): round(t, 4) for c, t in timing.items()}, "chosen": best}
-        head = timed_lanczos(A, packed_real)
+        head = timed_lanczos(A, packed_real, dump=args.dump_outputs)
 
     # algorithmic bytes of ONE SpMV launch on this rank: nnz*(16+4) + (rows+1)*8 + x once + y once
     bytes_launch = info.nnz * 20 + (info.nrows + 1) * 8 + (dim if world > 1 else info.nrows) * 16 + info.nrows * 16

@@ -1,7 +1,8 @@
 """tests/stub_rccl/librccl_stub.so is what lets N ranks on ONE GPU run the library's native communicator
-(qbh_comm_create_rccl, tests/test_gpu_native_ranks.py).  A checker has to be checked: here its own protocol runs in the build
-container on host buffers (the stub copies with memcpy when no HIP device is visible) -- all-gather, all-reduce, the grouped
-send / receive all-gather-v with ragged blocks, and the failures it must report where real RCCL would hang or corrupt."""
+(qbh_comm_create_rccl, tests/test_gpu_native_ranks.py).  A checker has to be checked: here its own protocol runs on host buffers,
+with every device hidden from the ranks on any machine (the stub copies with memcpy when no HIP device is visible) -- all-gather,
+all-reduce, the grouped send / receive all-gather-v with ragged blocks, and the failures it must report where real RCCL would hang
+or corrupt."""
 import ctypes as C
 import multiprocessing as mp
 import os
@@ -75,8 +76,11 @@ def _run(world, scenario):
     L = _stub()
     uid = _Uid()
     with tempfile.TemporaryDirectory() as tmp:
-        old = os.environ.get("TMPDIR")
+        old = {k: os.environ.get(k) for k in ("TMPDIR", "HIP_VISIBLE_DEVICES")}
         os.environ["TMPDIR"] = tmp
+        # the ranks see no device (an invalid ordinal hides them all), so on a GPU machine too the stub runs its host-buffer
+        # path: these buffers are numpy arrays, not device memory
+        os.environ["HIP_VISIBLE_DEVICES"] = "-1"
         try:
             assert L.ncclGetUniqueId(C.byref(uid)) == 0
             ctx = mp.get_context("spawn")
@@ -88,10 +92,11 @@ def _run(world, scenario):
             for p in ps:
                 p.join(timeout=30)
         finally:
-            if old is None:
-                os.environ.pop("TMPDIR", None)
-            else:
-                os.environ["TMPDIR"] = old
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
     return res
 
 
