@@ -18,6 +18,7 @@
 #include <cstring>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -270,6 +271,34 @@ void free_pool(std::vector<void *> &pool)
     for (void *p : pool) (void)hipFree(p);
     pool.clear();
 }
+
+// device arrays freed together when the owner goes out of scope, unless release() has handed them on
+struct DevBufs {
+    std::vector<void *> pool;
+    DevBufs() = default;
+    DevBufs(const DevBufs &) = delete;
+    DevBufs &operator=(const DevBufs &) = delete;
+    ~DevBufs() { free_pool(pool); }
+    template <typename T>
+    hipError_t alloc(T **d, size_t bytes)
+    {
+        const hipError_t e = qbh::dev_alloc(d, bytes);
+        if (e == hipSuccess) pool.push_back(*d);
+        return e;
+    }
+    void release() { pool.clear(); }
+};
+
+// QBH_HIP with the public entry point's name `who` in front of the message
+#define QBH_HIP_WHO(who, call)                                                            \
+    do {                                                                                  \
+        hipError_t _e = (call);                                                           \
+        if (_e != hipSuccess) {                                                           \
+            qbh::set_error("%s: %s failed: %s", (who), #call, hipGetErrorString(_e));     \
+            (void)hipGetLastError();                                                      \
+            return _e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;                     \
+        }                                                                                 \
+    } while (0)
 
 int merge_bonds(int n_sites, int n_bonds, const int32_t *bonds, std::map<std::pair<int, int>, double> &out)
 {
@@ -870,6 +899,61 @@ struct ReprDev {
     double fake_pos;
 };
 
+// the symmetry tables of a momentum sector: checks that translation 0 is the identity and every translation a site
+// permutation, fills the binomials and the characters, stores the permutations in perm8 (perm8[g * n_sites + site]) unless
+// it is null and builds the chunk tables tab[(g*n_chunks + c)*64 + v] = scattered bits of chunk c with value v under g.
+// `who` prefixes error messages.
+int sector_symmetry(int n_sites, int n_trans, const int32_t *perms, const double *chars, const char *who, uint64_t (*binom)[34],
+                    double *chr, int8_t *perm8, int &n_chunks, std::vector<uint64_t> &tab)
+{
+    for (int i = 0; i < n_sites; ++i)
+        if (perms[i] != i) {
+            set_error("%s: translation 0 must be the identity", who);
+            return QBH_EINVAL;
+        }
+    for (int g = 0; g < n_trans; ++g) {
+        std::vector<int> seen((size_t)n_sites, 0);
+        for (int s = 0; s < n_sites; ++s) {
+            const int img = perms[(size_t)g * n_sites + s];
+            if (img < 0 || img >= n_sites || seen[(size_t)img]++) {
+                set_error("%s: translation %d is not a site permutation", who, g);
+                return QBH_EINVAL;
+            }
+            if (perm8) perm8[g * n_sites + s] = (int8_t)img;
+        }
+    }
+    for (int p = 0; p <= 64; ++p)
+        for (int k = 0; k <= 33; ++k) binom[p][k] = binom_u64(p, k);
+    for (int g = 0; g < n_trans; ++g) {
+        chr[2 * g] = chars[2 * g];
+        chr[2 * g + 1] = chars[2 * g + 1];
+    }
+    n_chunks = (n_sites + 5) / 6;
+    tab.assign((size_t)n_trans * n_chunks * 64, 0ULL);
+    for (int g = 0; g < n_trans; ++g)
+        for (int c = 0; c < n_chunks; ++c)
+            for (int v = 0; v < 64; ++v) {
+                uint64_t m = 0;
+                for (int b = 0; b < 6; ++b) {
+                    const int site = 6 * c + b;
+                    if (site < n_sites && ((v >> b) & 1)) m |= 1ULL << perms[(size_t)g * n_sites + site];
+                }
+                tab[((size_t)g * n_chunks + c) * 64 + v] = m;
+            }
+    return QBH_OK;
+}
+
+// R zeroed, then the symmetry part of the fixed-n_dn spin sector filled in (bonds and fake_pos are the caller's)
+int repr_symmetry(ReprDev &R, std::vector<uint64_t> &tab, int n_sites, int n_dn, int n_trans, const int32_t *perms,
+                  const double *chars, const char *who)
+{
+    memset(&R, 0, sizeof(R));
+    R.h.n_sites = n_sites;
+    R.h.n_dn = n_dn;
+    R.n_trans = n_trans;
+    return sector_symmetry(n_sites, n_trans, perms, chars, who, R.h.binom, R.chr, nullptr, R.n_chunks, tab);
+}
+
 // image of bit pattern s under translation g; tab[(g*n_chunks + c)*64 + v] = scattered bits of chunk c with value v
 __device__ __forceinline__ uint64_t repr_translate(const uint64_t *tab, int n_chunks, int g, uint64_t s)
 {
@@ -1108,311 +1192,8 @@ __device__ int repr_row(const ReprDev &R, const uint64_t *tab, const uint64_t *r
     return m;
 }
 
-// row lengths of rows [r0, r1); with gf != nullptr the distinct values met on the way are collected for the value
-// dictionary, so that the fill pass can emit 1-byte codes and the 16 B/nnz value array never exists
-__global__ __launch_bounds__(128) void k_repr_count(const ReprDev *Rp, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
-                                                    int64_t dim, int64_t r0, int64_t r1, int32_t *cnt, DictTab T)
-{
-    __shared__ DictCollect D;
-    int32_t cols[kReprMaxRow];
-    d2 vals[kReprMaxRow];
-    bool collect = T.fp != nullptr;
-    if (T.fp != nullptr) dict_collect_init(D);
-    const int64_t stride = (int64_t)gridDim.x * 128;
-    for (int64_t i = r0 + (int64_t)blockIdx.x * 128 + threadIdx.x; i < r1; i += stride) {
-        const int m = repr_row(*Rp, tab, reps, info, dim, i, cols, vals);
-        cnt[i - r0] = m;
-        for (int q = 0; collect && q < m; ++q) collect = dict_collect_insert(D, T, vals[q]);
-    }
-}
-
-// ia is local to the shard (ia[0] = 0 at row r0)
-__global__ __launch_bounds__(128) void k_repr_fill(const ReprDev *Rp, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
-                                                   int64_t dim, int64_t r0, int64_t r1, const int64_t *ia, int32_t *ja, d2 *val)
-{
-    int32_t cols[kReprMaxRow];
-    d2 vals[kReprMaxRow];
-    const int64_t stride = (int64_t)gridDim.x * 128;
-    for (int64_t i = r0 + (int64_t)blockIdx.x * 128 + threadIdx.x; i < r1; i += stride) {
-        const int m = repr_row(*Rp, tab, reps, info, dim, i, cols, vals);
-        const int64_t p0 = ia[i - r0];
-        for (int q = 0; q < m; ++q) {
-            ja[p0 + q] = cols[q];
-            val[p0 + q] = vals[q];
-        }
-    }
-}
-
-template <typename CT>
-__global__ __launch_bounds__(128) void k_repr_fill_coded(const ReprDev *Rp, const uint64_t *tab, const uint64_t *reps,
-                                                         const uint8_t *info, int64_t dim, int64_t r0, int64_t r1, const int64_t *ia,
-                                                         int32_t *ja, CT *code, const d2 *dict, DictTab T)
-{
-    __shared__ DictEncode E;
-    int32_t cols[kReprMaxRow];
-    d2 vals[kReprMaxRow];
-    dict_encode_init(E);
-    const int64_t stride = (int64_t)gridDim.x * 128;
-    for (int64_t i = r0 + (int64_t)blockIdx.x * 128 + threadIdx.x; i < r1; i += stride) {
-        const int m = repr_row(*Rp, tab, reps, info, dim, i, cols, vals);
-        const int64_t p0 = ia[i - r0];
-        for (int q = 0; q < m; ++q) {
-            ja[p0 + q] = cols[q];
-            code[p0 + q] = (CT)dict_encode_one(E, T, dict, vals[q]);
-        }
-    }
-}
-
 }  // namespace
 }  // namespace qbh
-
-// row range of shard `shard`: the uniform partition of qbh_comm, or the caller's cuts (nnz- or cost-balanced, SURVEY 8e)
-static int sector_row_range(const char *who, int64_t dim, int shard, int n_shards, const int64_t *row_cuts, int64_t *r0, int64_t *r1)
-{
-    if (row_cuts) {
-        bool ok = row_cuts[0] == 0 && row_cuts[n_shards] == dim;
-        for (int q = 0; q < n_shards && ok; ++q) ok = row_cuts[q + 1] >= row_cuts[q];
-        if (!ok) {
-            qbh::set_error("%s: row_cuts must rise from 0 to the sector dimension %lld", who, (long long)dim);
-            return QBH_EINVAL;
-        }
-        *r0 = row_cuts[shard];
-        *r1 = row_cuts[shard + 1];
-    } else {
-        const int64_t nblk = (dim + n_shards - 1) / n_shards;
-        *r0 = std::min<int64_t>((int64_t)shard * nblk, dim);
-        *r1 = std::min<int64_t>(*r0 + nblk, dim);
-    }
-    return QBH_OK;
-}
-
-static int gen_heisenberg_repr_impl(qbh_csr **out, int n_sites, int n_dn, int n_bonds, const int32_t *bonds, double J,
-                                       int n_trans, const int32_t *perms, const double *chars, double fake_pos,
-                                       int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
-{
-    using namespace qbh;
-    if (!out || !bonds || !perms || !chars || n_sites <= 0 || n_sites > 62 || n_dn < 0 || n_dn > n_sites || n_dn > 33 ||
-        n_bonds <= 0 || n_trans < 1 || n_trans > kReprMaxTrans || n_shards < 1 || shard < 0 || shard >= n_shards) {
-        set_error("qbh_gen_heisenberg_repr: invalid argument (<= 62 sites, <= 64 translations)");
-        return QBH_EINVAL;
-    }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
-    if (opts && opts->device >= 0) QBH_HIP(hipSetDevice(opts->device));
-    for (int i = 0; i < n_sites; ++i)
-        if (perms[i] != i) {
-            set_error("qbh_gen_heisenberg_repr: translation 0 must be the identity");
-            return QBH_EINVAL;
-        }
-    std::map<std::pair<int, int>, double> bmap;
-    QBH_TRY(merge_bonds(n_sites, n_bonds, bonds, bmap));
-    if ((int)bmap.size() + 1 > kReprMaxRow || (int)bmap.size() > kMaxBonds) {
-        set_error("qbh_gen_heisenberg_repr: too many distinct bonds");
-        return QBH_EUNSUPP;
-    }
-    std::vector<ReprDev> rr(1);
-    ReprDev &R = rr[0];
-    memset(&R, 0, sizeof(R));
-    for (int p = 0; p <= 64; ++p)
-        for (int k = 0; k <= 33; ++k) R.h.binom[p][k] = binom_u64(p, k);
-    R.h.n_sites = n_sites;
-    R.h.n_dn = n_dn;
-    for (const auto &bw : bmap) {
-        R.h.sa[R.h.n_bonds] = bw.first.first;
-        R.h.sb[R.h.n_bonds] = bw.first.second;
-        R.h.offd[R.h.n_bonds] = 0.5 * J * bw.second;
-        R.h.diag[R.h.n_bonds] = 0.25 * J * bw.second;
-        R.h.n_bonds++;
-    }
-    R.n_trans = n_trans;
-    R.n_chunks = (n_sites + 5) / 6;
-    R.fake_pos = fake_pos;
-    for (int g = 0; g < n_trans; ++g) {
-        R.chr[2 * g] = chars[2 * g];
-        R.chr[2 * g + 1] = chars[2 * g + 1];
-    }
-    std::vector<uint64_t> tab((size_t)n_trans * R.n_chunks * 64, 0ULL);
-    for (int g = 0; g < n_trans; ++g)
-        for (int c = 0; c < R.n_chunks; ++c)
-            for (int v = 0; v < 64; ++v) {
-                uint64_t m = 0;
-                for (int b = 0; b < 6; ++b) {
-                    const int site = 6 * c + b;
-                    if (site < n_sites && ((v >> b) & 1)) {
-                        const int img = perms[(size_t)g * n_sites + site];
-                        if (img < 0 || img >= n_sites) {
-                            set_error("qbh_gen_heisenberg_repr: translation %d is not a site permutation", g);
-                            return QBH_EINVAL;
-                        }
-                        m |= 1ULL << img;
-                    }
-                }
-                tab[((size_t)g * R.n_chunks + c) * 64 + v] = m;
-            }
-    const uint64_t nstates_u = binom_u64(n_sites, n_dn);
-    if (nstates_u >= (1ULL << 40)) {
-        set_error("qbh_gen_heisenberg_repr: sector too large to enumerate");
-        return QBH_EUNSUPP;
-    }
-    const int64_t nstates = (int64_t)nstates_u;
-
-    std::vector<void *> pool;
-    ReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr;
-    QBH_TRY(upload(rr, &d_R, pool));
-    QBH_TRY(upload(tab, &d_tab, pool));
-    uint8_t *d_code = nullptr, *d_info = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr, *d_ia = nullptr;
-    uint64_t *d_reps = nullptr;
-    int32_t *d_ja = nullptr;
-    d2 *d_val = nullptr, *d_dict = nullptr;
-    DictBuild db;
-    int rc = QBH_OK;
-    int64_t dim = 0, nnz = 0;
-    auto cleanup = [&](bool all) {
-        free_pool(pool);
-        dict_build_end(&db);
-        if (all && d_code) (void)hipFree(d_code);
-        if (d_cnt) (void)hipFree(d_cnt);
-        if (d_pos) (void)hipFree(d_pos);
-        if (d_reps) (void)hipFree(d_reps);
-        if (d_info) (void)hipFree(d_info);
-        if (all) {
-            if (d_ia) (void)hipFree(d_ia);
-            if (d_ja) (void)hipFree(d_ja);
-            if (d_val) (void)hipFree(d_val);
-            if (d_dict) (void)hipFree(d_dict);
-        }
-    };
-#define QBH_R(call)                                                                            \
-    do {                                                                                       \
-        hipError_t _e = (call);                                                                \
-        if (_e != hipSuccess) {                                                                \
-            set_error("qbh_gen_heisenberg_repr: %s failed: %s", #call, hipGetErrorString(_e)); \
-            cleanup(true);                                                                     \
-            return _e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;                          \
-        }                                                                                      \
-    } while (0)
-    // 1. which states are representatives; their stabiliser order and norm
-    QBH_R(qbh::dev_alloc(&d_code, (size_t)nstates));
-    QBH_R(qbh::dev_alloc(&d_cnt, (size_t)nstates * sizeof(int32_t)));
-    QBH_R(qbh::dev_alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_repr_flag, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, d_tab, nstates, d_code, d_cnt);
-    QBH_R(hipGetLastError());
-    rc = exclusive_scan(d_cnt, nstates, d_pos, 0);
-    if (rc != QBH_OK) {
-        cleanup(true);
-        return rc;
-    }
-    QBH_R(hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (dim <= 0 || dim >= 2147483647LL) {
-        set_error("qbh_gen_heisenberg_repr: sector dimension %lld out of range", (long long)dim);
-        cleanup(true);
-        return QBH_EUNSUPP;
-    }
-    QBH_R(qbh::dev_alloc(&d_reps, (size_t)dim * sizeof(uint64_t)));
-    QBH_R(qbh::dev_alloc(&d_info, (size_t)dim));
-    hipLaunchKernelGGL(k_repr_compact, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, nstates, d_code, d_pos, d_reps,
-                       d_info);
-    QBH_R(hipGetLastError());
-    QBH_R(hipDeviceSynchronize());
-    (void)hipFree(d_code); d_code = nullptr;
-    (void)hipFree(d_cnt); d_cnt = nullptr;
-    (void)hipFree(d_pos); d_pos = nullptr;
-    // 2. this shard's rows: lengths (+ the distinct values) -> row pointers -> fill
-    int64_t r0 = 0, r1 = 0;
-    rc = sector_row_range("qbh_gen_heisenberg_repr", dim, shard, n_shards, row_cuts, &r0, &r1);
-    if (rc != QBH_OK) {
-        cleanup(true);
-        return rc;
-    }
-    const int64_t nloc = r1 - r0;
-    if (nloc <= 0) {
-        set_error("qbh_gen_heisenberg_repr: shard %d of %d is empty (dim %lld)", shard, n_shards, (long long)dim);
-        cleanup(true);
-        return QBH_EINVAL;
-    }
-    const bool want_dict = !opts || opts->value_dict;
-    if (want_dict) {
-        const bool rows_kernel = !opts || opts->spmv_kernel == QBH_KERNEL_AUTO || opts->spmv_kernel == QBH_KERNEL_ROWS;
-        rc = dict_build_begin(&db, (opts && opts->value_dict == 2) || !rows_kernel ? 256 : kDictMax, 0);
-        if (rc != QBH_OK) {
-            cleanup(true);
-            return rc;
-        }
-    }
-    QBH_R(qbh::dev_alloc(&d_cnt, (size_t)nloc * sizeof(int32_t)));
-    QBH_R(qbh::dev_alloc(&d_ia, (size_t)(nloc + 1) * sizeof(int64_t)));
-    const int rgrid = (int)std::min<int64_t>((nloc + 127) / 128, 256 * 16);
-    hipLaunchKernelGGL(k_repr_count, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_cnt, db.tab);
-    QBH_R(hipGetLastError());
-    rc = exclusive_scan(d_cnt, nloc, d_ia, 0);
-    if (rc != QBH_OK) {
-        cleanup(true);
-        return rc;
-    }
-    QBH_R(hipMemcpy(&nnz, d_ia + nloc, sizeof(int64_t), hipMemcpyDeviceToHost));
-    (void)hipFree(d_cnt); d_cnt = nullptr;
-    QBH_R(qbh::dev_alloc(&d_ja, (size_t)nnz * sizeof(int32_t)));
-    int n_dict = 0;
-    if (want_dict) {
-        rc = dict_build_finalize(&db, &d_dict, &n_dict, 0);
-        if (rc != QBH_OK) {
-            cleanup(true);
-            return rc;
-        }
-    }
-    if (n_dict > 0) {
-        // few distinct values: emit 1- or 2-byte codes directly (5 or 6 B/nnz instead of 20)
-        const int w = dict_code_width(n_dict);
-        QBH_R(qbh::dev_alloc(&d_code, (size_t)nnz * w + 16));
-        QBH_R(hipMemset(d_code + (size_t)nnz * w, 0, 16));
-        if (w == 1)
-            hipLaunchKernelGGL(k_repr_fill_coded<uint8_t>, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_ia,
-                               d_ja, d_code, d_dict, db.tab);
-        else
-            hipLaunchKernelGGL(k_repr_fill_coded<uint16_t>, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1,
-                               d_ia, d_ja, reinterpret_cast<uint16_t *>(d_code), d_dict, db.tab);
-        QBH_R(hipGetLastError());
-        int bad = 0;
-        rc = dict_build_mismatch(&db, &bad, 0);
-        if (rc == QBH_OK && bad) {
-            set_error("qbh_gen_heisenberg_repr: value dictionary mismatch between the count and fill passes");
-            rc = QBH_EHIP;
-        }
-        if (rc != QBH_OK) {
-            cleanup(true);
-            return rc;
-        }
-    } else {
-        if (d_dict) (void)hipFree(d_dict);
-        d_dict = nullptr;
-        hipError_t e = qbh::dev_alloc(&d_val, (size_t)nnz * sizeof(d2));
-        if (e != hipSuccess) {
-            set_error("qbh_gen_heisenberg_repr: %lld nonzeros with more than 65536 distinct values do not fit this GPU "
-                      "uncoded (%.1f GB); shard the sector over more GPUs", (long long)nnz, 20e-9 * (double)nnz);
-            cleanup(true);
-            return QBH_ENOMEM;
-        }
-        hipLaunchKernelGGL(k_repr_fill, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_ia, d_ja, d_val);
-        QBH_R(hipGetLastError());
-    }
-    QBH_R(hipDeviceSynchronize());
-#undef QBH_R
-    cleanup(false);
-    if (dim_out) *dim_out = dim;
-    if (d_code) rc = adopt_coded_csr(out, nloc, dim, r0, nnz, d_ia, d_ja, d_code, d_dict, n_dict, opts);
-    else {
-        qbh_opts og;
-        opts_generated(opts, &og);
-        rc = qbh_csr_create_device(out, nloc, dim, r0, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
-    }
-    return rc;                  // ownership passed with the call: on failure the arrays have already been released
-}
-
 
 // S^z_q on a translation-symmetric sector (see k_repr_apply_sz).  perms / chars_new as in qbh_gen_heisenberg_repr, with
 // the characters of the TARGET momentum; the vectors are indexed like the rows of the sector operators (all
@@ -1430,79 +1211,36 @@ extern "C" int qbh_mopr_sz_repr_dev(int n_sites, int n_dn, int n_trans, const in
         set_error("no HIP device visible");
         return QBH_ENODEVICE;
     }
+    const char *who = "qbh_mopr_sz_repr_dev";
     std::vector<ReprDev> rr(1);
-    ReprDev &R = rr[0];
-    memset(&R, 0, sizeof(R));
-    for (int p = 0; p <= 64; ++p)
-        for (int k = 0; k <= 33; ++k) R.h.binom[p][k] = binom_u64(p, k);
-    R.h.n_sites = n_sites;
-    R.h.n_dn = n_dn;
-    R.n_trans = n_trans;
-    R.n_chunks = (n_sites + 5) / 6;
-    for (int g = 0; g < n_trans; ++g) {
-        R.chr[2 * g] = chars_new[2 * g];
-        R.chr[2 * g + 1] = chars_new[2 * g + 1];
-    }
-    std::vector<uint64_t> tab((size_t)n_trans * R.n_chunks * 64, 0ULL);
-    for (int g = 0; g < n_trans; ++g)
-        for (int c = 0; c < R.n_chunks; ++c)
-            for (int v = 0; v < 64; ++v) {
-                uint64_t m = 0;
-                for (int b = 0; b < 6; ++b) {
-                    const int site = 6 * c + b;
-                    if (site < n_sites && ((v >> b) & 1)) {
-                        const int img = perms[(size_t)g * n_sites + site];
-                        if (img < 0 || img >= n_sites) {
-                            set_error("qbh_mopr_sz_repr_dev: translation %d is not a site permutation", g);
-                            return QBH_EINVAL;
-                        }
-                        m |= 1ULL << img;
-                    }
-                }
-                tab[((size_t)g * R.n_chunks + c) * 64 + v] = m;
-            }
+    std::vector<uint64_t> tab;
+    QBH_TRY(repr_symmetry(rr[0], tab, n_sites, n_dn, n_trans, perms, chars_new, who));
     const int64_t nstates = (int64_t)binom_u64(n_sites, n_dn);
     SpinCoefR cf{};
     for (int sidx = 0; sidx < n_sites; ++sidx) {
         cf.re[sidx] = coef[sidx].re;
         cf.im[sidx] = coef[sidx].im;
     }
-    std::vector<void *> pool;
+    DevBufs bufs;
     ReprDev *d_R = nullptr;
     uint64_t *d_tab = nullptr;
     uint8_t *d_code = nullptr;
     int32_t *d_cnt = nullptr;
     int64_t *d_pos = nullptr;
-    int rc = upload(rr, &d_R, pool);
-    if (rc == QBH_OK) rc = upload(tab, &d_tab, pool);
-    hipError_t e = hipSuccess;
+    QBH_TRY(upload(rr, &d_R, bufs.pool));
+    QBH_TRY(upload(tab, &d_tab, bufs.pool));
+    QBH_HIP_WHO(who, bufs.alloc(&d_code, (size_t)nstates));
+    QBH_HIP_WHO(who, bufs.alloc(&d_cnt, (size_t)nstates * sizeof(int32_t)));
+    QBH_HIP_WHO(who, bufs.alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t)));
+    hipLaunchKernelGGL(k_repr_flag, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, d_tab, nstates, d_code, d_cnt);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_TRY(exclusive_scan(d_cnt, nstates, d_pos, 0));
     int64_t dim = 0;
-    if (rc == QBH_OK) {
-        e = qbh::dev_alloc(&d_code, (size_t)nstates);
-        if (e == hipSuccess) e = qbh::dev_alloc(&d_cnt, (size_t)nstates * sizeof(int32_t));
-        if (e == hipSuccess) e = qbh::dev_alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t));
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_repr_flag, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, d_tab, nstates, d_code, d_cnt);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) rc = exclusive_scan(d_cnt, nstates, d_pos, 0);
-        if (e == hipSuccess && rc == QBH_OK) e = hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == QBH_OK) {
-            hipLaunchKernelGGL(k_repr_apply_sz, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, nstates, d_code, d_pos, cf,
-                               reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
-    }
-    free_pool(pool);
-    for (void *q : {(void *)d_code, (void *)d_cnt, (void *)d_pos})
-        if (q) (void)hipFree(q);
-    if (rc != QBH_OK) return rc;
-    if (e != hipSuccess) {
-        set_error("qbh_mopr_sz_repr_dev: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;
-    }
+    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL(k_repr_apply_sz, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, nstates, d_code, d_pos, cf,
+                       reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
     if (dim_out) *dim_out = dim;
     return QBH_OK;
 }
@@ -1510,71 +1248,38 @@ extern "C" int qbh_mopr_sz_repr_dev(int n_sites, int n_dn, int n_trans, const in
 
 namespace qbh {
 namespace {
-// representatives of one (n_dn, characters) sector on the device: d_reps (ascending) and d_info (|S| | zero-norm << 7)
-int enumerate_sector(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars, ReprDev **d_R_out,
-                     uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, std::vector<void *> &pool,
-                     const char *who)
+// representatives (ascending) and their info bytes (|S| | zero-norm << 7) of the sector described by R; d_R, d_tab, d_reps and
+// d_info join `pool`
+int repr_enumerate(const ReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, ReprDev **d_R_out,
+                   uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
 {
-    std::vector<ReprDev> rr(1);
-    ReprDev &R = rr[0];
-    memset(&R, 0, sizeof(R));
-    for (int p = 0; p <= 64; ++p)
-        for (int k = 0; k <= 33; ++k) R.h.binom[p][k] = binom_u64(p, k);
-    R.h.n_sites = n_sites;
-    R.h.n_dn = n_dn;
-    R.n_trans = n_trans;
-    R.n_chunks = (n_sites + 5) / 6;
-    for (int g = 0; g < n_trans; ++g) {
-        R.chr[2 * g] = chars[2 * g];
-        R.chr[2 * g + 1] = chars[2 * g + 1];
-    }
-    std::vector<uint64_t> tab((size_t)n_trans * R.n_chunks * 64, 0ULL);
-    for (int g = 0; g < n_trans; ++g)
-        for (int c = 0; c < R.n_chunks; ++c)
-            for (int v = 0; v < 64; ++v) {
-                uint64_t m = 0;
-                for (int b = 0; b < 6; ++b) {
-                    const int site = 6 * c + b;
-                    if (site < n_sites && ((v >> b) & 1)) {
-                        const int img = perms[(size_t)g * n_sites + site];
-                        if (img < 0 || img >= n_sites) {
-                            set_error("%s: translation %d is not a site permutation", who, g);
-                            return QBH_EINVAL;
-                        }
-                        m |= 1ULL << img;
-                    }
-                }
-                tab[((size_t)g * R.n_chunks + c) * 64 + v] = m;
-            }
-    const int64_t nstates = (int64_t)binom_u64(n_sites, n_dn);
-    QBH_TRY(upload(rr, d_R_out, pool));
+    const int64_t nstates = (int64_t)binom_u64(R.h.n_sites, R.h.n_dn);
+    QBH_TRY(upload(std::vector<ReprDev>(1, R), d_R_out, pool));
     QBH_TRY(upload(tab, d_tab_out, pool));
+    DevBufs tmp;
     uint8_t *d_code = nullptr;
     int32_t *d_cnt = nullptr;
     int64_t *d_pos = nullptr;
-    QBH_HIP(qbh::dev_alloc(&d_code, (size_t)nstates));
-    pool.push_back(d_code);
-    QBH_HIP(qbh::dev_alloc(&d_cnt, (size_t)nstates * sizeof(int32_t)));
-    pool.push_back(d_cnt);
-    QBH_HIP(qbh::dev_alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t)));
-    pool.push_back(d_pos);
+    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
+    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nstates * sizeof(int32_t)));
+    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t)));
     hipLaunchKernelGGL(k_repr_flag, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, *d_R_out, *d_tab_out, nstates, d_code, d_cnt);
-    QBH_HIP(hipGetLastError());
+    QBH_HIP_WHO(who, hipGetLastError());
     QBH_TRY(exclusive_scan(d_cnt, nstates, d_pos, 0));
     int64_t dim = 0;
-    QBH_HIP(hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost));
+    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost));
     if (dim <= 0) {
         set_error("%s: empty sector", who);
         return QBH_EINVAL;
     }
-    QBH_HIP(qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
+    QBH_HIP_WHO(who, qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
     pool.push_back(*d_reps_out);
-    QBH_HIP(qbh::dev_alloc(d_info_out, (size_t)dim));
+    QBH_HIP_WHO(who, qbh::dev_alloc(d_info_out, (size_t)dim));
     pool.push_back(*d_info_out);
     hipLaunchKernelGGL(k_repr_compact, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, *d_R_out, nstates, d_code, d_pos, *d_reps_out,
                        *d_info_out);
-    QBH_HIP(hipGetLastError());
-    QBH_HIP(hipDeviceSynchronize());
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
     *dim_out = dim;
     return QBH_OK;
 }
@@ -1603,16 +1308,18 @@ extern "C" int qbh_mopr_flip_repr_dev(int n_sites, int n_dn_old, int kind, int n
         cf.re[sidx] = coef[sidx].re;
         cf.im[sidx] = coef[sidx].im;
     }
+    const char *who = "qbh_mopr_flip_repr_dev";
+    std::vector<ReprDev> ro(1), rn(1);
+    std::vector<uint64_t> tab_o, tab_n;
+    QBH_TRY(repr_symmetry(ro[0], tab_o, n_sites, n_dn_old, n_trans, perms, chars_old, who));
+    QBH_TRY(repr_symmetry(rn[0], tab_n, n_sites, n_new, n_trans, perms, chars_new, who));
     std::vector<void *> pool;
     ReprDev *R_old = nullptr, *R_new = nullptr;
     uint64_t *tab_old = nullptr, *tab_new = nullptr, *reps_old = nullptr, *reps_new = nullptr;
     uint8_t *info_old = nullptr, *info_new = nullptr;
     int64_t dim_old = 0, dim_new = 0;
-    int rc = enumerate_sector(n_sites, n_dn_old, n_trans, perms, chars_old, &R_old, &tab_old, &reps_old, &info_old, &dim_old, pool,
-                              "qbh_mopr_flip_repr_dev");
-    if (rc == QBH_OK)
-        rc = enumerate_sector(n_sites, n_new, n_trans, perms, chars_new, &R_new, &tab_new, &reps_new, &info_new, &dim_new, pool,
-                              "qbh_mopr_flip_repr_dev");
+    int rc = repr_enumerate(ro[0], tab_o, pool, &R_old, &tab_old, &reps_old, &info_old, &dim_old, who);
+    if (rc == QBH_OK) rc = repr_enumerate(rn[0], tab_n, pool, &R_new, &tab_new, &reps_new, &info_new, &dim_new, who);
     hipError_t e = hipSuccess;
     if (rc == QBH_OK) {
         e = hipMemset(d_vec_new, 0, (size_t)dim_new * sizeof(d2));
@@ -1955,31 +1662,50 @@ __device__ int hubrepr_row(const HubReprDev &R, const uint64_t *tab, const uint6
     return m;
 }
 
-__global__ __launch_bounds__(128) void k_hubrepr_count(const HubReprDev *Rp, const uint64_t *tab, const uint64_t *reps,
-                                                       const uint8_t *info, int64_t dim, int64_t r0, int64_t r1, int32_t *cnt, DictTab T)
+// the row function and the row capacity of each sector family, for the row kernels they share
+__device__ __forceinline__ int sector_row(const ReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim,
+                                          int64_t i, int32_t *cols, d2 *vals)
+{
+    return repr_row(R, tab, reps, info, dim, i, cols, vals);
+}
+__device__ __forceinline__ int sector_row(const HubReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
+                                          int64_t dim, int64_t i, int32_t *cols, d2 *vals)
+{
+    return hubrepr_row(R, tab, reps, info, dim, i, cols, vals);
+}
+template <class Dev> constexpr int max_row = 0;
+template <> constexpr int max_row<ReprDev> = kReprMaxRow;
+template <> constexpr int max_row<HubReprDev> = kHubReprMaxRow;
+
+// row lengths of rows [r0, r1); with T.fp != nullptr the distinct values met on the way are collected for the value
+// dictionary, so that the fill pass can emit 1- or 2-byte codes and the 16 B/nnz value array never exists
+template <class Dev>
+__global__ __launch_bounds__(128) void k_sector_count(const Dev *Rp, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
+                                                      int64_t dim, int64_t r0, int64_t r1, int32_t *cnt, DictTab T)
 {
     __shared__ DictCollect D;
-    int32_t cols[kHubReprMaxRow];
-    d2 vals[kHubReprMaxRow];
+    int32_t cols[max_row<Dev>];
+    d2 vals[max_row<Dev>];
     bool collect = T.fp != nullptr;
     if (T.fp != nullptr) dict_collect_init(D);
     const int64_t stride = (int64_t)gridDim.x * 128;
     for (int64_t i = r0 + (int64_t)blockIdx.x * 128 + threadIdx.x; i < r1; i += stride) {
-        const int m = hubrepr_row(*Rp, tab, reps, info, dim, i, cols, vals);
+        const int m = sector_row(*Rp, tab, reps, info, dim, i, cols, vals);
         cnt[i - r0] = m;
         for (int q = 0; collect && q < m; ++q) collect = dict_collect_insert(D, T, vals[q]);
     }
 }
 
-__global__ __launch_bounds__(128) void k_hubrepr_fill(const HubReprDev *Rp, const uint64_t *tab, const uint64_t *reps,
-                                                      const uint8_t *info, int64_t dim, int64_t r0, int64_t r1, const int64_t *ia,
-                                                      int32_t *ja, d2 *val)
+// ia is local to the shard (ia[0] = 0 at row r0)
+template <class Dev>
+__global__ __launch_bounds__(128) void k_sector_fill(const Dev *Rp, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
+                                                     int64_t dim, int64_t r0, int64_t r1, const int64_t *ia, int32_t *ja, d2 *val)
 {
-    int32_t cols[kHubReprMaxRow];
-    d2 vals[kHubReprMaxRow];
+    int32_t cols[max_row<Dev>];
+    d2 vals[max_row<Dev>];
     const int64_t stride = (int64_t)gridDim.x * 128;
     for (int64_t i = r0 + (int64_t)blockIdx.x * 128 + threadIdx.x; i < r1; i += stride) {
-        const int m = hubrepr_row(*Rp, tab, reps, info, dim, i, cols, vals);
+        const int m = sector_row(*Rp, tab, reps, info, dim, i, cols, vals);
         const int64_t p0 = ia[i - r0];
         for (int q = 0; q < m; ++q) {
             ja[p0 + q] = cols[q];
@@ -1988,18 +1714,18 @@ __global__ __launch_bounds__(128) void k_hubrepr_fill(const HubReprDev *Rp, cons
     }
 }
 
-template <typename CT>
-__global__ __launch_bounds__(128) void k_hubrepr_fill_coded(const HubReprDev *Rp, const uint64_t *tab, const uint64_t *reps,
-                                                            const uint8_t *info, int64_t dim, int64_t r0, int64_t r1, const int64_t *ia,
-                                                            int32_t *ja, CT *code, const d2 *dict, DictTab T)
+template <class Dev, typename CT>
+__global__ __launch_bounds__(128) void k_sector_fill_coded(const Dev *Rp, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
+                                                           int64_t dim, int64_t r0, int64_t r1, const int64_t *ia, int32_t *ja, CT *code,
+                                                           const d2 *dict, DictTab T)
 {
     __shared__ DictEncode E;
-    int32_t cols[kHubReprMaxRow];
-    d2 vals[kHubReprMaxRow];
+    int32_t cols[max_row<Dev>];
+    d2 vals[max_row<Dev>];
     dict_encode_init(E);
     const int64_t stride = (int64_t)gridDim.x * 128;
     for (int64_t i = r0 + (int64_t)blockIdx.x * 128 + threadIdx.x; i < r1; i += stride) {
-        const int m = hubrepr_row(*Rp, tab, reps, info, dim, i, cols, vals);
+        const int m = sector_row(*Rp, tab, reps, info, dim, i, cols, vals);
         const int64_t p0 = ia[i - r0];
         for (int q = 0; q < m; ++q) {
             ja[p0 + q] = cols[q];
@@ -2008,8 +1734,254 @@ __global__ __launch_bounds__(128) void k_hubrepr_fill_coded(const HubReprDev *Rp
     }
 }
 
+// R zeroed, then the symmetry part of the (n_up, n_dn) sector filled in (the operator's terms are the caller's)
+int hubrepr_symmetry(HubReprDev &R, std::vector<uint64_t> &tab, int n_sites, int n_up, int n_dn, int n_trans, const int32_t *perms,
+                     const double *chars, const char *who)
+{
+    memset(&R, 0, sizeof(R));
+    R.n_sites = n_sites;
+    R.n_up = n_up;
+    R.n_dn = n_dn;
+    R.n_trans = n_trans;
+    return sector_symmetry(n_sites, n_trans, perms, chars, who, R.binom, R.chr, R.perm, R.n_chunks, tab);
+}
+
+// representatives (ascending) and their info bytes of the sector described by R; d_R, d_tab, d_reps and d_info join `pool`
+int hubrepr_enumerate(const HubReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, HubReprDev **d_R_out,
+                      uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
+{
+    const long double nst = (long double)binom_u64(R.n_sites, R.n_up) * (long double)binom_u64(R.n_sites, R.n_dn);
+    if (nst >= (long double)(1ULL << 40)) {
+        set_error("%s: sector too large to enumerate", who);
+        return QBH_EUNSUPP;
+    }
+    const int64_t nstates = (int64_t)(binom_u64(R.n_sites, R.n_up) * binom_u64(R.n_sites, R.n_dn));
+    QBH_TRY(upload(std::vector<HubReprDev>(1, R), d_R_out, pool));
+    QBH_TRY(upload(tab, d_tab_out, pool));
+    // one code byte per word, counts per chunk of kHubChunk words
+    const int64_t nchunks = (nstates + kHubChunk - 1) / kHubChunk;
+    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
+    DevBufs tmp;
+    uint8_t *d_code = nullptr;
+    int32_t *d_cnt = nullptr;
+    int64_t *d_pos = nullptr;
+    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
+    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
+    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
+    hipLaunchKernelGGL(k_hubrepr_flag, dim3(egrid), dim3(256), 0, 0, *d_R_out, *d_tab_out, nstates, d_code, d_cnt, nchunks);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_TRY(exclusive_scan(d_cnt, nchunks, d_pos, 0));
+    int64_t dim = 0;
+    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (dim <= 0 || dim >= 2147483647LL) {
+        set_error("%s: sector dimension %lld out of range", who, (long long)dim);
+        return QBH_EUNSUPP;
+    }
+    QBH_HIP_WHO(who, qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
+    pool.push_back(*d_reps_out);
+    QBH_HIP_WHO(who, qbh::dev_alloc(d_info_out, (size_t)dim));
+    pool.push_back(*d_info_out);
+    hipLaunchKernelGGL(k_hubrepr_compact, dim3(egrid), dim3(256), 0, 0, *d_R_out, nstates, d_code, d_pos, nchunks, *d_reps_out,
+                       *d_info_out);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    *dim_out = dim;
+    return QBH_OK;
+}
+
+// one-body terms amp * c^dag_i c_j merged on the same (i, j): (up re, up im, dn re, dn im)
+using TermMap = std::map<std::pair<int, int>, std::array<double, 4>>;
+
+// merges the terms and refuses what hubrepr_row would silently truncate: a row holds at most one move per unordered site
+// pair and species, one per spin-exchange term, and the diagonal
+int merge_terms(int n_sites, int n_terms, const int32_t *term_sites, const qbh_z *amp_up, const qbh_z *amp_dn, int n_exch,
+                const char *who, TermMap &tmap)
+{
+    for (int t = 0; t < n_terms; ++t) {
+        const int i = term_sites[2 * t], j = term_sites[2 * t + 1];
+        if (i < 0 || i >= n_sites || j < 0 || j >= n_sites) {
+            set_error("%s: term %d acts on a site outside the lattice", who, t);
+            return QBH_EINVAL;
+        }
+        auto &a = tmap[{i, j}];
+        a[0] += amp_up[t].re;
+        a[1] += amp_up[t].im;
+        a[2] += amp_dn[t].re;
+        a[3] += amp_dn[t].im;
+    }
+    std::map<std::pair<int, int>, int> pairs;
+    for (const auto &kv : tmap)
+        if (kv.first.first != kv.first.second) pairs[{std::min(kv.first.first, kv.first.second), std::max(kv.first.first, kv.first.second)}] = 1;
+    if ((int)tmap.size() > kHubReprMaxTerms || 2 * (int)pairs.size() + n_exch + 1 > kHubReprMaxRow) {
+        set_error("%s: too many distinct one-body terms (%d on %d site pairs)", who, (int)tmap.size(), (int)pairs.size());
+        return QBH_EUNSUPP;
+    }
+    return QBH_OK;
+}
+
 }  // namespace
 }  // namespace qbh
+
+// ------------------------------ stored sector operators: qbh_gen_heisenberg_repr, qbh_gen_hubbard_repr --
+// row range of shard `shard`: the uniform partition of qbh_comm, or the caller's cuts (nnz- or cost-balanced, SURVEY 8e)
+static int sector_row_range(const char *who, int64_t dim, int shard, int n_shards, const int64_t *row_cuts, int64_t *r0, int64_t *r1)
+{
+    if (row_cuts) {
+        bool ok = row_cuts[0] == 0 && row_cuts[n_shards] == dim;
+        for (int q = 0; q < n_shards && ok; ++q) ok = row_cuts[q + 1] >= row_cuts[q];
+        if (!ok) {
+            qbh::set_error("%s: row_cuts must rise from 0 to the sector dimension %lld", who, (long long)dim);
+            return QBH_EINVAL;
+        }
+        *r0 = row_cuts[shard];
+        *r1 = row_cuts[shard + 1];
+    } else {
+        const int64_t nblk = (dim + n_shards - 1) / n_shards;
+        *r0 = std::min<int64_t>((int64_t)shard * nblk, dim);
+        *r1 = std::min<int64_t>(*r0 + nblk, dim);
+    }
+    return QBH_OK;
+}
+
+// this shard's rows of a sector operator: lengths (+ the distinct values) -> row pointers -> coded or uncoded fill, adopted
+// into *out.  `pool` holds the caller's tables and representatives; it is released before the handle takes the arrays.
+template <class Dev>
+static int assemble_sector_rows(const char *who, std::vector<void *> &pool, const Dev *d_R, const uint64_t *d_tab,
+                                const uint64_t *d_reps, const uint8_t *d_info, int64_t dim, int shard, int n_shards,
+                                const int64_t *row_cuts, const qbh_opts *opts, qbh_csr **out, int64_t *dim_out)
+{
+    using namespace qbh;
+    if (dim >= 2147483647LL) {            // column indices are int32
+        set_error("%s: sector dimension %lld out of range", who, (long long)dim);
+        return QBH_EUNSUPP;
+    }
+    int64_t r0 = 0, r1 = 0;
+    QBH_TRY(sector_row_range(who, dim, shard, n_shards, row_cuts, &r0, &r1));
+    const int64_t nloc = r1 - r0;
+    if (nloc <= 0) {
+        set_error("%s: shard %d of %d is empty (dim %lld)", who, shard, n_shards, (long long)dim);
+        return QBH_EINVAL;
+    }
+    DictBuild db;
+    std::unique_ptr<DictBuild, void (*)(DictBuild *)> db_end(&db, dict_build_end);
+    const bool want_dict = !opts || opts->value_dict;
+    if (want_dict) {
+        const bool rows_kernel = !opts || opts->spmv_kernel == QBH_KERNEL_AUTO || opts->spmv_kernel == QBH_KERNEL_ROWS;
+        QBH_TRY(dict_build_begin(&db, (opts && opts->value_dict == 2) || !rows_kernel ? 256 : kDictMax, 0));
+    }
+    DevBufs csr;                          // the operator's arrays until the handle adopts them
+    int64_t *d_ia = nullptr;
+    int32_t *d_ja = nullptr;
+    uint8_t *d_code = nullptr;
+    d2 *d_val = nullptr, *d_dict = nullptr;
+    const int rgrid = (int)std::min<int64_t>((nloc + 127) / 128, 256 * 16);
+    int64_t nnz = 0;
+    {
+        DevBufs tmp;
+        int32_t *d_cnt = nullptr;
+        QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nloc * sizeof(int32_t)));
+        QBH_HIP_WHO(who, csr.alloc(&d_ia, (size_t)(nloc + 1) * sizeof(int64_t)));
+        hipLaunchKernelGGL(k_sector_count<Dev>, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_cnt, db.tab);
+        QBH_HIP_WHO(who, hipGetLastError());
+        QBH_TRY(exclusive_scan(d_cnt, nloc, d_ia, 0));
+        QBH_HIP_WHO(who, hipMemcpy(&nnz, d_ia + nloc, sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    QBH_HIP_WHO(who, csr.alloc(&d_ja, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
+    int n_dict = 0;
+    if (want_dict) {
+        QBH_TRY(dict_build_finalize(&db, &d_dict, &n_dict, 0));
+        if (d_dict) csr.pool.push_back(d_dict);
+    }
+    if (n_dict > 0) {
+        // few distinct values (amplitudes x signs x phases x square roots of stabiliser ratios): 1- or 2-byte codes are
+        // emitted directly (5 or 6 B/nnz instead of 20)
+        const int w = dict_code_width(n_dict);
+        QBH_HIP_WHO(who, csr.alloc(&d_code, (size_t)nnz * w + 16));
+        QBH_HIP_WHO(who, hipMemset(d_code + (size_t)nnz * w, 0, 16));
+        if (w == 1)
+            hipLaunchKernelGGL((k_sector_fill_coded<Dev, uint8_t>), dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1,
+                               d_ia, d_ja, d_code, d_dict, db.tab);
+        else
+            hipLaunchKernelGGL((k_sector_fill_coded<Dev, uint16_t>), dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1,
+                               d_ia, d_ja, reinterpret_cast<uint16_t *>(d_code), d_dict, db.tab);
+        QBH_HIP_WHO(who, hipGetLastError());
+        int bad = 0;
+        QBH_TRY(dict_build_mismatch(&db, &bad, 0));
+        if (bad) {
+            set_error("%s: value dictionary mismatch between the count and fill passes", who);
+            return QBH_EHIP;
+        }
+    } else {
+        const hipError_t e = csr.alloc(&d_val, (size_t)std::max<int64_t>(nnz, 1) * sizeof(d2));
+        if (e == hipErrorOutOfMemory) {
+            set_error("%s: %lld nonzeros with more than 65536 distinct values do not fit this GPU uncoded (%.1f GB); shard the "
+                      "sector over more GPUs", who, (long long)nnz, 20e-9 * (double)nnz);
+            (void)hipGetLastError();
+            return QBH_ENOMEM;
+        }
+        QBH_HIP_WHO(who, e);
+        hipLaunchKernelGGL(k_sector_fill<Dev>, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_ia, d_ja, d_val);
+        QBH_HIP_WHO(who, hipGetLastError());
+    }
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    free_pool(pool);
+    db_end.reset();
+    csr.release();                        // ownership passes with the call: on failure the arrays have already been released
+    if (dim_out) *dim_out = dim;
+    if (d_code) return adopt_coded_csr(out, nloc, dim, r0, nnz, d_ia, d_ja, d_code, d_dict, n_dict, opts);
+    qbh_opts og;
+    opts_generated(opts, &og);
+    return qbh_csr_create_device(out, nloc, dim, r0, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
+}
+
+static int gen_heisenberg_repr_impl(qbh_csr **out, int n_sites, int n_dn, int n_bonds, const int32_t *bonds, double J,
+                                       int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                                       int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    const char *who = "qbh_gen_heisenberg_repr";
+    if (!out || !bonds || !perms || !chars || n_sites <= 0 || n_sites > 62 || n_dn < 0 || n_dn > n_sites || n_dn > 33 ||
+        n_bonds <= 0 || n_trans < 1 || n_trans > kReprMaxTrans || n_shards < 1 || shard < 0 || shard >= n_shards) {
+        set_error("qbh_gen_heisenberg_repr: invalid argument (<= 62 sites, <= 64 translations)");
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_HIP(hipSetDevice(opts->device));
+    std::vector<ReprDev> rr(1);
+    ReprDev &R = rr[0];
+    std::vector<uint64_t> tab;
+    QBH_TRY(repr_symmetry(R, tab, n_sites, n_dn, n_trans, perms, chars, who));
+    std::map<std::pair<int, int>, double> bmap;
+    QBH_TRY(merge_bonds(n_sites, n_bonds, bonds, bmap));
+    if ((int)bmap.size() + 1 > kReprMaxRow || (int)bmap.size() > kMaxBonds) {
+        set_error("qbh_gen_heisenberg_repr: too many distinct bonds");
+        return QBH_EUNSUPP;
+    }
+    for (const auto &bw : bmap) {
+        R.h.sa[R.h.n_bonds] = bw.first.first;
+        R.h.sb[R.h.n_bonds] = bw.first.second;
+        R.h.offd[R.h.n_bonds] = 0.5 * J * bw.second;
+        R.h.diag[R.h.n_bonds] = 0.25 * J * bw.second;
+        R.h.n_bonds++;
+    }
+    R.fake_pos = fake_pos;
+    if (binom_u64(n_sites, n_dn) >= (1ULL << 40)) {
+        set_error("qbh_gen_heisenberg_repr: sector too large to enumerate");
+        return QBH_EUNSUPP;
+    }
+    std::vector<void *> pool;
+    ReprDev *d_R = nullptr;
+    uint64_t *d_tab = nullptr, *d_reps = nullptr;
+    uint8_t *d_info = nullptr;
+    int64_t dim = 0;
+    int rc = repr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, who);
+    if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
+    free_pool(pool);
+    return rc;
+}
 
 static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn, int n_terms, const int32_t *term_sites,
                                     const qbh_z *amp_up, const qbh_z *amp_dn, double U, int n_pairs, const int32_t *pair_sites,
@@ -2018,6 +1990,7 @@ static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn,
                                     int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
 {
     using namespace qbh;
+    const char *who = "qbh_gen_hubbard_repr";
     if (n_exch < 0 || n_exch > kHubReprMaxPairs || (n_exch > 0 && (!exch_sites || !exch_amp))) {
         set_error("qbh_gen_hubbard_repr: invalid spin-exchange term list");
         return QBH_EINVAL;
@@ -2034,42 +2007,12 @@ static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn,
         return QBH_ENODEVICE;
     }
     if (opts && opts->device >= 0) QBH_HIP(hipSetDevice(opts->device));
-    for (int i = 0; i < n_sites; ++i)
-        if (perms[i] != i) {
-            set_error("qbh_gen_hubbard_repr: translation 0 must be the identity");
-            return QBH_EINVAL;
-        }
-    // merge terms on the same (i, j)
-    std::map<std::pair<int, int>, std::array<double, 4>> tmap;
-    for (int t = 0; t < n_terms; ++t) {
-        const int i = term_sites[2 * t], j = term_sites[2 * t + 1];
-        if (i < 0 || i >= n_sites || j < 0 || j >= n_sites) {
-            set_error("qbh_gen_hubbard_repr: term %d acts on a site outside the lattice", t);
-            return QBH_EINVAL;
-        }
-        auto &a = tmap[{i, j}];
-        a[0] += amp_up[t].re;
-        a[1] += amp_up[t].im;
-        a[2] += amp_dn[t].re;
-        a[3] += amp_dn[t].im;
-    }
-    {   // a row holds at most one move per unordered site pair and species, plus the diagonal
-        std::map<std::pair<int, int>, int> pairs;
-        for (const auto &kv : tmap)
-            if (kv.first.first != kv.first.second) pairs[{std::min(kv.first.first, kv.first.second), std::max(kv.first.first, kv.first.second)}] = 1;
-        if ((int)tmap.size() > kHubReprMaxTerms || 2 * (int)pairs.size() + n_exch + 1 > kHubReprMaxRow) {
-            set_error("qbh_gen_hubbard_repr: too many distinct one-body terms (%d on %d site pairs)", (int)tmap.size(), (int)pairs.size());
-            return QBH_EUNSUPP;
-        }
-    }
     std::vector<HubReprDev> rr(1);
     HubReprDev &R = rr[0];
-    memset(&R, 0, sizeof(R));
-    for (int p = 0; p <= 64; ++p)
-        for (int k = 0; k <= 33; ++k) R.binom[p][k] = binom_u64(p, k);
-    R.n_sites = n_sites;
-    R.n_up = n_up;
-    R.n_dn = n_dn;
+    std::vector<uint64_t> tab;
+    QBH_TRY(hubrepr_symmetry(R, tab, n_sites, n_up, n_dn, n_trans, perms, chars, who));
+    TermMap tmap;
+    QBH_TRY(merge_terms(n_sites, n_terms, term_sites, amp_up, amp_dn, n_exch, who, tmap));
     for (const auto &kv : tmap) {
         R.ti[R.n_terms] = (int8_t)kv.first.first;
         R.tj[R.n_terms] = (int8_t)kv.first.second;
@@ -2104,180 +2047,15 @@ static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn,
     }
     R.n_exch = n_exch;
     R.no_double = no_double ? 1 : 0;
-    R.n_trans = n_trans;
-    R.n_chunks = (n_sites + 5) / 6;
-    for (int g = 0; g < n_trans; ++g) {
-        R.chr[2 * g] = chars[2 * g];
-        R.chr[2 * g + 1] = chars[2 * g + 1];
-        std::vector<int> seen((size_t)n_sites, 0);
-        for (int s = 0; s < n_sites; ++s) {
-            const int img = perms[(size_t)g * n_sites + s];
-            if (img < 0 || img >= n_sites || seen[(size_t)img]++) {
-                set_error("qbh_gen_hubbard_repr: translation %d is not a site permutation", g);
-                return QBH_EINVAL;
-            }
-            R.perm[g * n_sites + s] = (int8_t)img;
-        }
-    }
-    std::vector<uint64_t> tab((size_t)n_trans * R.n_chunks * 64, 0ULL);
-    for (int g = 0; g < n_trans; ++g)
-        for (int c = 0; c < R.n_chunks; ++c)
-            for (int v = 0; v < 64; ++v) {
-                uint64_t m = 0;
-                for (int b = 0; b < 6; ++b) {
-                    const int site = 6 * c + b;
-                    if (site < n_sites && ((v >> b) & 1)) m |= 1ULL << perms[(size_t)g * n_sites + site];
-                }
-                tab[((size_t)g * R.n_chunks + c) * 64 + v] = m;
-            }
-    const long double nst = (long double)binom_u64(n_sites, n_up) * (long double)binom_u64(n_sites, n_dn);
-    if (nst >= (long double)(1ULL << 40)) {
-        set_error("qbh_gen_hubbard_repr: sector too large to enumerate");
-        return QBH_EUNSUPP;
-    }
-    const int64_t nstates = (int64_t)(binom_u64(n_sites, n_up) * binom_u64(n_sites, n_dn));
-
     std::vector<void *> pool;
     HubReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr;
-    QBH_TRY(upload(rr, &d_R, pool));
-    QBH_TRY(upload(tab, &d_tab, pool));
-    uint8_t *d_code = nullptr, *d_info = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr, *d_ia = nullptr;
-    uint64_t *d_reps = nullptr;
-    int32_t *d_ja = nullptr;
-    d2 *d_val = nullptr, *d_dict = nullptr;
-    DictBuild db;
-    int rc = QBH_OK;
-    int64_t dim = 0, nnz = 0;
-    auto cleanup = [&](bool all) {
-        free_pool(pool);
-        dict_build_end(&db);
-        for (void *q : {(void *)d_cnt, (void *)d_pos, (void *)d_reps, (void *)d_info})
-            if (q) (void)hipFree(q);
-        if (all)
-            for (void *q : {(void *)d_code, (void *)d_ia, (void *)d_ja, (void *)d_val, (void *)d_dict})
-                if (q) (void)hipFree(q);
-    };
-#define QBH_R(call)                                                                         \
-    do {                                                                                    \
-        hipError_t _e = (call);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            set_error("qbh_gen_hubbard_repr: %s failed: %s", #call, hipGetErrorString(_e)); \
-            (void)hipGetLastError();                                                        \
-            cleanup(true);                                                                  \
-            return _e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;                       \
-        }                                                                                   \
-    } while (0)
-    // 1. which words are representatives (one code byte per word, counts per chunk of 4096 words)
-    const int64_t nchunks = (nstates + kHubChunk - 1) / kHubChunk;
-    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
-    QBH_R(qbh::dev_alloc(&d_code, (size_t)nstates));
-    QBH_R(qbh::dev_alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
-    QBH_R(qbh::dev_alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_hubrepr_flag, dim3(egrid), dim3(256), 0, 0, d_R, d_tab, nstates, d_code, d_cnt, nchunks);
-    QBH_R(hipGetLastError());
-    rc = exclusive_scan(d_cnt, nchunks, d_pos, 0);
-    if (rc != QBH_OK) {
-        cleanup(true);
-        return rc;
-    }
-    QBH_R(hipMemcpy(&dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (dim <= 0 || dim >= 2147483647LL) {
-        set_error("qbh_gen_hubbard_repr: sector dimension %lld out of range", (long long)dim);
-        cleanup(true);
-        return QBH_EUNSUPP;
-    }
-    QBH_R(qbh::dev_alloc(&d_reps, (size_t)dim * sizeof(uint64_t)));
-    QBH_R(qbh::dev_alloc(&d_info, (size_t)dim));
-    hipLaunchKernelGGL(k_hubrepr_compact, dim3(egrid), dim3(256), 0, 0, d_R, nstates, d_code, d_pos, nchunks, d_reps, d_info);
-    QBH_R(hipGetLastError());
-    QBH_R(hipDeviceSynchronize());
-    (void)hipFree(d_code); d_code = nullptr;
-    (void)hipFree(d_cnt); d_cnt = nullptr;
-    (void)hipFree(d_pos); d_pos = nullptr;
-    // 2. this shard's rows: lengths (+ the distinct values) -> row pointers -> fill
-    int64_t r0 = 0, r1 = 0;
-    rc = sector_row_range("qbh_gen_hubbard_repr", dim, shard, n_shards, row_cuts, &r0, &r1);
-    if (rc != QBH_OK) {
-        cleanup(true);
-        return rc;
-    }
-    const int64_t nloc = r1 - r0;
-    if (nloc <= 0) {
-        set_error("qbh_gen_hubbard_repr: shard %d of %d is empty (dim %lld)", shard, n_shards, (long long)dim);
-        cleanup(true);
-        return QBH_EINVAL;
-    }
-    const bool want_dict = !opts || opts->value_dict;
-    if (want_dict) {
-        const bool rows_kernel = !opts || opts->spmv_kernel == QBH_KERNEL_AUTO || opts->spmv_kernel == QBH_KERNEL_ROWS;
-        rc = dict_build_begin(&db, (opts && opts->value_dict == 2) || !rows_kernel ? 256 : kDictMax, 0);
-        if (rc != QBH_OK) {
-            cleanup(true);
-            return rc;
-        }
-    }
-    QBH_R(qbh::dev_alloc(&d_cnt, (size_t)nloc * sizeof(int32_t)));
-    QBH_R(qbh::dev_alloc(&d_ia, (size_t)(nloc + 1) * sizeof(int64_t)));
-    const int rgrid = (int)std::min<int64_t>((nloc + 127) / 128, 256 * 16);
-    hipLaunchKernelGGL(k_hubrepr_count, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_cnt, db.tab);
-    QBH_R(hipGetLastError());
-    rc = exclusive_scan(d_cnt, nloc, d_ia, 0);
-    if (rc != QBH_OK) {
-        cleanup(true);
-        return rc;
-    }
-    QBH_R(hipMemcpy(&nnz, d_ia + nloc, sizeof(int64_t), hipMemcpyDeviceToHost));
-    (void)hipFree(d_cnt); d_cnt = nullptr;
-    QBH_R(qbh::dev_alloc(&d_ja, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
-    int n_dict = 0;
-    if (want_dict) {
-        rc = dict_build_finalize(&db, &d_dict, &n_dict, 0);
-        if (rc != QBH_OK) {
-            cleanup(true);
-            return rc;
-        }
-    }
-    if (n_dict > 0) {
-        // few distinct values (hopping amplitude x sign x phase x sqrt of stabiliser ratios, the U ladder): 1- or 2-byte codes
-        // are emitted directly and the 16 B/nnz value array never exists
-        const int w = dict_code_width(n_dict);
-        QBH_R(qbh::dev_alloc(&d_code, (size_t)nnz * w + 16));
-        QBH_R(hipMemset(d_code + (size_t)nnz * w, 0, 16));
-        if (w == 1)
-            hipLaunchKernelGGL(k_hubrepr_fill_coded<uint8_t>, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_ia,
-                               d_ja, d_code, d_dict, db.tab);
-        else
-            hipLaunchKernelGGL(k_hubrepr_fill_coded<uint16_t>, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1,
-                               d_ia, d_ja, reinterpret_cast<uint16_t *>(d_code), d_dict, db.tab);
-        QBH_R(hipGetLastError());
-        int bad = 0;
-        rc = dict_build_mismatch(&db, &bad, 0);
-        if (rc == QBH_OK && bad) {
-            set_error("qbh_gen_hubbard_repr: value dictionary mismatch between the count and fill passes");
-            rc = QBH_EHIP;
-        }
-        if (rc != QBH_OK) {
-            cleanup(true);
-            return rc;
-        }
-    } else {
-        if (d_dict) (void)hipFree(d_dict);
-        d_dict = nullptr;
-        QBH_R(qbh::dev_alloc(&d_val, (size_t)std::max<int64_t>(nnz, 1) * sizeof(d2)));
-        hipLaunchKernelGGL(k_hubrepr_fill, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, r0, r1, d_ia, d_ja, d_val);
-        QBH_R(hipGetLastError());
-    }
-    QBH_R(hipDeviceSynchronize());
-#undef QBH_R
-    cleanup(false);
-    if (dim_out) *dim_out = dim;
-    if (d_code) return adopt_coded_csr(out, nloc, dim, r0, nnz, d_ia, d_ja, d_code, d_dict, n_dict, opts);
-    qbh_opts og;
-    opts_generated(opts, &og);
-    return qbh_csr_create_device(out, nloc, dim, r0, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
+    uint64_t *d_tab = nullptr, *d_reps = nullptr;
+    uint8_t *d_info = nullptr;
+    int64_t dim = 0;
+    int rc = hubrepr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, who);
+    if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
+    free_pool(pool);
+    return rc;
 }
 
 // ------------------------- diagonal one-body operators between Hubbard momentum sectors --
@@ -2290,113 +2068,6 @@ namespace qbh {
 namespace {
 
 struct HubCoef { double up_re[32], up_im[32], dn_re[32], dn_im[32]; };
-
-// fills the symmetry part of R (binomials, permutations, characters, chunk tables); `who` prefixes error messages
-int hubrepr_symmetry(HubReprDev &R, std::vector<uint64_t> &tab, int n_sites, int n_up, int n_dn, int n_trans, const int32_t *perms,
-                     const double *chars, const char *who)
-{
-    memset(&R, 0, sizeof(R));
-    for (int p = 0; p <= 64; ++p)
-        for (int k = 0; k <= 33; ++k) R.binom[p][k] = binom_u64(p, k);
-    R.n_sites = n_sites;
-    R.n_up = n_up;
-    R.n_dn = n_dn;
-    R.n_trans = n_trans;
-    R.n_chunks = (n_sites + 5) / 6;
-    for (int i = 0; i < n_sites; ++i)
-        if (perms[i] != i) {
-            set_error("%s: translation 0 must be the identity", who);
-            return QBH_EINVAL;
-        }
-    for (int g = 0; g < n_trans; ++g) {
-        R.chr[2 * g] = chars[2 * g];
-        R.chr[2 * g + 1] = chars[2 * g + 1];
-        std::vector<int> seen((size_t)n_sites, 0);
-        for (int s = 0; s < n_sites; ++s) {
-            const int img = perms[(size_t)g * n_sites + s];
-            if (img < 0 || img >= n_sites || seen[(size_t)img]++) {
-                set_error("%s: translation %d is not a site permutation", who, g);
-                return QBH_EINVAL;
-            }
-            R.perm[g * n_sites + s] = (int8_t)img;
-        }
-    }
-    tab.assign((size_t)n_trans * R.n_chunks * 64, 0ULL);
-    for (int g = 0; g < n_trans; ++g)
-        for (int c = 0; c < R.n_chunks; ++c)
-            for (int v = 0; v < 64; ++v) {
-                uint64_t m = 0;
-                for (int b = 0; b < 6; ++b) {
-                    const int site = 6 * c + b;
-                    if (site < n_sites && ((v >> b) & 1)) m |= 1ULL << perms[(size_t)g * n_sites + site];
-                }
-                tab[((size_t)g * R.n_chunks + c) * 64 + v] = m;
-            }
-    return QBH_OK;
-}
-
-// representatives (ascending) and their info bytes for the sector described by R; device arrays owned by the caller
-int hubrepr_enumerate(const HubReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, HubReprDev **d_R_out,
-                      uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
-{
-    const long double nst = (long double)binom_u64(R.n_sites, R.n_up) * (long double)binom_u64(R.n_sites, R.n_dn);
-    if (nst >= (long double)(1ULL << 40)) {
-        set_error("%s: sector too large to enumerate", who);
-        return QBH_EUNSUPP;
-    }
-    const int64_t nstates = (int64_t)(binom_u64(R.n_sites, R.n_up) * binom_u64(R.n_sites, R.n_dn));
-    std::vector<HubReprDev> rr(1, R);
-    HubReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr;
-    QBH_TRY(upload(rr, &d_R, pool));
-    QBH_TRY(upload(tab, &d_tab, pool));
-    uint8_t *d_code = nullptr, *d_info = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr;
-    uint64_t *d_reps = nullptr;
-    int64_t dim = 0;
-    const int64_t nchunks = (nstates + kHubChunk - 1) / kHubChunk;
-    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
-    hipError_t e = qbh::dev_alloc(&d_code, (size_t)nstates);
-    if (e == hipSuccess) e = qbh::dev_alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t));
-    if (e == hipSuccess) e = qbh::dev_alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t));
-    int rc = QBH_OK;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_hubrepr_flag, dim3(egrid), dim3(256), 0, 0, d_R, d_tab, nstates, d_code, d_cnt, nchunks);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) rc = exclusive_scan(d_cnt, nchunks, d_pos, 0);
-    if (e == hipSuccess && rc == QBH_OK) e = hipMemcpy(&dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == QBH_OK && (dim <= 0 || dim >= 2147483647LL)) {
-        set_error("%s: sector dimension %lld out of range", who, (long long)dim);
-        rc = QBH_EUNSUPP;
-    }
-    if (e == hipSuccess && rc == QBH_OK) e = qbh::dev_alloc(&d_reps, (size_t)dim * sizeof(uint64_t));
-    if (e == hipSuccess && rc == QBH_OK) e = qbh::dev_alloc(&d_info, (size_t)dim);
-    if (e == hipSuccess && rc == QBH_OK) {
-        hipLaunchKernelGGL(k_hubrepr_compact, dim3(egrid), dim3(256), 0, 0, d_R, nstates, d_code, d_pos, nchunks, d_reps, d_info);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    for (void *q : {(void *)d_code, (void *)d_cnt, (void *)d_pos})
-        if (q) (void)hipFree(q);
-    if (e != hipSuccess || rc != QBH_OK) {
-        if (d_reps) (void)hipFree(d_reps);
-        if (d_info) (void)hipFree(d_info);
-        if (e != hipSuccess) {
-            set_error("%s: %s", who, hipGetErrorString(e));
-            (void)hipGetLastError();
-            return e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;
-        }
-        return rc;
-    }
-    *d_R_out = d_R;
-    *d_tab_out = d_tab;
-    *d_reps_out = d_reps;
-    *d_info_out = d_info;
-    *dim_out = dim;
-    return QBH_OK;
-}
 
 __global__ __launch_bounds__(256) void k_hubrepr_apply_diag(int n_sites, const uint64_t *reps, const uint8_t *info_new, int64_t dim,
                                                             HubCoef cf, const d2 *x_old, d2 *y_new)
@@ -2492,8 +2163,6 @@ extern "C" int qbh_mopr_diag_hubrepr_dev(int n_sites, int n_up, int n_dn, int n_
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     free_pool(pool);
-    if (d_reps) (void)hipFree(d_reps);
-    if (d_info) (void)hipFree(d_info);
     if (rc != QBH_OK) return rc;
     if (e != hipSuccess) {
         set_error("qbh_mopr_diag_hubrepr_dev: %s", hipGetErrorString(e));
@@ -2609,8 +2278,6 @@ extern "C" int qbh_mopr_c_hubrepr_dev(int n_sites, int n_up_old, int n_dn_old, i
         }
     }
     free_pool(pool);
-    for (void *q : {(void *)reps_o, (void *)reps_n, (void *)info_o, (void *)info_n})
-        if (q) (void)hipFree(q);
     if (rc != QBH_OK) return rc;
     if (e != hipSuccess) {
         set_error("qbh_mopr_c_hubrepr_dev: %s", hipGetErrorString(e));
@@ -3194,31 +2861,10 @@ extern "C" int qbh_mf_hubbard_repr(qbh_csr **out, int n_sites, int n_up, int n_d
         return QBH_ENODEVICE;
     }
     if (opts && opts->device >= 0) QBH_HIP(hipSetDevice(opts->device));
-    // ---- the operator, exactly as qbh_gen_hubbard_repr merges it
-    std::map<std::pair<int, int>, std::array<double, 4>> tmap;
-    for (int t = 0; t < n_terms; ++t) {
-        const int i = term_sites[2 * t], j = term_sites[2 * t + 1];
-        if (i < 0 || i >= n_sites || j < 0 || j >= n_sites) {
-            set_error("%s: term %d acts on a site outside the lattice", who, t);
-            return QBH_EINVAL;
-        }
-        auto &a = tmap[{i, j}];
-        a[0] += amp_up[t].re;
-        a[1] += amp_up[t].im;
-        a[2] += amp_dn[t].re;
-        a[3] += amp_dn[t].im;
-    }
-    {   // the non-regular blocks and the remainder rows go through hubrepr_row, which holds at most kHubReprMaxRow
-        // distinct columns per row (one move per unordered site pair and species, plus the diagonal): refuse what
-        // would be silently truncated, as qbh_gen_hubbard_repr does
-        std::map<std::pair<int, int>, int> pairs;
-        for (const auto &kv : tmap)
-            if (kv.first.first != kv.first.second) pairs[{std::min(kv.first.first, kv.first.second), std::max(kv.first.first, kv.first.second)}] = 1;
-        if ((int)tmap.size() > kHubReprMaxTerms || 2 * (int)pairs.size() + 1 > kHubReprMaxRow) {
-            set_error("%s: too many distinct one-body terms (%d on %d site pairs)", who, (int)tmap.size(), (int)pairs.size());
-            return QBH_EUNSUPP;
-        }
-    }
+    // ---- the operator, exactly as qbh_gen_hubbard_repr merges it (the non-regular blocks and the remainder rows go
+    // through hubrepr_row); no spin-exchange terms here
+    TermMap tmap;
+    QBH_TRY(merge_terms(n_sites, n_terms, term_sites, amp_up, amp_dn, 0, who, tmap));
     std::vector<HubReprDev> rr(1);
     std::vector<uint64_t> tab;
     QBH_TRY(hubrepr_symmetry(rr[0], tab, n_sites, n_up, n_dn, n_trans, perms, chars, who));
@@ -3696,7 +3342,7 @@ extern "C" int qbh_mf_hubbard_repr(qbh_csr **out, int n_sites, int n_up, int n_d
     }
     if (rc == QBH_OK && e == hipSuccess) e = hipDeviceSynchronize();
     free_pool(pool);
-    for (void *q : {(void *)d_reps, (void *)d_info, (void *)d_flags, (void *)d_ia, (void *)d_pos, (void *)d_opos})
+    for (void *q : {(void *)d_flags, (void *)d_ia, (void *)d_pos, (void *)d_opos})
         if (q) (void)hipFree(q);
     auto drop_all = [&]() {
         for (void *q : {(void *)ms->rrow, (void *)ms->ria, (void *)ms->rja, (void *)ms->rval, (void *)d_vmap})
