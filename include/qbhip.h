@@ -106,7 +106,7 @@ typedef struct qbh_opts {
                                 packed-double vectors) follows the same rule with a split of its own: a second, re-ordered
                                 copy of the coded operator (3 B per nonzero beside the 5 B per nonzero of the coded CSR, which
                                 stays for complex vectors, shards and qbh_csr_download) whose near pass gathers from the block
-                                of x held in LDS -- taken when S doubles fit one workgroup's LDS (S <= 20480) and the major
+                                of x held in LDS -- taken when S doubles fit one workgroup's LDS (S <= 20046) and the major
                                 count fits 16 bits; used by the all-real solves only (qbh_csr_info.kron_minor / kron_sliced).
                                 Where the far entries of a row do not depend on its minor index and the near ones, the diagonal
                                 apart, not on its major index (H = T (x) 1 + 1 (x) T' + D: the two-species models), that is

@@ -295,5 +295,45 @@ def gpu_sharded_hostcsr(rank, world, port, backend, out_dir, native=False, case_
     dist.destroy_process_group()
 
 
+def gpu_sharded_probe(rank, world, port, backend, out_dir, L, n_up, n_dn, bonds_name, b1):
+    """One Lanczos continuation step (purpose dnmcs, k = 1, np = 1) on a row shard of the matrix-free Hubbard operator under
+    the communicator: slot 1 = this rank's slice of x, slot 0 = its slice of z, hess[1] = b1 (once 0 with z = 0, once b1 with
+    a random z).  Saves the slice of v2 and (a1, b2): (H x)_i = b2 v2_i + a1 x_i + b1 z_i (test_gpu_realforms.py)."""
+    import math
+    import torch
+    dist = _init(rank, world, port, backend)
+    torch.cuda.set_device(0)
+    import kronsum
+    import quantum_basis_amd as q
+    from quantum_basis_amd import dist as qdist, lattices
+
+    bonds = {"4x3": lattices.square(4, 3), "chain": lattices.chain(L)}[bonds_name]
+    dim = math.comb(L, n_up) * math.comb(L, n_dn)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        opts = q.make_opts(device=0, stream=stream.cuda_stream)
+        nblk, ranges = qdist.row_partition(dim, world)
+        r0, r1 = ranges[rank]
+        A = q.csr_mat.hubbard(L, n_up, n_dn, bonds, t=1.0, U=1.1, rows=(r0, r1), opts=opts, matrix_free=True)
+        comm = qdist.ShardComm(dim, rank=rank, world=world, device=torch.device("cuda", 0), stream=stream).attach(A)
+        x = kronsum.probe_vector(dim, 11)[r0:r1]
+        for beta in (False, True):
+            z = kronsum.probe_vector(dim, 12)[r0:r1] if beta else np.zeros(r1 - r0)
+            hess = np.zeros(8)
+            hess[1] = b1 if beta else 0.0
+            v = np.zeros(2 * (r1 - r0), dtype=np.complex128)
+            v[:r1 - r0], v[r1 - r0:] = z, x
+            n_real = A.stats().n_spmv_real
+            m = q.lanczos(1, 1, 4, r1 - r0, A, v, hess, "dnmcs")
+            assert m == 2 and not np.any(v.imag) and np.array_equal(v.real[r1 - r0:], x)
+            assert A.stats().n_spmv_real > n_real
+            np.save(os.path.join(out_dir, "v2_%d_%d.npy" % (beta, rank)), v.real[:r1 - r0].copy())
+            if rank == 0:
+                np.save(os.path.join(out_dir, "ab_%d.npy" % beta), np.array([hess[4 + 1], hess[2]]))
+        assert not comm.errors, comm.errors
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 if __name__ == "__main__":
     pass
