@@ -725,6 +725,35 @@ int qbh_mopr_diag_hubrepr_dev(int n_sites, int n_up, int n_dn, int n_trans, cons
 int qbh_mopr_c_hubrepr_dev(int n_sites, int n_up_old, int n_dn_old, int species, int kind, int n_trans, const int32_t *perms,
                            const double *chars_old, const double *chars_new, const qbh_z *coef, const qbh_z *d_vec_old,
                            qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out);
+/* Sites with d local levels and one conserved charge, assembled on the device: spin S (d = 2S+1, level l = S - m, so l = 0 is
+ * m = +S) and bosons with at most n_max per site (d = n_max + 1, l = n); the spin-1 chain and Bose-Hubbard examples of the
+ * reference (basis_prop, src/basis.cc:49-96).  Site s holds a level l_s in [0, d); the charge of level l is l, and the sector
+ * is every word with sum_s l_s = total.
+ * Basis: the words of the sector ranked in ascending order of sum_s l_s d^s (site n_sites-1 the most significant digit).  For
+ * d = 2 with l = 1 = down this is exactly the colexicographic order of qbh_gen_heisenberg.
+ * Two-site terms: pair_mat[p] (d^2 x d^2, row-major) is the matrix M on the sites (i, j) = pair_sites[2p], pair_sites[2p+1],
+ * M[(l'_i d + l'_j), (l_i d + l_j)] = <l'_i l'_j| M |l_i l_j>.  Terms on the same unordered pair are summed; a term given as
+ * (j, i) is transposed into (i, j) order first.  Every nonzero must conserve the charge (l'_i + l'_j = l_i + l_j), else
+ * QBH_EINVAL; every merged pair matrix must be Hermitian (to QBH_SPARSE_PRECISION), else QBH_ENOTHERM.
+ * Single-site terms are diagonal: single_diag[k*d + l] is added for level l of site single_sites[k].
+ * Output: FULL storage of global rows [row_begin, row_end) (row_end = -1: the whole sector), columns ascending, the diagonal
+ * always stored, exact zeros dropped elsewhere; *dim_out (may be NULL) receives the sector dimension.  The arrays are
+ * adopted as by qbh_csr_create_device, so the default value coding, row shards, qbh_csr_download and every solver apply.
+ * Limits: d in [2, 8] and n_sites * ceil(log2 d) <= 64 (the word packs into 64 bits), dim < 2^31 (int32 columns), at most
+ * 1024 distinct site pairs and 240 entries in the worst row (counted from the merged terms): QBH_EUNSUPP beyond them (d < 2
+ * is QBH_EINVAL).  Every argument and term check runs before the device is looked for. */
+int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total,
+                  int n_pairs, const int32_t *pair_sites /* [2*n_pairs] */, const qbh_z *pair_mat /* [n_pairs * d^4] */,
+                  int n_single, const int32_t *single_sites /* [n_single] */, const double *single_diag /* [n_single * d] */,
+                  int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
+/* moprXvec_full (src/model.cc:1468-1538) for the sectors of qbh_gen_qudit: vec_new = sum_s coef[s] O_s vec_old with the
+ * same local d x d matrix O on every site, local[l' d + l] = <l'|O|l>, nonzero only where l' = l + dq (else QBH_EINVAL).
+ * vec_old lives in the sector total_old, vec_new in total_old + dq (*dim_new_out, may be NULL, its dimension); both are
+ * device vectors in the basis of qbh_gen_qudit.  S^z_q: dq = 0; S^+_q: dq = -1 (l = S - m); bosons b_q: dq = -1, n_q: dq = 0.
+ * Every target row gathers its contributions: no atomics, deterministic.  Limits of d and n_sites as qbh_gen_qudit. */
+int qbh_mopr_qudit_dev(int n_sites, int d, int total_old, int dq, const qbh_z *coef /* [n_sites] */,
+                       const qbh_z *local /* [d*d] */, const qbh_z *d_vec_old, qbh_z *d_vec_new,
+                       int64_t *dim_new_out, void *stream);
 /* Measurement harness (SURVEY 7 hard-part 1): the operator of qbh_gen_heisenberg (kind 0) / qbh_gen_hubbard (kind 1), built with
  * complex128 values on one GPU, re-expressed ON THE DEVICE in the reference's own basis order and fermion convention, i.e.
  * exactly the matrix the unchanged host code assembles (src/model.cc:619-685) at sizes that code cannot reach: basis sorted

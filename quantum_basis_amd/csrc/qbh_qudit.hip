@@ -1,0 +1,508 @@
+// qbh_qudit.hip -- device assembly for sites with d local levels and one conserved charge (spin S, bosons with at most
+// n_max per site): qbh_gen_qudit and the operator x vector step qbh_mopr_qudit_dev.
+//
+// Basis (documented in include/qbhip.h): site s holds a level l_s in [0, d), the charge of a word is sum_s l_s, and the
+// words of one charge are ranked in ascending order of sum_s l_s d^s (site n-1 most significant).  With
+//     cnt[s][q] = number of words on sites 0..s-1 of charge q,   cum[s][q] = sum_{q' <= q} cnt[s][q'],
+// the rank of a word is  sum_s ( cum[s][Q_s] - cum[s][Q_s - l_s] ),  Q_s = l_0 + ... + l_s the charge of sites 0..s: the
+// words that agree with it above s and hold a smaller level at s.  The table cum[s][q] does not depend on the sector
+// (at most 64 x 65 x 8 B = 33 KB for every allowed (n_sites, d)) and sits in LDS in every kernel here.
+//
+// A two-site move on sites i < j changes the levels of i and j and the charges Q_i .. Q_{j-1}; every other site keeps its
+// contribution, so the column of a neighbour is the row plus a difference over sites i..j only (qd_move_delta).
+#include <algorithm>
+#include <cmath>
+#include <complex>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "qbh_internal.hpp"
+
+namespace qbh {
+namespace {
+
+constexpr int kQuditMaxD = 8;
+constexpr int kQuditMaxPairs = 1024;     // merged (unordered) site pairs
+constexpr int kQuditMaxRow = 240;        // entries of one row, diagonal included (the fill kernel stages 64 rows in LDS)
+constexpr int kQuditFillBlock = 64;      // one wave per workgroup in the fill kernel: lane = row, LDS column = lane
+
+int bits_per_level(int d) { return d <= 2 ? 1 : d <= 4 ? 2 : 3; }
+
+// cum[s * tw + q] for s < n_sites, q < tw; *dims = cnt[n_sites][q] (the dimension of every sector q < tw)
+void qudit_table(int n_sites, int d, int tw, std::vector<uint64_t> &cum, std::vector<uint64_t> &dims)
+{
+    std::vector<uint64_t> cnt((size_t)tw, 0), nxt((size_t)tw);
+    cnt[0] = 1;
+    cum.assign((size_t)n_sites * tw, 0);
+    for (int s = 0; s < n_sites; ++s) {
+        uint64_t acc = 0;
+        for (int q = 0; q < tw; ++q) cum[(size_t)s * tw + q] = (acc += cnt[q]);
+        for (int q = 0; q < tw; ++q) {
+            uint64_t v = 0;
+            for (int l = 0; l < d && l <= q; ++l) v += cnt[q - l];
+            nxt[q] = v;
+        }
+        cnt.swap(nxt);
+    }
+    dims = cnt;
+}
+
+struct QuditDev {
+    int n_sites, d, bits, total, tw, n_pairs, max_row;
+    const uint64_t *cum;        // [n_sites * tw]
+    const int32_t *pair_ij;     // [n_pairs] i | j << 8, i < j
+    const double *pdiag;        // [n_pairs * d^2] diagonal M[in][in] of pair p, in = l_i d + l_j
+    const int32_t *eoff;        // [n_pairs * d^2 + 1] off-diagonal nonzeros of row `in` of pair p: eoff[p d^2 + in] ..
+    const int32_t *eout;        // [n_ent] the column's levels l'_i | l'_j << 8
+    const d2 *eval;             // [n_ent] M[in][out] = <in|M|out>, the row's entry
+    const double *sdiag;        // [n_sites * d] single-site diagonal
+};
+
+__device__ __forceinline__ int qd_level(uint64_t w, int bits, int s)
+{
+    return (int)((w >> (s * bits)) & ((1ULL << bits) - 1));
+}
+
+// charge of sites 0..s
+__device__ __forceinline__ int qd_charge(uint64_t w, int bits, int s)
+{
+    const int nb = (s + 1) * bits;
+    if (nb < 64) w &= (1ULL << nb) - 1;
+    if (bits == 1) return __popcll(w);
+    if (bits == 2) return __popcll(w & 0x5555555555555555ULL) + 2 * __popcll(w & 0xAAAAAAAAAAAAAAAAULL);
+    const uint64_t m0 = 0x9249249249249249ULL;          // bit 0 of every 3-bit field
+    return __popcll(w & m0) + 2 * __popcll(w & (m0 << 1)) + 4 * __popcll(w & (m0 << 2));
+}
+
+// the word of rank r among the words of charge `total` (walks from the most significant site down)
+__device__ __forceinline__ uint64_t qd_unrank(const uint64_t *cum, int n_sites, int d, int bits, int tw, int total, uint64_t r)
+{
+    uint64_t w = 0;
+    int Q = total;
+    for (int s = n_sites - 1; s >= 0; --s) {
+        const uint64_t *c = cum + s * tw;
+        const uint64_t top = c[Q];
+        int l = min(d - 1, Q);
+        while (l > 0 && top - c[Q - l] > r) --l;          // largest level whose smaller siblings hold <= r words
+        r -= top - c[Q - l];
+        Q -= l;
+        w |= (uint64_t)l << (s * bits);
+    }
+    return w;
+}
+
+// rank(new) - rank(old) for the move (l_i, l_j) -> (ni, nj) on sites i < j of w, Q = charge of sites 0..j (mod 2^64)
+__device__ __forceinline__ uint64_t qd_move_delta(const uint64_t *cum, int tw, int bits, uint64_t w, int i, int j, int Q, int lj,
+                                                 int ni, int nj)
+{
+    const uint64_t *cj = cum + j * tw;
+    uint64_t delta = cj[Q - lj] - cj[Q - nj];
+    int Qo = Q - lj, Qn = Q - nj;
+    for (int t = j - 1; t > i; --t) {
+        const uint64_t *ct = cum + t * tw;
+        const int l = qd_level(w, bits, t);
+        delta += (ct[Qn] - ct[Qn - l]) - (ct[Qo] - ct[Qo - l]);
+        Qo -= l;
+        Qn -= l;
+    }
+    (void)ni;                                              // Qn - ni == Qo - l_i: the lower halves cancel
+    const uint64_t *ci = cum + i * tw;
+    return delta + ci[Qn] - ci[Qo];
+}
+
+__device__ __forceinline__ void qd_stage_table(uint64_t *dst, const uint64_t *src, int n, int nthreads)
+{
+    for (int k = threadIdx.x; k < n; k += nthreads) dst[k] = src[k];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_qudit_count(QuditDev h, int64_t row_begin, int64_t row_end, int32_t *cnt)
+{
+    extern __shared__ uint64_t qd_lds[];
+    qd_stage_table(qd_lds, h.cum, h.n_sites * h.tw, 256);
+    const int d2n = h.d * h.d;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t row = row_begin + (int64_t)blockIdx.x * 256 + threadIdx.x; row < row_end; row += stride) {
+        const uint64_t w = qd_unrank(qd_lds, h.n_sites, h.d, h.bits, h.tw, h.total, (uint64_t)row);
+        int c = 1;
+        for (int p = 0; p < h.n_pairs; ++p) {                 // uniform: the pair's sites come through scalar loads
+            const int ij = h.pair_ij[p];
+            const int in = qd_level(w, h.bits, ij & 0xff) * h.d + qd_level(w, h.bits, ij >> 8);
+            const int32_t *o = h.eoff + p * d2n + in;
+            c += o[1] - o[0];
+        }
+        cnt[row - row_begin] = c;
+    }
+}
+
+// One row per lane; its entries are insertion-sorted by column in the lane's own LDS column (entry k of lane L at k * 64 + L),
+// as (column, entry index; -1 = the diagonal), then written out.  No private array: nothing spills to scratch.
+__global__ __launch_bounds__(kQuditFillBlock) void k_qudit_fill(QuditDev h, int64_t row_begin, int64_t row_end, const int64_t *ia,
+                                                                int32_t *ja, d2 *val)
+{
+    extern __shared__ uint64_t qd_lds[];
+    const int ntab = h.n_sites * h.tw;
+    qd_stage_table(qd_lds, h.cum, ntab, kQuditFillBlock);
+    int32_t *scol = reinterpret_cast<int32_t *>(qd_lds + ntab) + threadIdx.x;
+    int32_t *sent = scol + kQuditFillBlock * h.max_row;
+    const int d2n = h.d * h.d;
+    const int64_t stride = (int64_t)gridDim.x * kQuditFillBlock;
+    for (int64_t row = row_begin + (int64_t)blockIdx.x * kQuditFillBlock + threadIdx.x; row < row_end; row += stride) {
+        const uint64_t w = qd_unrank(qd_lds, h.n_sites, h.d, h.bits, h.tw, h.total, (uint64_t)row);
+        double dg = 0.0;
+        for (int s = 0; s < h.n_sites; ++s) dg += h.sdiag[s * h.d + qd_level(w, h.bits, s)];
+        int n = 0;
+        for (int p = 0; p < h.n_pairs; ++p) {
+            const int ij = h.pair_ij[p];
+            const int i = ij & 0xff, j = ij >> 8;
+            const int li = qd_level(w, h.bits, i), lj = qd_level(w, h.bits, j);
+            const int in = li * h.d + lj;
+            dg += h.pdiag[p * d2n + in];
+            const int e0 = h.eoff[p * d2n + in], e1 = h.eoff[p * d2n + in + 1];
+            if (e0 == e1) continue;
+            const int Q = qd_charge(w, h.bits, j);
+            for (int e = e0; e < e1; ++e) {
+                const int o = h.eout[e];
+                const int32_t c = (int32_t)((uint64_t)row + qd_move_delta(qd_lds, h.tw, h.bits, w, i, j, Q, lj, o & 0xff, o >> 8));
+                int q = n++;
+                while (q > 0 && scol[(q - 1) * kQuditFillBlock] > c) {
+                    scol[q * kQuditFillBlock] = scol[(q - 1) * kQuditFillBlock];
+                    sent[q * kQuditFillBlock] = sent[(q - 1) * kQuditFillBlock];
+                    --q;
+                }
+                scol[q * kQuditFillBlock] = c;
+                sent[q * kQuditFillBlock] = e;
+            }
+        }
+        {
+            const int32_t c = (int32_t)row;
+            int q = n++;
+            while (q > 0 && scol[(q - 1) * kQuditFillBlock] > c) {
+                scol[q * kQuditFillBlock] = scol[(q - 1) * kQuditFillBlock];
+                sent[q * kQuditFillBlock] = sent[(q - 1) * kQuditFillBlock];
+                --q;
+            }
+            scol[q * kQuditFillBlock] = c;
+            sent[q * kQuditFillBlock] = -1;
+        }
+        const int64_t p0 = ia[row - row_begin];
+        for (int q = 0; q < n; ++q) {
+            const int e = sent[q * kQuditFillBlock];
+            ja[p0 + q] = scol[q * kQuditFillBlock];
+            val[p0 + q] = e < 0 ? d2{dg, 0.0} : h.eval[e];
+        }
+    }
+}
+
+// vec_new[row] = sum_s coef[s] a(l'_s) vec_old[rank_old(row's word with l'_s -> l'_s - dq)], a(l') = local[l' d + l' - dq].
+// The old rank is (contributions of the sites below s, charges unchanged) + (site s) + (sites above s, charges shifted by
+// -dq): the shifted sum is formed over all sites first and the sites <= s are taken out of it on the way up.  Indices of
+// terms that are taken out again or never used may leave [0, qmax]: they are clamped, never read out of the table.
+struct QuditMopr { double ca[64], cb[64]; double la[kQuditMaxD], lb[kQuditMaxD]; };
+
+__global__ __launch_bounds__(256) void k_qudit_mopr(int n_sites, int d, int bits, int tw, int total_new, int dq, QuditMopr cf,
+                                                    const uint64_t *cum_g, const d2 *x_old, d2 *y_new, int64_t dim_new)
+{
+    extern __shared__ uint64_t qd_lds[];
+    qd_stage_table(qd_lds, cum_g, n_sites * tw, 256);
+    const int qmax = tw - 1;
+    auto T = [&](int s, int q) -> uint64_t { return qd_lds[s * tw + min(max(q, 0), qmax)]; };
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < dim_new; row += stride) {
+        const uint64_t w = qd_unrank(qd_lds, n_sites, d, bits, tw, total_new, (uint64_t)row);
+        uint64_t hi = 0;                                      // sum over all sites of the shifted contributions
+        int Q = 0;
+        for (int s = 0; s < n_sites; ++s) {
+            const int l = qd_level(w, bits, s);
+            Q += l;
+            hi += T(s, Q - dq) - T(s, Q - dq - l);
+        }
+        uint64_t lo = 0;
+        double ar = 0.0, ai = 0.0;
+        Q = 0;
+        for (int s = 0; s < n_sites; ++s) {
+            const int l = qd_level(w, bits, s), ls = l - dq;
+            Q += l;
+            hi -= T(s, Q - dq) - T(s, Q - dq - l);
+            if (ls >= 0 && ls < d) {
+                const double a_re = cf.la[l], a_im = cf.lb[l];
+                if (a_re != 0.0 || a_im != 0.0) {
+                    const uint64_t src = lo + (T(s, Q - dq) - T(s, Q - dq - ls)) + hi;
+                    const double cr = cf.ca[s] * a_re - cf.cb[s] * a_im, ci = cf.ca[s] * a_im + cf.cb[s] * a_re;
+                    const d2 x = x_old[src];
+                    ar += cr * x.x - ci * x.y;
+                    ai += cr * x.y + ci * x.x;
+                }
+            }
+            lo += T(s, Q) - T(s, Q - l);
+        }
+        y_new[row] = d2{ar, ai};
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- host side --
+struct PairMat { std::vector<std::complex<double>> m; };      // d^2 x d^2, row = out, column = in
+
+int check_shape(const char *who, int n_sites, int d)
+{
+    if (n_sites <= 0 || d < 2) {
+        set_error("%s: need n_sites >= 1 and d >= 2 (got %d, %d)", who, n_sites, d);
+        return QBH_EINVAL;
+    }
+    if (d > kQuditMaxD) {
+        set_error("%s: d = %d local levels; at most %d are supported", who, d, kQuditMaxD);
+        return QBH_EUNSUPP;
+    }
+    if (n_sites * bits_per_level(d) > 64 || n_sites > 64) {
+        set_error("%s: %d sites of %d bits do not pack into 64 bits", who, n_sites, bits_per_level(d));
+        return QBH_EUNSUPP;
+    }
+    return QBH_OK;
+}
+
+struct HipFree {
+    std::vector<void *> p;
+    ~HipFree() { for (void *q : p) (void)hipFree(q); }
+};
+
+template <typename T>
+hipError_t up(HipFree &pool, T **d, const std::vector<T> &h)
+{
+    hipError_t e = qbh::dev_alloc(d, std::max<size_t>(h.size(), 1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    pool.p.push_back(*d);
+    return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+}  // namespace
+}  // namespace qbh
+
+using qbh::d2;
+
+#define QBH_QHIP(who, call)                                                                \
+    do {                                                                                   \
+        hipError_t _e = (call);                                                            \
+        if (_e != hipSuccess) {                                                            \
+            qbh::set_error("%s: %s failed: %s", (who), #call, hipGetErrorString(_e));      \
+            (void)hipGetLastError();                                                       \
+            return _e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;                      \
+        }                                                                                  \
+    } while (0)
+
+extern "C" int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
+                             const qbh_z *pair_mat, int n_single, const int32_t *single_sites, const double *single_diag,
+                             int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    static const char *who = "qbh_gen_qudit";
+    if (!out) {
+        set_error("%s: out is NULL", who);
+        return QBH_EINVAL;
+    }
+    QBH_TRY(check_shape(who, n_sites, d));
+    if (total < 0 || total > n_sites * (d - 1) || n_pairs < 0 || n_single < 0 || (n_pairs > 0 && (!pair_sites || !pair_mat)) ||
+        (n_single > 0 && (!single_sites || !single_diag))) {
+        set_error("%s: invalid charge %d (0 .. %d) or term arrays", who, total, n_sites * (d - 1));
+        return QBH_EINVAL;
+    }
+    const int d2n = d * d;
+    // merge the pair terms into (i < j) order; (j, i) is transposed: element [(a' d + b'), (a d + b)] -> [(b' d + a'), (b d + a)]
+    std::map<std::pair<int, int>, PairMat> pm;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int a = pair_sites[2 * p], b = pair_sites[2 * p + 1];
+        if (a < 0 || b < 0 || a >= n_sites || b >= n_sites || a == b) {
+            set_error("%s: pair %d = (%d, %d) is invalid for %d sites", who, p, a, b, n_sites);
+            return QBH_EINVAL;
+        }
+        PairMat &M = pm[{std::min(a, b), std::max(a, b)}];
+        if (M.m.empty()) M.m.assign((size_t)d2n * d2n, 0.0);
+        const qbh_z *src = pair_mat + (size_t)p * d2n * d2n;
+        for (int r = 0; r < d2n; ++r)
+            for (int c = 0; c < d2n; ++c) {
+                const qbh_z z = src[(size_t)r * d2n + c];
+                if (z.re == 0.0 && z.im == 0.0) continue;
+                if (r / d + r % d != c / d + c % d) {
+                    set_error("%s: pair %d element [%d][%d] = (%g, %g) changes the charge", who, p, r, c, z.re, z.im);
+                    return QBH_EINVAL;
+                }
+                const int rr = a < b ? r : (r % d) * d + r / d, cc = a < b ? c : (c % d) * d + c / d;
+                M.m[(size_t)rr * d2n + cc] += std::complex<double>(z.re, z.im);
+            }
+    }
+    for (const auto &kv : pm)
+        for (int r = 0; r < d2n; ++r)
+            for (int c = r; c < d2n; ++c) {
+                const std::complex<double> x = kv.second.m[(size_t)r * d2n + c], y = kv.second.m[(size_t)c * d2n + r];
+                if (std::abs(x - std::conj(y)) > QBH_SPARSE_PRECISION) {
+                    set_error("%s: the merged pair (%d, %d) is not Hermitian at [%d][%d]", who, kv.first.first, kv.first.second, r, c);
+                    return QBH_ENOTHERM;
+                }
+            }
+    std::vector<double> sdiag((size_t)n_sites * d, 0.0);
+    for (int k = 0; k < n_single; ++k) {
+        const int s = single_sites[k];
+        if (s < 0 || s >= n_sites) {
+            set_error("%s: single-site term %d names site %d of %d", who, k, s, n_sites);
+            return QBH_EINVAL;
+        }
+        for (int l = 0; l < d; ++l) sdiag[(size_t)s * d + l] += single_diag[(size_t)k * d + l];
+    }
+    if ((int)pm.size() > kQuditMaxPairs) {
+        set_error("%s: %d distinct site pairs; at most %d are supported", who, (int)pm.size(), kQuditMaxPairs);
+        return QBH_EUNSUPP;
+    }
+    // term tables: per pair and state `in` of the row's word, the off-diagonal nonzeros <in|M|o> of that row (ascending o)
+    std::vector<int32_t> pair_ij, eoff(1, 0), eout;
+    std::vector<double> pdiag;
+    std::vector<d2> eval;
+    int max_row = 1;
+    for (const auto &kv : pm) {
+        pair_ij.push_back(kv.first.first | (kv.first.second << 8));
+        int worst = 0;
+        for (int in = 0; in < d2n; ++in) {
+            pdiag.push_back(kv.second.m[(size_t)in * d2n + in].real());
+            int k = 0;
+            for (int o = 0; o < d2n; ++o) {
+                const std::complex<double> z = kv.second.m[(size_t)in * d2n + o];
+                if (o == in || (z.real() == 0.0 && z.imag() == 0.0)) continue;
+                eout.push_back((o / d) | ((o % d) << 8));
+                eval.push_back(d2{z.real(), z.imag()});
+                ++k;
+            }
+            eoff.push_back((int32_t)eout.size());
+            worst = std::max(worst, k);
+        }
+        max_row += worst;
+    }
+    if (max_row > kQuditMaxRow) {
+        set_error("%s: a row may hold %d entries; at most %d are supported", who, max_row, kQuditMaxRow);
+        return QBH_EUNSUPP;
+    }
+    const int tw = total + 1;
+    std::vector<uint64_t> cum, dims;
+    qudit_table(n_sites, d, tw, cum, dims);
+    const uint64_t dim_u = dims[(size_t)total];
+    if (dim_out) *dim_out = (int64_t)std::min<uint64_t>(dim_u, (uint64_t)INT64_MAX);
+    if (dim_u >= 2147483647ULL) {
+        set_error("%s: dim %llu exceeds int32 columns", who, (unsigned long long)dim_u);
+        return QBH_EUNSUPP;
+    }
+    const int64_t dim = (int64_t)dim_u;
+    if (row_end < 0) row_end = dim;
+    if (row_begin < 0 || row_begin >= row_end || row_end > dim) {
+        set_error("%s: bad row range [%lld, %lld) of %lld", who, (long long)row_begin, (long long)row_end, (long long)dim);
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_QHIP(who, hipSetDevice(opts->device));
+
+    HipFree pool;
+    QuditDev h{};
+    h.n_sites = n_sites;
+    h.d = d;
+    h.bits = bits_per_level(d);
+    h.total = total;
+    h.tw = tw;
+    h.n_pairs = (int)pm.size();
+    h.max_row = max_row;
+    {
+        uint64_t *c;
+        int32_t *pij, *eo, *eu;
+        double *pd, *sd;
+        d2 *ev;
+        QBH_QHIP(who, up(pool, &c, cum));
+        QBH_QHIP(who, up(pool, &pij, pair_ij));
+        QBH_QHIP(who, up(pool, &pd, pdiag));
+        QBH_QHIP(who, up(pool, &eo, eoff));
+        QBH_QHIP(who, up(pool, &eu, eout));
+        QBH_QHIP(who, up(pool, &ev, eval));
+        QBH_QHIP(who, up(pool, &sd, sdiag));
+        h.cum = c; h.pair_ij = pij; h.pdiag = pd; h.eoff = eo; h.eout = eu; h.eval = ev; h.sdiag = sd;
+    }
+    const int64_t nrows = row_end - row_begin;
+    const size_t tab_bytes = cum.size() * sizeof(uint64_t);
+    const size_t fill_lds = tab_bytes + (size_t)kQuditFillBlock * max_row * 8;
+    int32_t *d_cnt = nullptr;
+    QBH_QHIP(who, qbh::dev_alloc(&d_cnt, (size_t)nrows * sizeof(int32_t)));
+    pool.p.push_back(d_cnt);
+    int64_t *d_ia = nullptr;
+    QBH_QHIP(who, qbh::dev_alloc(&d_ia, (size_t)(nrows + 1) * sizeof(int64_t)));
+    HipFree own;                                              // the CSR arrays until the handle adopts them
+    own.p.push_back(d_ia);
+    hipLaunchKernelGGL(k_qudit_count, dim3(blas_grid(nrows)), dim3(256), tab_bytes, 0, h, row_begin, row_end, d_cnt);
+    QBH_QHIP(who, hipGetLastError());
+    QBH_TRY(exclusive_scan(d_cnt, nrows, d_ia, 0));
+    int64_t nnz = 0;
+    QBH_QHIP(who, hipMemcpy(&nnz, d_ia + nrows, sizeof(int64_t), hipMemcpyDeviceToHost));
+    int32_t *d_ja = nullptr;
+    d2 *d_val = nullptr;
+    QBH_QHIP(who, qbh::dev_alloc(&d_ja, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
+    own.p.push_back(d_ja);
+    QBH_QHIP(who, qbh::dev_alloc(&d_val, (size_t)std::max<int64_t>(nnz, 1) * sizeof(d2)));
+    own.p.push_back(d_val);
+    QBH_QHIP(who, hipFuncSetAttribute(reinterpret_cast<const void *>(k_qudit_fill), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)fill_lds));
+    int64_t grid = (nrows + kQuditFillBlock - 1) / kQuditFillBlock;
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(k_qudit_fill, dim3((unsigned)grid), dim3(kQuditFillBlock), fill_lds, 0, h, row_begin, row_end, d_ia, d_ja,
+                       d_val);
+    QBH_QHIP(who, hipGetLastError());
+    QBH_QHIP(who, hipDeviceSynchronize());
+    own.p.clear();                                            // ownership passes with the call (freed by it on failure)
+    qbh_opts og;
+    opts_generated(opts, &og);
+    return qbh_csr_create_device(out, nrows, dim, row_begin, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
+}
+
+extern "C" int qbh_mopr_qudit_dev(int n_sites, int d, int total_old, int dq, const qbh_z *coef, const qbh_z *local,
+                                  const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_new_out, void *stream)
+{
+    using namespace qbh;
+    static const char *who = "qbh_mopr_qudit_dev";
+    QBH_TRY(check_shape(who, n_sites, d));
+    const int total_new = total_old + dq;
+    if (!coef || !local || !d_vec_old || !d_vec_new || total_old < 0 || total_old > n_sites * (d - 1) || total_new < 0 ||
+        total_new > n_sites * (d - 1)) {
+        set_error("%s: invalid argument (charge %d -> %d of at most %d)", who, total_old, total_new, n_sites * (d - 1));
+        return QBH_EINVAL;
+    }
+    QuditMopr cf{};
+    for (int lp = 0; lp < d; ++lp)
+        for (int l = 0; l < d; ++l) {
+            const qbh_z z = local[lp * d + l];
+            if (z.re == 0.0 && z.im == 0.0) continue;
+            if (lp != l + dq) {
+                set_error("%s: local[%d][%d] is nonzero but does not change the level by dq = %d", who, lp, l, dq);
+                return QBH_EINVAL;
+            }
+            cf.la[lp] = z.re;
+            cf.lb[lp] = z.im;
+        }
+    for (int s = 0; s < n_sites; ++s) {
+        cf.ca[s] = coef[s].re;
+        cf.cb[s] = coef[s].im;
+    }
+    const int tw = std::max(total_old, total_new) + 1;
+    std::vector<uint64_t> cum, dims;
+    qudit_table(n_sites, d, tw, cum, dims);
+    const int64_t dim_new = (int64_t)std::min<uint64_t>(dims[(size_t)total_new], (uint64_t)INT64_MAX);
+    if (dim_new_out) *dim_new_out = dim_new;
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    HipFree pool;
+    uint64_t *d_cum = nullptr;
+    QBH_QHIP(who, up(pool, &d_cum, cum));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_qudit_mopr, dim3(blas_grid(dim_new)), dim3(256), cum.size() * sizeof(uint64_t), s, n_sites, d,
+                       bits_per_level(d), tw, total_new, dq, cf, d_cum, reinterpret_cast<const d2 *>(d_vec_old),
+                       reinterpret_cast<d2 *>(d_vec_new), dim_new);
+    QBH_QHIP(who, hipGetLastError());
+    QBH_QHIP(who, hipStreamSynchronize(s));
+    return QBH_OK;
+}

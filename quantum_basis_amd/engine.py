@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
+from .qudit import qudit_dim  # noqa: F401  (host-side sector dimension of csr_mat.qudit)
 
 lanczos_precision = 2e-12      # src/miscellaneous.cc:47
 sparse_precision = 1e-14       # src/miscellaneous.cc:46
@@ -268,6 +269,46 @@ class csr_mat:
         pairs = [(i, j, 0.0, -0.5 * J, -0.5 * J, 0.0) for (i, j) in b]            # J Sz Sz - J n n / 4
         exch = [(i, j, 0.5 * J) for (i, j) in b]
         return cls.hubbard_repr(n_sites, n_up, n_dn, b, perms, chars, t=t, U=0.0, pairs=pairs, exchange=exch, no_double=True, **kw)
+
+    @classmethod
+    def qudit(cls, n_sites, d, total, pairs=(), singles=(), rows=None, opts=None):
+        """Sector of charge `total` of n_sites sites with d levels, assembled on the device (qbh_gen_qudit; basis and term
+        conventions in quantum_basis_amd.qudit).  pairs: (i, j, M) with M a d^2 x d^2 matrix; singles: (i, diag) with d
+        values; rows=(r0, r1): that row block only."""
+        _lib.require_gpu()
+        opts = opts if opts is not None else make_opts()
+        pairs, singles = list(pairs), list(singles)
+        ps = np.ascontiguousarray(np.array([(p[0], p[1]) for p in pairs], dtype=np.int32).reshape(-1, 2))
+        pm = np.ascontiguousarray(np.array([np.asarray(p[2], dtype=np.complex128).reshape(d * d, d * d) for p in pairs],
+                                           dtype=np.complex128).reshape(-1))
+        ss = np.ascontiguousarray(np.array([s[0] for s in singles], dtype=np.int32))
+        sd = np.ascontiguousarray(np.array([np.asarray(s[1], dtype=np.float64).reshape(d) for s in singles],
+                                           dtype=np.float64).reshape(-1))
+        r0, r1 = (0, -1) if rows is None else rows
+        h = C.c_void_p()
+        dim = C.c_int64(0)
+        check(lib().qbh_gen_qudit(C.byref(h), n_sites, d, total, len(pairs), _p(ps), _p(pm), len(singles), _p(ss), _p(sd),
+                                  C.c_int64(r0), C.c_int64(r1), C.byref(dim), C.byref(opts)), "qbh_gen_qudit")
+        return cls(0, None, None, None, opts=opts, _handle=h)
+
+    @classmethod
+    def spin_heisenberg(cls, n_sites, S, two_sz, bonds, J=1.0, Jz=None, K=0.0, D=0.0, rows=None, opts=None):
+        """Spin-S XXZ / bilinear-biquadratic chain or lattice with single-ion anisotropy in the sector 2 S^z = two_sz:
+        sum_<ij> [J/2 (S+S- + S-S+) + Jz SzSz + K (S.S)^2] + D sum (S^z)^2 on qbh_gen_qudit (total = n S - S^z)."""
+        from . import qudit as qd
+        singles = qd.single_ion(S, n_sites, D) if D != 0.0 else []
+        return cls.qudit(n_sites, qd._two_s(S) + 1, qd.spin_charge(n_sites, S, two_sz), qd.heisenberg_terms(S, bonds, J, Jz, K),
+                         singles, rows=rows, opts=opts)
+
+    @classmethod
+    def bose_hubbard(cls, n_sites, n_bosons, n_max, bonds, t=1.0, U=1.1, mu=0.0, rows=None, opts=None):
+        """-t sum_<ij> (b+_i b_j + h.c.) + U/2 sum n(n-1) - mu sum n with n_bosons bosons, at most n_max per site
+        (examples/trans_absent/latt_square/square_Bose_Hubbard.cc) on qbh_gen_qudit."""
+        from . import qudit as qd
+        pairs, _ = qd.bose_hubbard_terms(n_max, bonds, t, U, mu)
+        n = np.arange(n_max + 1, dtype=np.float64)
+        dg = 0.5 * U * n * (n - 1) - mu * n
+        return cls.qudit(n_sites, n_max + 1, n_bosons, pairs, [(s, dg) for s in range(n_sites)], rows=rows, opts=opts)
 
     # ---- reference interface -------------------------------------------------------------
     def dimension(self):
@@ -702,6 +743,18 @@ def moprXvec_terms(family, n_sites, n_a_old, n_b_old, terms, d_vec_old, d_vec_ne
     dim_new = C.c_int64(0)
     check(lib().qbh_mopr_terms_dev(fam, n_sites, n_a_old, n_b_old, len(terms), _p(ptr), _p(kind), _p(site), _p(spec), _p(coef), d_vec_old, d_vec_new,
                                    C.byref(dim_new), stream), "qbh_mopr_terms_dev")
+    return dim_new.value
+
+
+def moprXvec_qudit(n_sites, d, total_old, dq, coef, local, d_vec_old, d_vec_new, stream=None):
+    """vec_new = sum_s coef[s] O_s vec_old between the sectors total_old and total_old + dq of qbh_gen_qudit (O: d x d,
+    <l'|O|l> nonzero only for l' = l + dq; qbh_mopr_qudit_dev).  Returns the dimension of the target sector."""
+    c = np.ascontiguousarray(coef, dtype=np.complex128)
+    o = np.ascontiguousarray(np.asarray(local, dtype=np.complex128).reshape(d * d))
+    assert c.size == n_sites
+    dim_new = C.c_int64(0)
+    check(lib().qbh_mopr_qudit_dev(n_sites, d, total_old, dq, _p(c), _p(o), d_vec_old, d_vec_new, C.byref(dim_new), stream),
+          "qbh_mopr_qudit_dev")
     return dim_new.value
 
 
