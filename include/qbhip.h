@@ -273,7 +273,7 @@ void qbh_csr_destroy(qbh_csr *A);
 
 typedef struct qbh_csr_info {
     int64_t nrows, ncols, row_offset, nnz;   /* nnz as applied (full storage)                 */
-    int64_t n_blocks;                        /* workgroups per SpMV launch                     */
+    int64_t n_blocks;                        /* row blocks of the CSR geometry (both parts of a split shard) */
     int64_t bytes_matrix;                    /* HBM bytes held by the matrix arrays            */
     int64_t bytes_algorithmic;               /* nnz*20 + (nrows+1)*8 + nrows*16 + nrows*16     */
     int     kernel;                          /* QBH_KERNEL_* actually selected                 */

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import csrforms as cf
 import quantum_basis_amd as q
 from quantum_basis_amd import _lib
 
@@ -70,16 +71,26 @@ def test_random_matrices_all_kernels(shape, upper):
     y0 = (rng.normal(size=n) + 1j * rng.normal(size=n)).astype(np.complex128)
     want = M @ x
     scale = max(np.abs(want).max(), 1e-300)
+    _, fia, _, fval = _to_ref(M, False)            # the full storage the device holds (what the route depends on)
+    if upper:                                       # ... whose lower triangle is the conjugate of the upper one, bit for bit
+        rows = np.repeat(np.arange(n), np.diff(ia))
+        fval = np.concatenate([val, np.conj(val[ja != rows])])
     for kernel in (_lib.KERNEL_ROWS, _lib.KERNEL_STREAM, _lib.KERNEL_VECTOR, _lib.KERNEL_WAVE):
         for vd in (0, 1):
             for npb in (0, 1024):
                 A = q.csr_mat(n, ia, ja, val, sym=upper, opts=q.make_opts(spmv_kernel=kernel, value_dict=vd, nnz_per_block=npb))
+                # the form that actually runs: WAVE with value_dict = 1 is the coded row kernel when the values code,
+                # STREAM / VECTOR stay uncoded above 256 distinct values
+                r = cf.route(kernel, vd, fia, fval, npb_opt=npb)
+                form = (r["kernel"], r["key"], npb)
+                info = A.info()
+                assert (info.kernel, info.value_dict) == (r["info_kernel"], r["n_dict"]), form
                 y = np.empty(n, dtype=np.complex128)
                 A.MultMv(x, y)
-                assert np.abs(y - want).max() <= 2e-13 * scale, (kernel, vd, npb)
+                assert np.abs(y - want).max() <= 2e-13 * scale, form
                 y2 = y0.copy()
                 A.MultMv2(x, y2)
-                assert np.abs(y2 - (y0 + want)).max() <= 2e-13 * max(scale, np.abs(y0).max())
+                assert np.abs(y2 - (y0 + want)).max() <= 2e-13 * max(scale, np.abs(y0).max()), form
                 if kw.get("few_values") and vd:
                     assert 0 < A.info().value_dict <= 256
                 A.destroy()
