@@ -11,12 +11,17 @@ v_m = -b v_{m-2} + H v_{m-1}, a = Re<v_{m-1}, v_m>, v_m -= a v_{m-1}, b = |v_m|,
 the host Ritz solve + stop test ("sr_val0").  The Hamiltonian is assembled on the device
 (synthetic: no dataset exists for this path), resident in HBM before the timed region.
 
+A plain run does only what the headline needs: it builds the operator, makes the W + K steps, writes --dump-outputs and
+prints the line.  Everything that takes runs of its own -- the median of several processes, the untimed run to convergence
+behind e0, and the blocks below value / roofline -- is measured with --full.
+
 What the blocks of the JSON line are measured on:
   value / roofline   THE NORTH-STAR FORMAT (default --format complex128): CSR with complex128 values (16 B) + int32
                      columns, complex128 vectors, complex arithmetic -- the format SURVEY 8(d)'s algorithmic bytes
                      (nnz*20 + rows*40) describe, semantics of csr_mat::MultMv2 (src/sparse.cc:262-289).
-                     At N = 1 the headline is the MEDIAN of --processes fresh child processes (each builds its own operator
-                     and times W + exactly K steps); min / median / max are printed in "processes".
+                     With --full at N = 1 the headline is the MEDIAN of --processes fresh child processes (each builds its
+                     own operator and times W + exactly K steps); min / median / max are printed in "processes".
+  e0                 --full: the same solver run on to convergence after the timed steps (untimed).
   fast_path          the library's default for a real operator (lossless, bit-identical results): 1-byte value codes,
                      vectors and gathers as packed doubles.  Its roofline fraction is defined on the bytes the form that
                      runs must MOVE (coded_format_roofline): the sliced coded split of a recognised Kronecker sum streams
@@ -639,23 +644,26 @@ def main():
                     "RCCL's own kernels find a place beside them; 0 (library default) 64, -1 none")
     ap.add_argument("--no-reserve-calibration", action="store_true", help="N > 1: keep qbh_opts.comm_reserve at the library's default instead of trying 64 / 128 / 32 in a few untimed steps")
     ap.add_argument("--no-partition", action="store_true", help="N > 1, hubbard workloads: keep the up configurations in ascending pattern order (qbh_opts.major_partition = 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-converge", action="store_true", help="skip the untimed run to convergence (E0)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well: the median of --processes fresh processes, the untimed "
+                         "run to convergence (e0), cpu_baseline, bare_spmv, locate_E0, fast_path, matrix_free_* (each --no-* below drops one)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-converge", action="store_true", help="--full: skip the untimed run to convergence (E0)")
     ap.add_argument("--cpu-rows", type=int, default=2_000_000)
     ap.add_argument("--matrix-free", action="store_true", help="use the matrix-free operator as THE operator (not the CSR north-star path)")
-    ap.add_argument("--no-matrix-free", action="store_true", help="skip the extra measurement of the matrix-free operator")
+    ap.add_argument("--no-matrix-free", action="store_true", help="--full: skip the extra measurement of the matrix-free operator")
     ap.add_argument("--packed-real", action="store_true", help="matrix-free operator + Lanczos vectors as packed doubles (qbh_lanczos_real_dev); "
                     "forced for the workloads whose complex vectors do not fit one GPU")
-    ap.add_argument("--converge", action="store_true", help="run to convergence also for the dim > 1e9 packed-real workloads")
-    ap.add_argument("--no-fast-path", action="store_true", help="skip the extra measurement of the coded / real fast path")
+    ap.add_argument("--converge", action="store_true", help="--full: run to convergence also for the dim > 1e9 packed-real workloads")
+    ap.add_argument("--no-fast-path", action="store_true", help="--full: skip the extra measurement of the coded / real fast path")
     ap.add_argument("--no-plain", action="store_true", help="(kept for older command lines; the uncoded kernel is the headline now)")
-    ap.add_argument("--processes", type=int, default=3,
-                    help="N = 1 only: the headline (W warm-up + exactly K timed steps on a freshly created operator) is measured in this many "
-                         "FRESH child processes, started one after the other before this process touches the GPU; the line reports min / "
-                         "median / max and the headline value / roofline.frac are the MEDIAN process's (physical placement differs from "
+    ap.add_argument("--processes", type=int, default=None,
+                    help="N = 1 only (default 3 with --full, 1 without): the headline (W warm-up + exactly K timed steps on a freshly "
+                         "created operator) is measured in this many FRESH child processes, started one after the other before this "
+                         "process touches the GPU; the line reports min / median / max and the headline value / roofline.frac are the MEDIAN process's (physical placement differs from "
                          "process to process: DESIGN-history 5.0c).  1: this process only")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-locate", action="store_true", help="skip the timing of the user call locate_E0_lanczos(nev=1, ncv=1) = Lanczos + CG eigenvector")
+    ap.add_argument("--no-locate", action="store_true", help="--full: skip the timing of the user call locate_E0_lanczos(nev=1, ncv=1) = Lanczos + CG eigenvector")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="one GPU: after the timed steps, write what the timed Lanczos call left its caller (step count, hessenberg array, "
                          "a fixed sample of both Lanczos vectors) as float64 DIR/<name>.npy (see dump_outputs)")
@@ -664,8 +672,13 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.gpus > 1:
         ap.error("--dump-outputs is a one-GPU option")
-    if args.child:
+    if args.converge and not args.full:
+        ap.error("--converge is a --full option")
+    if args.processes is None:
+        args.processes = 3 if args.full else 1
+    if args.child or not args.full:
         args.no_cpu_baseline = args.no_fast_path = args.no_matrix_free = args.no_converge = args.no_locate = True
+    if args.child:
         args.processes = 1
         args.dump_outputs = None             # children only time: the parent writes the outputs of its own timed steps
     if args.format is None:                  # workloads whose complex128 CSR cannot be stored name their own default

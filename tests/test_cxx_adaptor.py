@@ -156,7 +156,7 @@ def test_bench_under_torch_distributed_run_uses_the_native_communicator(nranks):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "5", "--warmup", "2", "--workload", "hubbard_4x3_half", "--no-cpu-baseline"]
+    common = ["--steps", "5", "--warmup", "2", "--workload", "hubbard_4x3_half", "--full", "--no-cpu-baseline"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True,
                          env=env, cwd=ROOT, timeout=600)
     assert one.returncode == 0, one.stdout + one.stderr

@@ -209,7 +209,7 @@ def test_bench_two_ranks_on_one_gpu_through_the_native_communicator(rig):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, QBH_RCCL_LIB=STUB, QBH_DIST_BACKEND="gloo", TMPDIR=rig["tmp"], HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "5", "--warmup", "2", "--workload", "hubbard_4x3_half", "--no-cpu-baseline", "--no-matrix-free", "--no-fast-path", "--processes", "1"]
+    common = ["--steps", "5", "--warmup", "2", "--workload", "hubbard_4x3_half", "--full", "--no-cpu-baseline", "--no-matrix-free", "--no-fast-path", "--processes", "1"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     assert one.returncode == 0, one.stdout + one.stderr
     ref = json.loads([ln for ln in one.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -291,7 +291,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(rig):
     before it touches the GPU, relays rank 0's line and the ranks' exit code; --gpus 1 is unchanged."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(QBH_RCCL_LIB=STUB, QBH_DIST_BACKEND="gloo", TMPDIR=rig["tmp"], HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "4", "--warmup", "2", "--workload", "hubbard_4x3_half", "--no-cpu-baseline", "--no-matrix-free", "--no-fast-path", "--processes", "1", "--force-split"]
+    common = ["--steps", "4", "--warmup", "2", "--workload", "hubbard_4x3_half", "--full", "--no-cpu-baseline", "--no-matrix-free", "--no-fast-path", "--processes", "1", "--force-split"]
     many = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + common, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert many.returncode == 0, many.stdout + many.stderr
     lines = [ln for ln in many.stdout.strip().splitlines() if ln.startswith("{")]

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 
 
 def run(env, n, extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", "custom", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-fast-path",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", "custom", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-fast-path",
            "--no-matrix-free", "--no-locate", "--processes", "1", "--force-split"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
