@@ -754,6 +754,40 @@ int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total,
 int qbh_mopr_qudit_dev(int n_sites, int d, int total_old, int dq, const qbh_z *coef /* [n_sites] */,
                        const qbh_z *local /* [d*d] */, const qbh_z *d_vec_old, qbh_z *d_vec_new,
                        int64_t *dim_new_out, void *stream);
+/* Momentum sectors of the d-level sites of qbh_gen_qudit (model::generate_Ham_sparse_repr, src/model.cc:687-836, for spin S
+ * and bosons).  Terms, d and total as in qbh_gen_qudit, with the same checks and codes; translations as in
+ * qbh_gen_heisenberg_repr (perms[g*n_sites + site], g = 0 the identity, 1 .. 64 of them, chars[2g], chars[2g+1] = Re, Im of
+ * chi_k(g)).  The merged terms must be invariant under every translation -- the pair on (g(i), g(j)) carries the matrix of
+ * (i, j), transposed when g swaps the order, and the single-site diagonals of s and g(s) agree -- else QBH_EINVAL.
+ * Basis: ALL orbit representatives (the smallest packed word of the orbit; words packed as in qbh_gen_qudit, so their
+ * integer order is its rank order), ascending; a representative whose character sum over its stabiliser vanishes stays as a
+ * decoupled row holding only the fake diagonal fake_pos + i/dim.  At d = 2 with level 1 = down this is the basis of
+ * qbh_gen_heisenberg_repr.  Row a: O[a][b] = sum of <a|M|c> conj(chi(g*)) sqrt(|S_b|/|S_a|) over the pair entries that take
+ * a to a word c with representative b = g* c; duplicates merged, cancelled entries and zero-norm targets dropped, columns
+ * ascending.  Shards, row_cuts, value coding and adoption as in qbh_gen_heisenberg_repr(_cuts).  Limits of qbh_gen_qudit,
+ * except that a row may hold at most 160 entries counted from the merged terms, and a sector of 2^40 words or more cannot be
+ * enumerated (QBH_EUNSUPP).  Every argument and term check runs before the device is looked for. */
+int qbh_gen_qudit_repr(qbh_csr **out, int n_sites, int d, int total,
+                       int n_pairs, const int32_t *pair_sites, const qbh_z *pair_mat,
+                       int n_single, const int32_t *single_sites, const double *single_diag,
+                       int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                       int shard, int n_shards, int64_t *dim_out, const qbh_opts *opts);
+/* ... with the caller's row cuts (see qbh_gen_heisenberg_repr_cuts) */
+int qbh_gen_qudit_repr_cuts(qbh_csr **out, int n_sites, int d, int total,
+                            int n_pairs, const int32_t *pair_sites, const qbh_z *pair_mat,
+                            int n_single, const int32_t *single_sites, const double *single_diag,
+                            int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                            int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts);
+/* moprXvec_repr (src/model.cc:1715-1846) for O_q = sum_s coef[s] O_s between momentum sectors of qbh_gen_qudit_repr: local as
+ * in qbh_mopr_qudit_dev (nonzero only where l' = l + dq, else QBH_EINVAL).  coef must transform with a character,
+ * coef[g(s)] = eta(g) coef[s] for every translation (else QBH_EINVAL); the operator maps the sector (total_old, chars_old)
+ * to (total_old + dq, chars_old * eta).  Both vectors are device vectors indexed like the rows of the sector operators;
+ * every target row gathers its contributions (no atomics, deterministic), and target rows of zero norm get 0.
+ * *dim_old_out, *dim_new_out (may be NULL) receive the two sector dimensions. */
+int qbh_mopr_qudit_repr_dev(int n_sites, int d, int total_old, int dq, int n_trans, const int32_t *perms,
+                            const double *chars_old, const qbh_z *coef /* [n_sites] */, const qbh_z *local /* [d*d] */,
+                            const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out,
+                            void *stream);
 /* Measurement harness (SURVEY 7 hard-part 1): the operator of qbh_gen_heisenberg (kind 0) / qbh_gen_hubbard (kind 1), built with
  * complex128 values on one GPU, re-expressed ON THE DEVICE in the reference's own basis order and fermion convention, i.e.
  * exactly the matrix the unchanged host code assembles (src/model.cc:619-685) at sizes that code cannot reach: basis sorted

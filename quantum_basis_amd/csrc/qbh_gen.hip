@@ -25,6 +25,7 @@
 
 #include "qbh_internal.hpp"
 #include "qbh_dict.hpp"
+#include "qbh_qudit.hpp"
 
 namespace qbh {
 namespace {
@@ -900,11 +901,12 @@ struct ReprDev {
 };
 
 // the symmetry tables of a momentum sector: checks that translation 0 is the identity and every translation a site
-// permutation, fills the binomials and the characters, stores the permutations in perm8 (perm8[g * n_sites + site]) unless
-// it is null and builds the chunk tables tab[(g*n_chunks + c)*64 + v] = scattered bits of chunk c with value v under g.
+// permutation, fills the binomials (unless binom is null) and the characters, stores the permutations in perm8
+// (perm8[g * n_sites + site]) unless it is null and builds the chunk tables tab[(g*n_chunks + c)*64 + v] = scattered bits
+// of chunk c with value v under g.  A site holds `bits` bits (1, 2 or 3), so a 6-bit chunk holds 6 / bits whole sites.
 // `who` prefixes error messages.
 int sector_symmetry(int n_sites, int n_trans, const int32_t *perms, const double *chars, const char *who, uint64_t (*binom)[34],
-                    double *chr, int8_t *perm8, int &n_chunks, std::vector<uint64_t> &tab)
+                    double *chr, int8_t *perm8, int &n_chunks, std::vector<uint64_t> &tab, int bits = 1)
 {
     for (int i = 0; i < n_sites; ++i)
         if (perms[i] != i) {
@@ -922,21 +924,25 @@ int sector_symmetry(int n_sites, int n_trans, const int32_t *perms, const double
             if (perm8) perm8[g * n_sites + s] = (int8_t)img;
         }
     }
-    for (int p = 0; p <= 64; ++p)
-        for (int k = 0; k <= 33; ++k) binom[p][k] = binom_u64(p, k);
+    if (binom)
+        for (int p = 0; p <= 64; ++p)
+            for (int k = 0; k <= 33; ++k) binom[p][k] = binom_u64(p, k);
     for (int g = 0; g < n_trans; ++g) {
         chr[2 * g] = chars[2 * g];
         chr[2 * g + 1] = chars[2 * g + 1];
     }
-    n_chunks = (n_sites + 5) / 6;
+    const int per = 6 / bits;                 // sites per chunk
+    const uint64_t field = (1ULL << bits) - 1ULL;
+    n_chunks = (n_sites + per - 1) / per;
     tab.assign((size_t)n_trans * n_chunks * 64, 0ULL);
     for (int g = 0; g < n_trans; ++g)
         for (int c = 0; c < n_chunks; ++c)
             for (int v = 0; v < 64; ++v) {
                 uint64_t m = 0;
-                for (int b = 0; b < 6; ++b) {
-                    const int site = 6 * c + b;
-                    if (site < n_sites && ((v >> b) & 1)) m |= 1ULL << perms[(size_t)g * n_sites + site];
+                for (int b = 0; b < per; ++b) {
+                    const int site = per * c + b;
+                    const uint64_t l = ((uint64_t)v >> (b * bits)) & field;
+                    if (site < n_sites && l) m |= l << (perms[(size_t)g * n_sites + site] * bits);
                 }
                 tab[((size_t)g * n_chunks + c) * 64 + v] = m;
             }
@@ -1677,6 +1683,252 @@ template <class Dev> constexpr int max_row = 0;
 template <> constexpr int max_row<ReprDev> = kReprMaxRow;
 template <> constexpr int max_row<HubReprDev> = kHubReprMaxRow;
 
+// ------------------------------------ d-level sites in translation-symmetric sectors (qbh_gen_qudit_repr) --
+// Words packed as in qbh_gen_qudit (site s in bits [s b, (s+1) b), qbh_qudit.hpp), so the chunk tables of sector_symmetry
+// with `bits` = b translate them and the integer order of the words is the generator's order.  Basis: ALL orbit
+// representatives (smallest image) of the charge-`total` words, ascending; zero-norm ones are decoupled fake rows.  Row a:
+//     O[a][b] = sum over the pair entries <a|M|c> that move a to c, b = g* c:  <a|M|c> * conj(chi(g*)) * sqrt(|S_b|/|S_a|)
+// (the Heisenberg convention above; no signs: bosons and spins).
+constexpr int kQuditReprMaxRow = 160;     // entries of one row before merging, counted from the merged terms
+
+struct QuditReprDev {
+    int n_sites, d, bits, total, tw, n_pairs, n_trans, n_chunks;
+    double chr[2 * kReprMaxTrans];
+    double fake_pos;
+    const uint64_t *cum;                  // [n_sites * tw], qudit_table
+    const int32_t *pair_ij, *eoff, *eout; // the term tables of QuditTerms
+    const double *pdiag, *sdiag;
+    const d2 *eval;
+};
+template <> constexpr int max_row<QuditReprDev> = kQuditReprMaxRow;
+
+__device__ __forceinline__ uint64_t qrepr_canonical(const QuditReprDev &R, const uint64_t *tab, uint64_t s, int *gstar)
+{
+    uint64_t best = s;
+    int gb = 0;
+    for (int g = 1; g < R.n_trans; ++g) {
+        const uint64_t t = repr_translate(tab, R.n_chunks, g, s);
+        if (t < best) {
+            best = t;
+            gb = g;
+        }
+    }
+    *gstar = gb;
+    return best;
+}
+
+// pass 1 over the words of the sector in ascending order, one workgroup per chunk of kHubChunk consecutive words (the
+// layout of k_hubrepr_flag: one code byte per word, one count per chunk).  A lane unranks the first of its kHubRun words
+// and steps to the next word of the same charge from there.
+__global__ __launch_bounds__(256) void k_qrepr_flag(const QuditReprDev *Rp, const uint64_t *tab, int64_t nstates, uint8_t *code,
+                                                    int32_t *chunk_cnt, int64_t nchunks)
+{
+    const QuditReprDev &R = *Rp;
+    __shared__ int wsum[4];
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int64_t r0 = chunk * kHubChunk + (int64_t)threadIdx.x * kHubRun;
+        const int64_t r1 = (r0 + kHubRun < nstates) ? r0 + kHubRun : nstates;
+        int mine = 0;
+        if (r0 < nstates) {
+            uint64_t s = qd_unrank(R.cum, R.n_sites, R.d, R.bits, R.tw, R.total, (uint64_t)r0);
+            for (int64_t r = r0; r < r1; ++r) {
+                bool rep = true;
+                int nstab = 1;
+                double sr = R.chr[0], si = R.chr[1];
+                for (int g = 1; g < R.n_trans; ++g) {
+                    const uint64_t t = repr_translate(tab, R.n_chunks, g, s);
+                    if (t < s) {
+                        rep = false;
+                        break;
+                    }
+                    if (t == s) {
+                        nstab++;
+                        sr += R.chr[2 * g];
+                        si += R.chr[2 * g + 1];
+                    }
+                }
+                code[r] = rep ? (uint8_t)(nstab | ((sr * sr + si * si < 1e-20) ? 0x80 : 0)) : 0;
+                mine += rep ? 1 : 0;
+                s = qd_next(s, R.n_sites, R.d, R.bits);
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
+        __syncthreads();
+        if (threadIdx.x == 0) chunk_cnt[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+
+// pass 2: the representatives of a chunk go to reps[chunk_pos[chunk] ...] in ascending order
+__global__ __launch_bounds__(256) void k_qrepr_compact(const QuditReprDev *Rp, int64_t nstates, const uint8_t *code,
+                                                       const int64_t *chunk_pos, int64_t nchunks, uint64_t *reps, uint8_t *info)
+{
+    const QuditReprDev &R = *Rp;
+    __shared__ int scan[256];
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int64_t r0 = chunk * kHubChunk + (int64_t)threadIdx.x * kHubRun;
+        const int64_t r1 = (r0 + kHubRun < nstates) ? r0 + kHubRun : nstates;
+        int mine = 0;
+        for (int64_t r = r0; r < r1; ++r) mine += code[r] ? 1 : 0;
+        __syncthreads();
+        scan[threadIdx.x] = mine;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {          // inclusive Hillis-Steele scan
+            const int v = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
+            __syncthreads();
+            scan[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (mine == 0) continue;
+        int64_t at = chunk_pos[chunk] + scan[threadIdx.x] - mine;
+        uint64_t s = qd_unrank(R.cum, R.n_sites, R.d, R.bits, R.tw, R.total, (uint64_t)r0);
+        for (int64_t r = r0; r < r1; ++r) {
+            if (code[r]) {
+                reps[at] = s;
+                info[at] = code[r];
+                ++at;
+            }
+            s = qd_next(s, R.n_sites, R.d, R.bits);
+        }
+    }
+}
+
+// position of representative b in the ascending list reps[0, dim)
+__device__ __forceinline__ int64_t qrepr_find(const uint64_t *reps, int64_t dim, uint64_t b)
+{
+    int64_t lo = 0, hi = dim;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (reps[mid] < b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one row of the sector operator into (cols, vals), columns ascending, duplicates merged; returns its length
+__device__ int qrepr_row(const QuditReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
+                         int32_t *cols, d2 *vals)
+{
+    const uint8_t ci = info[i];
+    if (ci & 0x80) {
+        cols[0] = (int32_t)i;
+        vals[0] = d2{R.fake_pos + (double)i / (double)dim, 0.0};
+        return 1;
+    }
+    const double sa = (double)(ci & 0x7f);
+    const uint64_t a = reps[i];
+    const int d2n = R.d * R.d;
+    const uint64_t field = (1ULL << R.bits) - 1ULL;
+    int n = 1;
+    cols[0] = (int32_t)i;
+    d2 dg = {0.0, 0.0};
+    for (int s = 0; s < R.n_sites; ++s) dg.x += R.sdiag[s * R.d + qd_level(a, R.bits, s)];
+    for (int p = 0; p < R.n_pairs; ++p) {
+        const int ij = R.pair_ij[p];
+        const int si = ij & 0xff, sj = ij >> 8;
+        const int in = qd_level(a, R.bits, si) * R.d + qd_level(a, R.bits, sj);
+        dg.x += R.pdiag[p * d2n + in];
+        const int e1 = R.eoff[p * d2n + in + 1];
+        for (int e = R.eoff[p * d2n + in]; e < e1; ++e) {
+            const int o = R.eout[e];
+            const uint64_t c = (a & ~((field << (si * R.bits)) | (field << (sj * R.bits)))) | ((uint64_t)(o & 0xff) << (si * R.bits)) |
+                               ((uint64_t)(o >> 8) << (sj * R.bits));
+            int g = 0;
+            const uint64_t b = qrepr_canonical(R, tab, c, &g);
+            const int64_t lo = qrepr_find(reps, dim, b);
+            const uint8_t cj = info[lo];
+            if (cj & 0x80) continue;      // zero-norm target: dropped
+            const double f = sqrt((double)(cj & 0x7f) / sa);
+            const d2 h = R.eval[e];
+            const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];        // conj(chi(g*)) * sqrt(|S_b|/|S_a|)
+            const d2 v = {h.x * cr - h.y * cim, h.x * cim + h.y * cr};
+            if (lo == i) {
+                dg += v;
+                continue;
+            }
+            int q = 1;
+            while (q < n && cols[q] != (int32_t)lo) ++q;
+            if (q < n) {
+                vals[q] += v;
+            } else if (n < kQuditReprMaxRow) {
+                cols[n] = (int32_t)lo;
+                vals[n] = v;
+                ++n;
+            }
+        }
+    }
+    vals[0] = dg;
+    int m = 1;                            // drop cancelled off-diagonal entries, then sort by column
+    for (int q = 1; q < n; ++q)
+        if (vals[q].x * vals[q].x + vals[q].y * vals[q].y >= 1e-28) {
+            cols[m] = cols[q];
+            vals[m] = vals[q];
+            ++m;
+        }
+    for (int q = 1; q < m; ++q) {
+        const int32_t c = cols[q];
+        const d2 v = vals[q];
+        int p = q - 1;
+        while (p >= 0 && cols[p] > c) {
+            cols[p + 1] = cols[p];
+            vals[p + 1] = vals[p];
+            --p;
+        }
+        cols[p + 1] = c;
+        vals[p + 1] = v;
+    }
+    return m;
+}
+
+__device__ __forceinline__ int sector_row(const QuditReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
+                                          int64_t dim, int64_t i, int32_t *cols, d2 *vals)
+{
+    return qrepr_row(R, tab, reps, info, dim, i, cols, vals);
+}
+
+// moprXvec_repr (src/model.cc:1715-1846) for O_q = sum_s c_s O_s with c_{g(s)} = eta(g) c_s, from the sector (total, chi)
+// to (total + dq, chi eta), gathered by TARGET row b: the entry for the source word c = b with the level of site s lowered
+// by dq, a = g* c its representative, is  c_s <b_s|O|c_s> conj(chi(g*)) sqrt(|S_a| / |S_b|)  (the row formula of the sector
+// operators with the source sector's characters).  Zero-norm targets get 0, zero-norm sources are skipped.
+__global__ __launch_bounds__(256) void k_qrepr_mopr(const QuditReprDev *Rold, const uint64_t *tab, const uint64_t *reps_old,
+                                                    const uint8_t *info_old, int64_t dim_old, const uint64_t *reps_new,
+                                                    const uint8_t *info_new, int64_t dim_new, int dq, QuditMopr cf, const d2 *x_old,
+                                                    d2 *y_new)
+{
+    const QuditReprDev &R = *Rold;
+    const uint64_t field = (1ULL << R.bits) - 1ULL;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < dim_new; i += stride) {
+        const uint8_t cb = info_new[i];
+        double ar = 0.0, ai = 0.0;
+        if (!(cb & 0x80)) {
+            const uint64_t b = reps_new[i];
+            const double sb = (double)(cb & 0x7f);
+            for (int s = 0; s < R.n_sites; ++s) {
+                const int l = qd_level(b, R.bits, s), ls = l - dq;
+                if (ls < 0 || ls >= R.d) continue;
+                const double lr = cf.la[l], li = cf.lb[l];
+                if ((lr == 0.0 && li == 0.0) || (cf.ca[s] == 0.0 && cf.cb[s] == 0.0)) continue;
+                const uint64_t c = (b & ~(field << (s * R.bits))) | ((uint64_t)ls << (s * R.bits));
+                int g = 0;
+                const uint64_t a = qrepr_canonical(R, tab, c, &g);
+                const int64_t lo = qrepr_find(reps_old, dim_old, a);
+                const uint8_t ca = info_old[lo];
+                if (ca & 0x80) continue;
+                const double f = sqrt((double)(ca & 0x7f) / sb);
+                const double wr0 = cf.ca[s] * lr - cf.cb[s] * li, wi0 = cf.ca[s] * li + cf.cb[s] * lr;
+                const double xr = f * R.chr[2 * g], xi = -f * R.chr[2 * g + 1];
+                const double wr = wr0 * xr - wi0 * xi, wi = wr0 * xi + wi0 * xr;
+                const d2 x = x_old[lo];
+                ar += wr * x.x - wi * x.y;
+                ai += wr * x.y + wi * x.x;
+            }
+        }
+        y_new[i] = d2{ar, ai};
+    }
+}
+
 // row lengths of rows [r0, r1); with T.fp != nullptr the distinct values met on the way are collected for the value
 // dictionary, so that the fill pass can emit 1- or 2-byte codes and the 16 B/nnz value array never exists
 template <class Dev>
@@ -1816,6 +2068,114 @@ int merge_terms(int n_sites, int n_terms, const int32_t *term_sites, const qbh_z
         set_error("%s: too many distinct one-body terms (%d on %d site pairs)", who, (int)tmap.size(), (int)pairs.size());
         return QBH_EUNSUPP;
     }
+    return QBH_OK;
+}
+
+// R zeroed, then the symmetry part of the d-level sector of charge `total` filled in (the terms are the caller's)
+int qrepr_symmetry(QuditReprDev &R, std::vector<uint64_t> &tab, int n_sites, int d, int total, int n_trans, const int32_t *perms,
+                   const double *chars, const char *who)
+{
+    memset(&R, 0, sizeof(R));
+    R.n_sites = n_sites;
+    R.d = d;
+    R.bits = bits_per_level(d);
+    R.total = total;
+    R.tw = total + 1;
+    R.n_trans = n_trans;
+    return sector_symmetry(n_sites, n_trans, perms, chars, who, nullptr, R.chr, nullptr, R.n_chunks, tab, R.bits);
+}
+
+// the sector matrix is only right for an operator that commutes with every translation: the pair on (g(i), g(j)) must carry
+// the matrix of (i, j) (transposed when g swaps the order) and the single-site diagonals of s and g(s) must agree
+int qrepr_invariant(const QuditTerms &T, int n_sites, int d, int n_trans, const int32_t *perms, const char *who)
+{
+    const int d2n = d * d;
+    const std::vector<std::complex<double>> zero((size_t)d2n * d2n, 0.0);
+    auto close = [](std::complex<double> x, std::complex<double> y) {
+        return std::abs(x - y) <= QBH_SPARSE_PRECISION * std::max(1.0, std::max(std::abs(x), std::abs(y)));
+    };
+    for (int g = 1; g < n_trans; ++g) {
+        const int32_t *pg = perms + (size_t)g * n_sites;
+        for (const auto &kv : T.pm) {
+            const int gi = pg[kv.first.first], gj = pg[kv.first.second];
+            const auto it = T.pm.find({std::min(gi, gj), std::max(gi, gj)});
+            const std::vector<std::complex<double>> &img = it == T.pm.end() ? zero : it->second;
+            for (int r = 0; r < d2n; ++r)
+                for (int c = 0; c < d2n; ++c) {
+                    const int rr = gi < gj ? r : (r % d) * d + r / d, cc = gi < gj ? c : (c % d) * d + c / d;
+                    if (!close(kv.second[(size_t)r * d2n + c], img[(size_t)rr * d2n + cc])) {
+                        set_error("%s: the terms are not invariant under translation %d: pair (%d, %d) and its image (%d, %d) differ",
+                                  who, g, kv.first.first, kv.first.second, gi, gj);
+                        return QBH_EINVAL;
+                    }
+                }
+        }
+        for (int s = 0; s < n_sites; ++s)
+            for (int l = 0; l < d; ++l)
+                if (!close(T.sdiag[(size_t)s * d + l], T.sdiag[(size_t)pg[s] * d + l])) {
+                    set_error("%s: the single-site terms are not invariant under translation %d: site %d and its image %d differ", who,
+                              g, s, pg[s]);
+                    return QBH_EINVAL;
+                }
+    }
+    return QBH_OK;
+}
+
+// number of words of the sector, refused beyond what one code byte per word can enumerate
+int qrepr_words(int n_sites, int d, int total, int64_t *nstates, const char *who)
+{
+    std::vector<uint64_t> cum, dims;
+    qudit_table(n_sites, d, total + 1, cum, dims);
+    if (dims[(size_t)total] >= (1ULL << 40)) {
+        set_error("%s: sector too large to enumerate (%llu words)", who, (unsigned long long)dims[(size_t)total]);
+        return QBH_EUNSUPP;
+    }
+    *nstates = (int64_t)dims[(size_t)total];
+    return QBH_OK;
+}
+
+// representatives (ascending) and their info bytes of the sector described by R (its term pointers already set, or unused);
+// the counting table, d_R, d_tab, d_reps and d_info join `pool`
+int qrepr_enumerate(const QuditReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, QuditReprDev **d_R_out,
+                    uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
+{
+    int64_t nstates = 0;
+    QBH_TRY(qrepr_words(R.n_sites, R.d, R.total, &nstates, who));
+    std::vector<uint64_t> cum, dims;
+    qudit_table(R.n_sites, R.d, R.tw, cum, dims);
+    std::vector<QuditReprDev> rr(1, R);
+    uint64_t *d_cum = nullptr;
+    QBH_TRY(upload(cum, &d_cum, pool));
+    rr[0].cum = d_cum;
+    QBH_TRY(upload(rr, d_R_out, pool));
+    QBH_TRY(upload(tab, d_tab_out, pool));
+    const int64_t nchunks = (nstates + kHubChunk - 1) / kHubChunk;
+    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
+    DevBufs tmp;
+    uint8_t *d_code = nullptr;
+    int32_t *d_cnt = nullptr;
+    int64_t *d_pos = nullptr;
+    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
+    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
+    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
+    hipLaunchKernelGGL(k_qrepr_flag, dim3(egrid), dim3(256), 0, 0, *d_R_out, *d_tab_out, nstates, d_code, d_cnt, nchunks);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_TRY(exclusive_scan(d_cnt, nchunks, d_pos, 0));
+    int64_t dim = 0;
+    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (dim <= 0 || dim >= 2147483647LL) {
+        set_error("%s: sector dimension %lld out of range", who, (long long)dim);
+        return QBH_EUNSUPP;
+    }
+    QBH_HIP_WHO(who, qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
+    pool.push_back(*d_reps_out);
+    QBH_HIP_WHO(who, qbh::dev_alloc(d_info_out, (size_t)dim));
+    pool.push_back(*d_info_out);
+    hipLaunchKernelGGL(k_qrepr_compact, dim3(egrid), dim3(256), 0, 0, *d_R_out, nstates, d_code, d_pos, nchunks, *d_reps_out,
+                       *d_info_out);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    *dim_out = dim;
     return QBH_OK;
 }
 
@@ -2056,6 +2416,166 @@ static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn,
     if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
     free_pool(pool);
     return rc;
+}
+
+// ------------------------------ d-level sites in momentum sectors: qbh_gen_qudit_repr, qbh_mopr_qudit_repr_dev --
+static int gen_qudit_repr_impl(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
+                               const qbh_z *pair_mat, int n_single, const int32_t *single_sites, const double *single_diag,
+                               int n_trans, const int32_t *perms, const double *chars, double fake_pos, int shard, int n_shards,
+                               const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    const char *who = "qbh_gen_qudit_repr";
+    if (!out) {
+        set_error("%s: out is NULL", who);
+        return QBH_EINVAL;
+    }
+    QBH_TRY(qudit_check_shape(who, n_sites, d));
+    if (total < 0 || total > n_sites * (d - 1) || n_pairs < 0 || n_single < 0 || (n_pairs > 0 && (!pair_sites || !pair_mat)) ||
+        (n_single > 0 && (!single_sites || !single_diag))) {
+        set_error("%s: invalid charge %d (0 .. %d) or term arrays", who, total, n_sites * (d - 1));
+        return QBH_EINVAL;
+    }
+    if (!perms || !chars || n_trans < 1 || n_trans > kReprMaxTrans || n_shards < 1 || shard < 0 || shard >= n_shards) {
+        set_error("%s: invalid symmetry or shard argument (1 .. %d translations)", who, kReprMaxTrans);
+        return QBH_EINVAL;
+    }
+    QuditTerms T;
+    QBH_TRY(qudit_merge_terms(who, n_sites, d, n_pairs, pair_sites, pair_mat, n_single, single_sites, single_diag, T));
+    QuditReprDev R;
+    std::vector<uint64_t> tab;
+    QBH_TRY(qrepr_symmetry(R, tab, n_sites, d, total, n_trans, perms, chars, who));
+    QBH_TRY(qrepr_invariant(T, n_sites, d, n_trans, perms, who));
+    if (T.max_row > kQuditReprMaxRow) {
+        set_error("%s: a row may hold %d entries; at most %d are supported", who, T.max_row, kQuditReprMaxRow);
+        return QBH_EUNSUPP;
+    }
+    int64_t nstates = 0;
+    QBH_TRY(qrepr_words(n_sites, d, total, &nstates, who));
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_HIP_WHO(who, hipSetDevice(opts->device));
+    R.n_pairs = (int)T.pm.size();
+    R.fake_pos = fake_pos;
+    std::vector<void *> pool;
+    int32_t *pij = nullptr, *eo = nullptr, *eu = nullptr;
+    double *pd = nullptr, *sd = nullptr;
+    d2 *ev = nullptr;
+    int rc = upload(T.pair_ij, &pij, pool);
+    if (rc == QBH_OK) rc = upload(T.eoff, &eo, pool);
+    if (rc == QBH_OK) rc = upload(T.eout, &eu, pool);
+    if (rc == QBH_OK) rc = upload(T.pdiag, &pd, pool);
+    if (rc == QBH_OK) rc = upload(T.sdiag, &sd, pool);
+    if (rc == QBH_OK) rc = upload(T.eval, &ev, pool);
+    R.pair_ij = pij; R.eoff = eo; R.eout = eu; R.pdiag = pd; R.sdiag = sd; R.eval = ev;
+    QuditReprDev *d_R = nullptr;
+    uint64_t *d_tab = nullptr, *d_reps = nullptr;
+    uint8_t *d_info = nullptr;
+    int64_t dim = 0;
+    if (rc == QBH_OK) rc = qrepr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, who);
+    if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
+    free_pool(pool);
+    return rc;
+}
+
+extern "C" int qbh_gen_qudit_repr(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
+                                  const qbh_z *pair_mat, int n_single, const int32_t *single_sites, const double *single_diag,
+                                  int n_trans, const int32_t *perms, const double *chars, double fake_pos, int shard, int n_shards,
+                                  int64_t *dim_out, const qbh_opts *opts)
+{
+    return gen_qudit_repr_impl(out, n_sites, d, total, n_pairs, pair_sites, pair_mat, n_single, single_sites, single_diag, n_trans,
+                               perms, chars, fake_pos, shard, n_shards, nullptr, dim_out, opts);
+}
+
+extern "C" int qbh_gen_qudit_repr_cuts(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
+                                       const qbh_z *pair_mat, int n_single, const int32_t *single_sites, const double *single_diag,
+                                       int n_trans, const int32_t *perms, const double *chars, double fake_pos, int shard,
+                                       int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
+{
+    return gen_qudit_repr_impl(out, n_sites, d, total, n_pairs, pair_sites, pair_mat, n_single, single_sites, single_diag, n_trans,
+                               perms, chars, fake_pos, shard, n_shards, row_cuts, dim_out, opts);
+}
+
+// see k_qrepr_mopr; the target characters chi_old * eta follow from coef
+extern "C" int qbh_mopr_qudit_repr_dev(int n_sites, int d, int total_old, int dq, int n_trans, const int32_t *perms,
+                                       const double *chars_old, const qbh_z *coef, const qbh_z *local, const qbh_z *d_vec_old,
+                                       qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out, void *stream)
+{
+    using namespace qbh;
+    const char *who = "qbh_mopr_qudit_repr_dev";
+    QBH_TRY(qudit_check_shape(who, n_sites, d));
+    const int total_new = total_old + dq;
+    if (!perms || !chars_old || !coef || !local || !d_vec_old || !d_vec_new || total_old < 0 || total_old > n_sites * (d - 1) ||
+        total_new < 0 || total_new > n_sites * (d - 1) || n_trans < 1 || n_trans > kReprMaxTrans) {
+        set_error("%s: invalid argument (charge %d -> %d of at most %d, 1 .. %d translations)", who, total_old, total_new,
+                  n_sites * (d - 1), kReprMaxTrans);
+        return QBH_EINVAL;
+    }
+    QuditMopr cf{};
+    for (int lp = 0; lp < d; ++lp)
+        for (int l = 0; l < d; ++l) {
+            const qbh_z z = local[lp * d + l];
+            if (z.re == 0.0 && z.im == 0.0) continue;
+            if (lp != l + dq) {
+                set_error("%s: local[%d][%d] is nonzero but does not change the level by dq = %d", who, lp, l, dq);
+                return QBH_EINVAL;
+            }
+            cf.la[lp] = z.re;
+            cf.lb[lp] = z.im;
+        }
+    for (int s = 0; s < n_sites; ++s) {
+        cf.ca[s] = coef[s].re;
+        cf.cb[s] = coef[s].im;
+    }
+    QuditReprDev Ro, Rn;
+    std::vector<uint64_t> tab, tab_n;
+    QBH_TRY(qrepr_symmetry(Ro, tab, n_sites, d, total_old, n_trans, perms, chars_old, who));
+    // eta(g) = c_{g(s)} / c_s from the largest coefficient, then c_{g(s)} = eta(g) c_s checked on every site
+    std::vector<std::complex<double>> c(n_sites);
+    int s0 = 0;
+    for (int s = 0; s < n_sites; ++s) {
+        c[s] = std::complex<double>(coef[s].re, coef[s].im);
+        if (std::abs(c[s]) > std::abs(c[s0])) s0 = s;
+    }
+    const double cmax = std::abs(c[s0]);
+    std::vector<double> chars_new((size_t)2 * n_trans);
+    for (int g = 0; g < n_trans; ++g) {
+        const int32_t *pg = perms + (size_t)g * n_sites;
+        const std::complex<double> eta = cmax > 0.0 ? c[pg[s0]] / c[s0] : 1.0;
+        for (int s = 0; s < n_sites; ++s)
+            if (std::abs(c[pg[s]] - eta * c[s]) > 1e-12 * cmax) {
+                set_error("%s: coef does not transform with a character under translation %d (site %d)", who, g, s);
+                return QBH_EINVAL;
+            }
+        const std::complex<double> chi = std::complex<double>(chars_old[2 * g], chars_old[2 * g + 1]) * eta;
+        chars_new[2 * g] = chi.real();
+        chars_new[2 * g + 1] = chi.imag();
+    }
+    QBH_TRY(qrepr_symmetry(Rn, tab_n, n_sites, d, total_new, n_trans, perms, chars_new.data(), who));
+    int64_t nst = 0;
+    QBH_TRY(qrepr_words(n_sites, d, total_old, &nst, who));
+    QBH_TRY(qrepr_words(n_sites, d, total_new, &nst, who));
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    DevBufs bufs;
+    QuditReprDev *R_old = nullptr, *R_new = nullptr;
+    uint64_t *tab_old = nullptr, *tab_new = nullptr, *reps_old = nullptr, *reps_new = nullptr;
+    uint8_t *info_old = nullptr, *info_new = nullptr;
+    int64_t dim_old = 0, dim_new = 0;
+    QBH_TRY(qrepr_enumerate(Ro, tab, bufs.pool, &R_old, &tab_old, &reps_old, &info_old, &dim_old, who));
+    QBH_TRY(qrepr_enumerate(Rn, tab_n, bufs.pool, &R_new, &tab_new, &reps_new, &info_new, &dim_new, who));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_qrepr_mopr, dim3(blas_grid(dim_new)), dim3(256), 0, st, R_old, tab_old, reps_old, info_old, dim_old, reps_new,
+                       info_new, dim_new, dq, cf, reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipStreamSynchronize(st));
+    if (dim_old_out) *dim_old_out = dim_old;
+    if (dim_new_out) *dim_new_out = dim_new;
+    return QBH_OK;
 }
 
 // ------------------------- diagonal one-body operators between Hubbard momentum sectors --

@@ -18,35 +18,13 @@
 #include <vector>
 
 #include "qbh_internal.hpp"
+#include "qbh_qudit.hpp"
 
 namespace qbh {
 namespace {
 
-constexpr int kQuditMaxD = 8;
-constexpr int kQuditMaxPairs = 1024;     // merged (unordered) site pairs
 constexpr int kQuditMaxRow = 240;        // entries of one row, diagonal included (the fill kernel stages 64 rows in LDS)
 constexpr int kQuditFillBlock = 64;      // one wave per workgroup in the fill kernel: lane = row, LDS column = lane
-
-int bits_per_level(int d) { return d <= 2 ? 1 : d <= 4 ? 2 : 3; }
-
-// cum[s * tw + q] for s < n_sites, q < tw; *dims = cnt[n_sites][q] (the dimension of every sector q < tw)
-void qudit_table(int n_sites, int d, int tw, std::vector<uint64_t> &cum, std::vector<uint64_t> &dims)
-{
-    std::vector<uint64_t> cnt((size_t)tw, 0), nxt((size_t)tw);
-    cnt[0] = 1;
-    cum.assign((size_t)n_sites * tw, 0);
-    for (int s = 0; s < n_sites; ++s) {
-        uint64_t acc = 0;
-        for (int q = 0; q < tw; ++q) cum[(size_t)s * tw + q] = (acc += cnt[q]);
-        for (int q = 0; q < tw; ++q) {
-            uint64_t v = 0;
-            for (int l = 0; l < d && l <= q; ++l) v += cnt[q - l];
-            nxt[q] = v;
-        }
-        cnt.swap(nxt);
-    }
-    dims = cnt;
-}
 
 struct QuditDev {
     int n_sites, d, bits, total, tw, n_pairs, max_row;
@@ -59,11 +37,6 @@ struct QuditDev {
     const double *sdiag;        // [n_sites * d] single-site diagonal
 };
 
-__device__ __forceinline__ int qd_level(uint64_t w, int bits, int s)
-{
-    return (int)((w >> (s * bits)) & ((1ULL << bits) - 1));
-}
-
 // charge of sites 0..s
 __device__ __forceinline__ int qd_charge(uint64_t w, int bits, int s)
 {
@@ -73,23 +46,6 @@ __device__ __forceinline__ int qd_charge(uint64_t w, int bits, int s)
     if (bits == 2) return __popcll(w & 0x5555555555555555ULL) + 2 * __popcll(w & 0xAAAAAAAAAAAAAAAAULL);
     const uint64_t m0 = 0x9249249249249249ULL;          // bit 0 of every 3-bit field
     return __popcll(w & m0) + 2 * __popcll(w & (m0 << 1)) + 4 * __popcll(w & (m0 << 2));
-}
-
-// the word of rank r among the words of charge `total` (walks from the most significant site down)
-__device__ __forceinline__ uint64_t qd_unrank(const uint64_t *cum, int n_sites, int d, int bits, int tw, int total, uint64_t r)
-{
-    uint64_t w = 0;
-    int Q = total;
-    for (int s = n_sites - 1; s >= 0; --s) {
-        const uint64_t *c = cum + s * tw;
-        const uint64_t top = c[Q];
-        int l = min(d - 1, Q);
-        while (l > 0 && top - c[Q - l] > r) --l;          // largest level whose smaller siblings hold <= r words
-        r -= top - c[Q - l];
-        Q -= l;
-        w |= (uint64_t)l << (s * bits);
-    }
-    return w;
 }
 
 // rank(new) - rank(old) for the move (l_i, l_j) -> (ni, nj) on sites i < j of w, Q = charge of sites 0..j (mod 2^64)
@@ -199,7 +155,6 @@ __global__ __launch_bounds__(kQuditFillBlock) void k_qudit_fill(QuditDev h, int6
 // The old rank is (contributions of the sites below s, charges unchanged) + (site s) + (sites above s, charges shifted by
 // -dq): the shifted sum is formed over all sites first and the sites <= s are taken out of it on the way up.  Indices of
 // terms that are taken out again or never used may leave [0, qmax]: they are clamped, never read out of the table.
-struct QuditMopr { double ca[64], cb[64]; double la[kQuditMaxD], lb[kQuditMaxD]; };
 
 __global__ __launch_bounds__(256) void k_qudit_mopr(int n_sites, int d, int bits, int tw, int total_new, int dq, QuditMopr cf,
                                                     const uint64_t *cum_g, const d2 *x_old, d2 *y_new, int64_t dim_new)
@@ -242,9 +197,23 @@ __global__ __launch_bounds__(256) void k_qudit_mopr(int n_sites, int d, int bits
 }
 
 // ------------------------------------------------------------------------------------------------------- host side --
-struct PairMat { std::vector<std::complex<double>> m; };      // d^2 x d^2, row = out, column = in
+struct HipFree {
+    std::vector<void *> p;
+    ~HipFree() { for (void *q : p) (void)hipFree(q); }
+};
 
-int check_shape(const char *who, int n_sites, int d)
+template <typename T>
+hipError_t up(HipFree &pool, T **d, const std::vector<T> &h)
+{
+    hipError_t e = qbh::dev_alloc(d, std::max<size_t>(h.size(), 1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    pool.p.push_back(*d);
+    return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+}  // namespace
+
+int qudit_check_shape(const char *who, int n_sites, int d)
 {
     if (n_sites <= 0 || d < 2) {
         set_error("%s: need n_sites >= 1 and d >= 2 (got %d, %d)", who, n_sites, d);
@@ -261,21 +230,82 @@ int check_shape(const char *who, int n_sites, int d)
     return QBH_OK;
 }
 
-struct HipFree {
-    std::vector<void *> p;
-    ~HipFree() { for (void *q : p) (void)hipFree(q); }
-};
-
-template <typename T>
-hipError_t up(HipFree &pool, T **d, const std::vector<T> &h)
+int qudit_merge_terms(const char *who, int n_sites, int d, int n_pairs, const int32_t *pair_sites, const qbh_z *pair_mat,
+                      int n_single, const int32_t *single_sites, const double *single_diag, QuditTerms &T)
 {
-    hipError_t e = qbh::dev_alloc(d, std::max<size_t>(h.size(), 1) * sizeof(T));
-    if (e != hipSuccess) return e;
-    pool.p.push_back(*d);
-    return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+    const int d2n = d * d;
+    // merge the pair terms into (i < j) order; (j, i) is transposed: element [(a' d + b'), (a d + b)] -> [(b' d + a'), (b d + a)]
+    for (int p = 0; p < n_pairs; ++p) {
+        const int a = pair_sites[2 * p], b = pair_sites[2 * p + 1];
+        if (a < 0 || b < 0 || a >= n_sites || b >= n_sites || a == b) {
+            set_error("%s: pair %d = (%d, %d) is invalid for %d sites", who, p, a, b, n_sites);
+            return QBH_EINVAL;
+        }
+        std::vector<std::complex<double>> &M = T.pm[{std::min(a, b), std::max(a, b)}];
+        if (M.empty()) M.assign((size_t)d2n * d2n, 0.0);
+        const qbh_z *src = pair_mat + (size_t)p * d2n * d2n;
+        for (int r = 0; r < d2n; ++r)
+            for (int c = 0; c < d2n; ++c) {
+                const qbh_z z = src[(size_t)r * d2n + c];
+                if (z.re == 0.0 && z.im == 0.0) continue;
+                if (r / d + r % d != c / d + c % d) {
+                    set_error("%s: pair %d element [%d][%d] = (%g, %g) changes the charge", who, p, r, c, z.re, z.im);
+                    return QBH_EINVAL;
+                }
+                const int rr = a < b ? r : (r % d) * d + r / d, cc = a < b ? c : (c % d) * d + c / d;
+                M[(size_t)rr * d2n + cc] += std::complex<double>(z.re, z.im);
+            }
+    }
+    for (const auto &kv : T.pm)
+        for (int r = 0; r < d2n; ++r)
+            for (int c = r; c < d2n; ++c) {
+                const std::complex<double> x = kv.second[(size_t)r * d2n + c], y = kv.second[(size_t)c * d2n + r];
+                if (std::abs(x - std::conj(y)) > QBH_SPARSE_PRECISION) {
+                    set_error("%s: the merged pair (%d, %d) is not Hermitian at [%d][%d]", who, kv.first.first, kv.first.second, r, c);
+                    return QBH_ENOTHERM;
+                }
+            }
+    std::vector<double> &sdiag = T.sdiag;
+    sdiag.assign((size_t)n_sites * d, 0.0);
+    for (int k = 0; k < n_single; ++k) {
+        const int s = single_sites[k];
+        if (s < 0 || s >= n_sites) {
+            set_error("%s: single-site term %d names site %d of %d", who, k, s, n_sites);
+            return QBH_EINVAL;
+        }
+        for (int l = 0; l < d; ++l) sdiag[(size_t)s * d + l] += single_diag[(size_t)k * d + l];
+    }
+    if ((int)T.pm.size() > kQuditMaxPairs) {
+        set_error("%s: %d distinct site pairs; at most %d are supported", who, (int)T.pm.size(), kQuditMaxPairs);
+        return QBH_EUNSUPP;
+    }
+    // term tables: per pair and state `in` of the row's word, the off-diagonal nonzeros <in|M|o> of that row (ascending o)
+    std::vector<int32_t> &pair_ij = T.pair_ij, &eoff = T.eoff, &eout = T.eout;
+    std::vector<double> &pdiag = T.pdiag;
+    std::vector<d2> &eval = T.eval;
+    int &max_row = T.max_row;
+    eoff.assign(1, 0);
+    for (const auto &kv : T.pm) {
+        pair_ij.push_back(kv.first.first | (kv.first.second << 8));
+        int worst = 0;
+        for (int in = 0; in < d2n; ++in) {
+            pdiag.push_back(kv.second[(size_t)in * d2n + in].real());
+            int k = 0;
+            for (int o = 0; o < d2n; ++o) {
+                const std::complex<double> z = kv.second[(size_t)in * d2n + o];
+                if (o == in || (z.real() == 0.0 && z.imag() == 0.0)) continue;
+                eout.push_back((o / d) | ((o % d) << 8));
+                eval.push_back(d2{z.real(), z.imag()});
+                ++k;
+            }
+            eoff.push_back((int32_t)eout.size());
+            worst = std::max(worst, k);
+        }
+        max_row += worst;
+    }
+    return QBH_OK;
 }
 
-}  // namespace
 }  // namespace qbh
 
 using qbh::d2;
@@ -300,81 +330,15 @@ extern "C" int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total, int n
         set_error("%s: out is NULL", who);
         return QBH_EINVAL;
     }
-    QBH_TRY(check_shape(who, n_sites, d));
+    QBH_TRY(qudit_check_shape(who, n_sites, d));
     if (total < 0 || total > n_sites * (d - 1) || n_pairs < 0 || n_single < 0 || (n_pairs > 0 && (!pair_sites || !pair_mat)) ||
         (n_single > 0 && (!single_sites || !single_diag))) {
         set_error("%s: invalid charge %d (0 .. %d) or term arrays", who, total, n_sites * (d - 1));
         return QBH_EINVAL;
     }
-    const int d2n = d * d;
-    // merge the pair terms into (i < j) order; (j, i) is transposed: element [(a' d + b'), (a d + b)] -> [(b' d + a'), (b d + a)]
-    std::map<std::pair<int, int>, PairMat> pm;
-    for (int p = 0; p < n_pairs; ++p) {
-        const int a = pair_sites[2 * p], b = pair_sites[2 * p + 1];
-        if (a < 0 || b < 0 || a >= n_sites || b >= n_sites || a == b) {
-            set_error("%s: pair %d = (%d, %d) is invalid for %d sites", who, p, a, b, n_sites);
-            return QBH_EINVAL;
-        }
-        PairMat &M = pm[{std::min(a, b), std::max(a, b)}];
-        if (M.m.empty()) M.m.assign((size_t)d2n * d2n, 0.0);
-        const qbh_z *src = pair_mat + (size_t)p * d2n * d2n;
-        for (int r = 0; r < d2n; ++r)
-            for (int c = 0; c < d2n; ++c) {
-                const qbh_z z = src[(size_t)r * d2n + c];
-                if (z.re == 0.0 && z.im == 0.0) continue;
-                if (r / d + r % d != c / d + c % d) {
-                    set_error("%s: pair %d element [%d][%d] = (%g, %g) changes the charge", who, p, r, c, z.re, z.im);
-                    return QBH_EINVAL;
-                }
-                const int rr = a < b ? r : (r % d) * d + r / d, cc = a < b ? c : (c % d) * d + c / d;
-                M.m[(size_t)rr * d2n + cc] += std::complex<double>(z.re, z.im);
-            }
-    }
-    for (const auto &kv : pm)
-        for (int r = 0; r < d2n; ++r)
-            for (int c = r; c < d2n; ++c) {
-                const std::complex<double> x = kv.second.m[(size_t)r * d2n + c], y = kv.second.m[(size_t)c * d2n + r];
-                if (std::abs(x - std::conj(y)) > QBH_SPARSE_PRECISION) {
-                    set_error("%s: the merged pair (%d, %d) is not Hermitian at [%d][%d]", who, kv.first.first, kv.first.second, r, c);
-                    return QBH_ENOTHERM;
-                }
-            }
-    std::vector<double> sdiag((size_t)n_sites * d, 0.0);
-    for (int k = 0; k < n_single; ++k) {
-        const int s = single_sites[k];
-        if (s < 0 || s >= n_sites) {
-            set_error("%s: single-site term %d names site %d of %d", who, k, s, n_sites);
-            return QBH_EINVAL;
-        }
-        for (int l = 0; l < d; ++l) sdiag[(size_t)s * d + l] += single_diag[(size_t)k * d + l];
-    }
-    if ((int)pm.size() > kQuditMaxPairs) {
-        set_error("%s: %d distinct site pairs; at most %d are supported", who, (int)pm.size(), kQuditMaxPairs);
-        return QBH_EUNSUPP;
-    }
-    // term tables: per pair and state `in` of the row's word, the off-diagonal nonzeros <in|M|o> of that row (ascending o)
-    std::vector<int32_t> pair_ij, eoff(1, 0), eout;
-    std::vector<double> pdiag;
-    std::vector<d2> eval;
-    int max_row = 1;
-    for (const auto &kv : pm) {
-        pair_ij.push_back(kv.first.first | (kv.first.second << 8));
-        int worst = 0;
-        for (int in = 0; in < d2n; ++in) {
-            pdiag.push_back(kv.second.m[(size_t)in * d2n + in].real());
-            int k = 0;
-            for (int o = 0; o < d2n; ++o) {
-                const std::complex<double> z = kv.second.m[(size_t)in * d2n + o];
-                if (o == in || (z.real() == 0.0 && z.imag() == 0.0)) continue;
-                eout.push_back((o / d) | ((o % d) << 8));
-                eval.push_back(d2{z.real(), z.imag()});
-                ++k;
-            }
-            eoff.push_back((int32_t)eout.size());
-            worst = std::max(worst, k);
-        }
-        max_row += worst;
-    }
+    QuditTerms T;
+    QBH_TRY(qudit_merge_terms(who, n_sites, d, n_pairs, pair_sites, pair_mat, n_single, single_sites, single_diag, T));
+    const int max_row = T.max_row;
     if (max_row > kQuditMaxRow) {
         set_error("%s: a row may hold %d entries; at most %d are supported", who, max_row, kQuditMaxRow);
         return QBH_EUNSUPP;
@@ -407,7 +371,7 @@ extern "C" int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total, int n
     h.bits = bits_per_level(d);
     h.total = total;
     h.tw = tw;
-    h.n_pairs = (int)pm.size();
+    h.n_pairs = (int)T.pm.size();
     h.max_row = max_row;
     {
         uint64_t *c;
@@ -415,12 +379,12 @@ extern "C" int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total, int n
         double *pd, *sd;
         d2 *ev;
         QBH_QHIP(who, up(pool, &c, cum));
-        QBH_QHIP(who, up(pool, &pij, pair_ij));
-        QBH_QHIP(who, up(pool, &pd, pdiag));
-        QBH_QHIP(who, up(pool, &eo, eoff));
-        QBH_QHIP(who, up(pool, &eu, eout));
-        QBH_QHIP(who, up(pool, &ev, eval));
-        QBH_QHIP(who, up(pool, &sd, sdiag));
+        QBH_QHIP(who, up(pool, &pij, T.pair_ij));
+        QBH_QHIP(who, up(pool, &pd, T.pdiag));
+        QBH_QHIP(who, up(pool, &eo, T.eoff));
+        QBH_QHIP(who, up(pool, &eu, T.eout));
+        QBH_QHIP(who, up(pool, &ev, T.eval));
+        QBH_QHIP(who, up(pool, &sd, T.sdiag));
         h.cum = c; h.pair_ij = pij; h.pdiag = pd; h.eoff = eo; h.eout = eu; h.eval = ev; h.sdiag = sd;
     }
     const int64_t nrows = row_end - row_begin;
@@ -463,7 +427,7 @@ extern "C" int qbh_mopr_qudit_dev(int n_sites, int d, int total_old, int dq, con
 {
     using namespace qbh;
     static const char *who = "qbh_mopr_qudit_dev";
-    QBH_TRY(check_shape(who, n_sites, d));
+    QBH_TRY(qudit_check_shape(who, n_sites, d));
     const int total_new = total_old + dq;
     if (!coef || !local || !d_vec_old || !d_vec_new || total_old < 0 || total_old > n_sites * (d - 1) || total_new < 0 ||
         total_new > n_sites * (d - 1)) {

@@ -1,0 +1,108 @@
+// qbh_qudit.hpp -- what the d-level generators share: the word packing and ranking of qbh_qudit.hip (the full sector,
+// qbh_gen_qudit) and of the momentum sectors in qbh_gen.hip (qbh_gen_qudit_repr), and the term merging both run.
+//
+// Site s holds a level l_s in [0, d) in bits [s b, (s+1) b), b = bits_per_level(d); words of one charge are ranked in
+// ascending order of sum_s l_s d^s, which is the order of the packed words as integers.  The counting table cum[s][q] is
+// described at the top of qbh_qudit.hip.
+#pragma once
+#include <complex>
+#include <map>
+#include <utility>
+#include <vector>
+
+#include "qbh_internal.hpp"
+
+namespace qbh {
+
+constexpr int kQuditMaxD = 8;
+constexpr int kQuditMaxPairs = 1024;     // merged (unordered) site pairs
+
+inline int bits_per_level(int d) { return d <= 2 ? 1 : d <= 4 ? 2 : 3; }
+
+// cum[s * tw + q] for s < n_sites, q < tw; *dims = cnt[n_sites][q] (the dimension of every sector q < tw)
+inline void qudit_table(int n_sites, int d, int tw, std::vector<uint64_t> &cum, std::vector<uint64_t> &dims)
+{
+    std::vector<uint64_t> cnt((size_t)tw, 0), nxt((size_t)tw);
+    cnt[0] = 1;
+    cum.assign((size_t)n_sites * tw, 0);
+    for (int s = 0; s < n_sites; ++s) {
+        uint64_t acc = 0;
+        for (int q = 0; q < tw; ++q) cum[(size_t)s * tw + q] = (acc += cnt[q]);
+        for (int q = 0; q < tw; ++q) {
+            uint64_t v = 0;
+            for (int l = 0; l < d && l <= q; ++l) v += cnt[q - l];
+            nxt[q] = v;
+        }
+        cnt.swap(nxt);
+    }
+    dims = cnt;
+}
+
+__device__ __forceinline__ int qd_level(uint64_t w, int bits, int s)
+{
+    return (int)((w >> (s * bits)) & ((1ULL << bits) - 1));
+}
+
+// the word of rank r among the words of charge `total` (walks from the most significant site down)
+__device__ __forceinline__ uint64_t qd_unrank(const uint64_t *cum, int n_sites, int d, int bits, int tw, int total, uint64_t r)
+{
+    uint64_t w = 0;
+    int Q = total;
+    for (int s = n_sites - 1; s >= 0; --s) {
+        const uint64_t *c = cum + s * tw;
+        const uint64_t top = c[Q];
+        int l = min(d - 1, Q);
+        while (l > 0 && top - c[Q - l] > r) --l;          // largest level whose smaller siblings hold <= r words
+        r -= top - c[Q - l];
+        Q -= l;
+        w |= (uint64_t)l << (s * bits);
+    }
+    return w;
+}
+
+// the next word of the same charge: the lowest site s that can take one more level while the sites below it give one up
+// is raised, and the charge left below it is packed into the lowest sites (the smallest such word).  The last word of the
+// sector comes back unchanged.
+__device__ __forceinline__ uint64_t qd_next(uint64_t w, int n_sites, int d, int bits)
+{
+    int below = 0;
+    for (int s = 0; s < n_sites; ++s) {
+        const int l = qd_level(w, bits, s);
+        if (below > 0 && l < d - 1) {
+            uint64_t out = ((w >> (s * bits)) + 1ULL) << (s * bits);      // s >= 1, so the shift stays below 64
+            int rest = below - 1;
+            for (int t = 0; rest > 0; ++t) {
+                const int v = min(d - 1, rest);
+                out |= (uint64_t)v << (t * bits);
+                rest -= v;
+            }
+            return out;
+        }
+        below += l;
+    }
+    return w;
+}
+
+// sum_s coef[s] O_s with one local d x d matrix O: la/lb[l'] = Re/Im <l'|O|l' - dq>
+struct QuditMopr { double ca[64], cb[64]; double la[kQuditMaxD], lb[kQuditMaxD]; };
+
+// The merged terms of a d-level operator and their device tables: per pair p (i < j, pair_ij = i | j << 8) and state
+// `in` = l_i d + l_j of the row's word, the diagonal pdiag[p d^2 + in] and the off-diagonal nonzeros <in|M|o> of that row
+// (ascending o) in eout / eval [eoff[p d^2 + in], eoff[p d^2 + in + 1]); sdiag[s d + l] the single-site diagonal.
+// max_row = 1 + sum_p (most off-diagonal nonzeros in one row of pair p): the longest row the terms can produce.
+struct QuditTerms {
+    std::map<std::pair<int, int>, std::vector<std::complex<double>>> pm;   // d^2 x d^2, row = out, column = in
+    std::vector<double> sdiag, pdiag;
+    std::vector<int32_t> pair_ij, eoff, eout;
+    std::vector<d2> eval;
+    int max_row = 1;
+};
+
+// checks of qbh_gen_qudit on the shape: QBH_EINVAL below 1 site or 2 levels, QBH_EUNSUPP beyond 8 levels or 64 bits
+int qudit_check_shape(const char *who, int n_sites, int d);
+// merges and checks the terms as qbh_gen_qudit does (charge: QBH_EINVAL, Hermitian: QBH_ENOTHERM, sites: QBH_EINVAL,
+// more than kQuditMaxPairs pairs: QBH_EUNSUPP) and builds the tables; the row capacity is the caller's to check
+int qudit_merge_terms(const char *who, int n_sites, int d, int n_pairs, const int32_t *pair_sites, const qbh_z *pair_mat,
+                      int n_single, const int32_t *single_sites, const double *single_diag, QuditTerms &T);
+
+}  // namespace qbh

@@ -310,6 +310,51 @@ class csr_mat:
         dg = 0.5 * U * n * (n - 1) - mu * n
         return cls.qudit(n_sites, n_max + 1, n_bosons, pairs, [(s, dg) for s in range(n_sites)], rows=rows, opts=opts)
 
+    @classmethod
+    def qudit_repr(cls, n_sites, d, total, perms, chars, pairs=(), singles=(), fake_pos=100.0, shard=(0, 1), opts=None,
+                   row_cuts=None):
+        """Momentum sector of the d-level operator of qudit (qbh_gen_qudit_repr): perms / chars / fake_pos / shard / row_cuts
+        as in heisenberg_repr, pairs / singles as in qudit.  The terms must be invariant under every translation."""
+        _lib.require_gpu()
+        opts = opts if opts is not None else make_opts()
+        pairs, singles = list(pairs), list(singles)
+        ps = np.ascontiguousarray(np.array([(p[0], p[1]) for p in pairs], dtype=np.int32).reshape(-1, 2))
+        pm = np.ascontiguousarray(np.array([np.asarray(p[2], dtype=np.complex128).reshape(d * d, d * d) for p in pairs],
+                                           dtype=np.complex128).reshape(-1))
+        ss = np.ascontiguousarray(np.array([s[0] for s in singles], dtype=np.int32))
+        sd = np.ascontiguousarray(np.array([np.asarray(s[1], dtype=np.float64).reshape(d) for s in singles],
+                                           dtype=np.float64).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+        c = np.ascontiguousarray(np.asarray(chars, dtype=np.complex128))
+        assert p.shape == (len(c), n_sites)
+        cuts = None if row_cuts is None else np.ascontiguousarray(row_cuts, dtype=np.int64)      # see heisenberg_repr
+        assert cuts is None or cuts.size == int(shard[1]) + 1
+        h = C.c_void_p()
+        dim = C.c_int64(0)
+        check(lib().qbh_gen_qudit_repr_cuts(C.byref(h), n_sites, d, total, len(pairs), _p(ps), _p(pm), len(singles), _p(ss), _p(sd),
+                                            len(c), _p(p), _p(c), fake_pos, int(shard[0]), int(shard[1]),
+                                            _p(cuts) if cuts is not None else None, C.byref(dim), C.byref(opts)),
+              "qbh_gen_qudit_repr")
+        return cls(0, None, None, None, opts=opts, _handle=h)
+
+    @classmethod
+    def spin_heisenberg_repr(cls, n_sites, S, two_sz, bonds, perms, chars, J=1.0, Jz=None, K=0.0, D=0.0, **kw):
+        """The operator of spin_heisenberg in a momentum sector (qbh_gen_qudit_repr; the reference's
+        examples/trans_symmetric/latt_chain/chain_Heisenberg_spin_one.cc); keywords as in qudit_repr."""
+        from . import qudit as qd
+        singles = qd.single_ion(S, n_sites, D) if D != 0.0 else []
+        return cls.qudit_repr(n_sites, qd._two_s(S) + 1, qd.spin_charge(n_sites, S, two_sz), perms, chars,
+                              qd.heisenberg_terms(S, bonds, J, Jz, K), singles, **kw)
+
+    @classmethod
+    def bose_hubbard_repr(cls, n_sites, n_bosons, n_max, bonds, perms, chars, t=1.0, U=1.1, mu=0.0, **kw):
+        """The operator of bose_hubbard in a momentum sector (qbh_gen_qudit_repr); keywords as in qudit_repr."""
+        from . import qudit as qd
+        pairs, _ = qd.bose_hubbard_terms(n_max, bonds, t, U, mu)
+        n = np.arange(n_max + 1, dtype=np.float64)
+        dg = 0.5 * U * n * (n - 1) - mu * n
+        return cls.qudit_repr(n_sites, n_max + 1, n_bosons, perms, chars, pairs, [(s, dg) for s in range(n_sites)], **kw)
+
     # ---- reference interface -------------------------------------------------------------
     def dimension(self):
         return self.dim
@@ -756,6 +801,21 @@ def moprXvec_qudit(n_sites, d, total_old, dq, coef, local, d_vec_old, d_vec_new,
     check(lib().qbh_mopr_qudit_dev(n_sites, d, total_old, dq, _p(c), _p(o), d_vec_old, d_vec_new, C.byref(dim_new), stream),
           "qbh_mopr_qudit_dev")
     return dim_new.value
+
+
+def moprXvec_qudit_repr(n_sites, d, total_old, dq, perms, chars_old, coef, local, d_vec_old, d_vec_new, stream=None):
+    """moprXvec_repr (src/model.cc:1715-1846) for sum_s coef[s] O_s between momentum sectors of qbh_gen_qudit_repr
+    (qbh_mopr_qudit_repr_dev; local as in moprXvec_qudit): from (total_old, chars_old) to (total_old + dq, chars_old * eta)
+    with coef[g(s)] = eta(g) coef[s].  Returns (dim_old, dim_new)."""
+    p = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+    co = np.ascontiguousarray(np.asarray(chars_old, dtype=np.complex128))
+    c = np.ascontiguousarray(coef, dtype=np.complex128)
+    o = np.ascontiguousarray(np.asarray(local, dtype=np.complex128).reshape(d * d))
+    assert p.shape == (len(co), n_sites) and c.size == n_sites
+    d0, d1 = C.c_int64(0), C.c_int64(0)
+    check(lib().qbh_mopr_qudit_repr_dev(n_sites, d, total_old, dq, len(co), _p(p), _p(co), _p(c), _p(o), d_vec_old, d_vec_new,
+                                        C.byref(d0), C.byref(d1), stream), "qbh_mopr_qudit_repr_dev")
+    return d0.value, d1.value
 
 
 def moprXvec_sz_repr(n_sites, n_dn, perms, chars_new, coef, d_vec_old, d_vec_new):
