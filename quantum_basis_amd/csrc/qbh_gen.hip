@@ -882,23 +882,13 @@ extern "C" int qbh_mf_heisenberg(qbh_csr **out, int n_sites, int n_dn, int n_bon
 // the Hamiltonian in the basis of momentum states built on orbit representatives.  The reference reaches the
 // representative of a hopped state through its sublattice (Weisse) tables; here every state is canonicalised
 // directly -- all |G| translations are applied with byte-sliced lookup tables and the smallest image wins.
-//   basis      ALL orbit representatives of the fixed-n_dn sector, ascending bit pattern; a representative whose
-//              norm vanishes at this momentum stays in the basis as a decoupled row with the fake diagonal
-//              fake_pos + i/dim (src/model.cc:735-740)
+//   basis      the orbit representatives of the fixed-n_dn sector (see k_sector_flag for what every family's basis holds)
 //   H[a][b]    sum over bond terms taking |a> to c = l.b of h * conj(chi(g*)) * sqrt(|S_b|/|S_a|), g* c = b
 //              (the phase exp(2 pi i k.d/L) * sqrt(nu_i/nu_j) of src/model.cc:808-814)
 namespace qbh {
 namespace {
 
 constexpr int kReprMaxTrans = 64;
-constexpr int kReprMaxRow = 160;          // distinct columns in one row (unique bonds + diagonal)
-
-struct ReprDev {
-    HeisDev h;                            // binomials, bonds, amplitudes
-    int n_trans, n_chunks;
-    double chr[2 * kReprMaxTrans];        // characters chi(g)
-    double fake_pos;
-};
 
 // the symmetry tables of a momentum sector: checks that translation 0 is the identity and every translation a site
 // permutation, fills the binomials (unless binom is null) and the characters, stores the permutations in perm8
@@ -949,17 +939,6 @@ int sector_symmetry(int n_sites, int n_trans, const int32_t *perms, const double
     return QBH_OK;
 }
 
-// R zeroed, then the symmetry part of the fixed-n_dn spin sector filled in (bonds and fake_pos are the caller's)
-int repr_symmetry(ReprDev &R, std::vector<uint64_t> &tab, int n_sites, int n_dn, int n_trans, const int32_t *perms,
-                  const double *chars, const char *who)
-{
-    memset(&R, 0, sizeof(R));
-    R.h.n_sites = n_sites;
-    R.h.n_dn = n_dn;
-    R.n_trans = n_trans;
-    return sector_symmetry(n_sites, n_trans, perms, chars, who, R.h.binom, R.chr, nullptr, R.n_chunks, tab);
-}
-
 // image of bit pattern s under translation g; tab[(g*n_chunks + c)*64 + v] = scattered bits of chunk c with value v
 __device__ __forceinline__ uint64_t repr_translate(const uint64_t *tab, int n_chunks, int g, uint64_t s)
 {
@@ -969,13 +948,59 @@ __device__ __forceinline__ uint64_t repr_translate(const uint64_t *tab, int n_ch
     return out;
 }
 
-// smallest image and the translation that produces it
-__device__ __forceinline__ uint64_t repr_canonical(const ReprDev &R, const uint64_t *tab, uint64_t s, int *gstar)
+__device__ __forceinline__ uint64_t unrank_k(const uint64_t (*binom)[34], int n_sites, int k, uint64_t r)
+{
+    uint64_t bits = 0;
+    int p = n_sites - 1;
+    for (; k >= 1; --k) {
+        while (binom[p][k] > r) --p;
+        bits |= 1ULL << p;
+        r -= binom[p][k];
+        --p;
+    }
+    return bits;
+}
+
+// next bit pattern with the same popcount (Gosper)
+__device__ __forceinline__ uint64_t next_same_popcount(uint64_t s)
+{
+    const uint64_t t2 = s | (s - 1ULL);
+    return (t2 + 1ULL) | (((~t2 & (t2 + 1ULL)) - 1ULL) >> (__ffsll((long long)s)));
+}
+
+// ---- what a sector family is ----
+// A family is a device struct Dev (n_trans, n_chunks, chr, fake_pos and its own terms) with, next to it,
+//   sector_word_count(R, ctab)      host: the number of words of the sector (UINT64_MAX if that overflows); a family whose
+//                                   cursor reads a counting table on the device leaves it in ctab, and
+//   sector_tables(R, ctab, pool)    uploads it and points R at it (default: nothing)
+//   sector_seek(R, r)               the cursor at the word of rank r (ascending words); sector_word(R, cur) the word under it,
+//   sector_step(R, cur)             the step to the next word
+//   sector_allowed(R, s)            whether word s is in the space at all (default: yes)
+//   sector_translate(R, tab, g, s)  the image of s under translation g (default: one field of n_chunks chunks)
+//   sector_parity(R, g, s)          1 if T_g |s> = -|g(s)> (default: 0, no signs)
+//   sector_row(R, ...), max_row<Dev>  one row of the sector operator and its capacity
+// The defaults below serve a family whose word is one field and whose cursor is the word itself; a family with more
+// structure overloads them for its struct.
+template <class Dev> int sector_tables(Dev &, const std::vector<uint64_t> &, std::vector<void *> &) { return QBH_OK; }
+template <class Dev> __device__ __forceinline__ uint64_t sector_word(const Dev &, uint64_t cur) { return cur; }
+template <class Dev> __device__ __forceinline__ bool sector_allowed(const Dev &, uint64_t) { return true; }
+template <class Dev> __device__ __forceinline__ int sector_parity(const Dev &, int, uint64_t) { return 0; }
+template <class Dev>
+__device__ __forceinline__ uint64_t sector_translate(const Dev &R, const uint64_t *tab, int g, uint64_t s)
+{
+    return repr_translate(tab, R.n_chunks, g, s);
+}
+template <class Dev> constexpr int max_row = 0;
+
+// ---- the row toolkit of the families: everything from the point where a term's value v and its column are known ----
+// smallest image of s and the translation that produces it
+template <class Dev>
+__device__ __forceinline__ uint64_t sector_canonical(const Dev &R, const uint64_t *tab, uint64_t s, int *gstar)
 {
     uint64_t best = s;
     int gb = 0;                           // g = 0 is the identity
     for (int g = 1; g < R.n_trans; ++g) {
-        const uint64_t t = repr_translate(tab, R.n_chunks, g, s);
+        const uint64_t t = sector_translate(R, tab, g, s);
         if (t < best) {
             best = t;
             gb = g;
@@ -985,100 +1010,155 @@ __device__ __forceinline__ uint64_t repr_canonical(const ReprDev &R, const uint6
     return best;
 }
 
-// pass 1: code[r] = 0 if state r (colex rank in the n_dn sector) is not a representative, else |S| | (zero-norm << 7)
-__global__ __launch_bounds__(256) void k_repr_flag(const ReprDev *Rp, const uint64_t *tab, int64_t nstates, uint8_t *code,
-                                                   int32_t *cnt)
+// position of representative b in the ascending list reps[0, dim)
+__device__ __forceinline__ int64_t sector_find(const uint64_t *reps, int64_t dim, uint64_t b)
 {
-    const ReprDev &R = *Rp;
-    constexpr int RUN = 32;               // consecutive ranks per lane: one unrank, then next-combination steps
-    const int64_t nruns = (nstates + RUN - 1) / RUN;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t run = (int64_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += stride) {
-        const int64_t r0 = run * RUN, r1 = (r0 + RUN < nstates) ? r0 + RUN : nstates;
-        uint64_t s = heis_unrank(R.h, (uint64_t)r0);
-        for (int64_t r = r0; r < r1; ++r) {
-            uint8_t c = 0;
-            bool rep = true;
-            int nstab = 1;
-            double sr = R.chr[0], si = R.chr[1];
-            for (int g = 1; g < R.n_trans; ++g) {
-                const uint64_t t = repr_translate(tab, R.n_chunks, g, s);
-                if (t < s) {
-                    rep = false;
-                    break;
-                }
-                if (t == s) {
-                    nstab++;
-                    sr += R.chr[2 * g];
-                    si += R.chr[2 * g + 1];
-                }
-            }
-            if (rep) c = (uint8_t)(nstab | ((sr * sr + si * si < 1e-20) ? 0x80 : 0));
-            code[r] = c;
-            cnt[r] = rep ? 1 : 0;
-            // next bit pattern with the same popcount (Gosper)
-            const uint64_t t2 = s | (s - 1ULL);
-            s = (t2 + 1ULL) | (((~t2 & (t2 + 1ULL)) - 1ULL) >> (__ffsll((long long)s)));
-        }
+    int64_t lo = 0, hi = dim;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (reps[mid] < b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the row of a representative whose norm vanishes at this momentum: it stays in the basis, decoupled, with the fake diagonal
+// fake_pos + i/dim (src/model.cc:735-740)
+__device__ __forceinline__ int row_zero_norm(double fake_pos, int64_t dim, int64_t i, int32_t *cols, d2 *vals)
+{
+    cols[0] = (int32_t)i;
+    vals[0] = d2{fake_pos + (double)i / (double)dim, 0.0};
+    return 1;
+}
+
+// v at column lo among the entries [first, n): added to that column if the row has it, else appended while there is room
+__device__ __forceinline__ void row_merge(int32_t *cols, d2 *vals, int &n, int cap, int first, int64_t lo, d2 v)
+{
+    int q = first;
+    while (q < n && cols[q] != (int32_t)lo) ++q;
+    if (q < n) {
+        vals[q] += v;
+    } else if (n < cap) {
+        cols[n] = (int32_t)lo;
+        vals[n] = v;
+        ++n;
     }
 }
 
-__global__ __launch_bounds__(256) void k_repr_compact(const ReprDev *Rp, int64_t nstates, const uint8_t *code, const int64_t *pos,
-                                                      uint64_t *reps, uint8_t *info)
+// v at column lo of row i, whose slot 0 is kept for the diagonal dg
+__device__ __forceinline__ void row_add(int32_t *cols, d2 *vals, int &n, int cap, int64_t i, int64_t lo, d2 v, d2 &dg)
 {
-    const ReprDev &R = *Rp;
-    constexpr int RUN = 32;
-    const int64_t nruns = (nstates + RUN - 1) / RUN;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t run = (int64_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += stride) {
-        const int64_t r0 = run * RUN, r1 = (r0 + RUN < nstates) ? r0 + RUN : nstates;
-        uint64_t s = heis_unrank(R.h, (uint64_t)r0);
-        for (int64_t r = r0; r < r1; ++r) {
-            if (code[r]) {
-                reps[pos[r]] = s;
-                info[pos[r]] = code[r];
-            }
-            const uint64_t t2 = s | (s - 1ULL);
-            s = (t2 + 1ULL) | (((~t2 & (t2 + 1ULL)) - 1ULL) >> (__ffsll((long long)s)));
+    if (lo == i) dg += v;
+    else row_merge(cols, vals, n, cap, 1, lo, v);
+}
+
+__device__ __forceinline__ void row_sort(int32_t *cols, d2 *vals, int m)      // insertion sort by column (rows are short)
+{
+    for (int q = 1; q < m; ++q) {
+        const int32_t c = cols[q];
+        const d2 v = vals[q];
+        int p = q - 1;
+        while (p >= 0 && cols[p] > c) {
+            cols[p + 1] = cols[p];
+            vals[p + 1] = vals[p];
+            --p;
+        }
+        cols[p + 1] = c;
+        vals[p + 1] = v;
+    }
+}
+
+// the diagonal into slot 0, cancelled off-diagonal entries dropped (lil_mat::add, src/sparse.cc:72-77), columns ascending;
+// returns the row's length
+__device__ __forceinline__ int row_finish(int32_t *cols, d2 *vals, int n, d2 dg)
+{
+    vals[0] = dg;
+    int m = 1;
+    for (int q = 1; q < n; ++q)
+        if (vals[q].x * vals[q].x + vals[q].y * vals[q].y >= 1e-28) {
+            cols[m] = cols[q];
+            vals[m] = vals[q];
+            ++m;
+        }
+    row_sort(cols, vals, m);
+    return m;
+}
+
+// ------------------------------------ spin-1/2 family (qbh_gen_heisenberg_repr) --
+constexpr int kReprMaxRow = 160;          // distinct columns in one row (unique bonds + diagonal)
+
+struct ReprDev {
+    HeisDev h;                            // binomials, bonds, amplitudes
+    int n_trans, n_chunks;
+    double chr[2 * kReprMaxTrans];        // characters chi(g)
+    double fake_pos;
+};
+template <> constexpr int max_row<ReprDev> = kReprMaxRow;
+
+uint64_t sector_word_count(const ReprDev &R, std::vector<uint64_t> &) { return binom_u64(R.h.n_sites, R.h.n_dn); }
+__device__ __forceinline__ uint64_t sector_seek(const ReprDev &R, uint64_t r) { return heis_unrank(R.h, r); }
+__device__ __forceinline__ void sector_step(const ReprDev &, uint64_t &cur) { cur = next_same_popcount(cur); }
+
+// one row of the sector Hamiltonian into (cols, vals), columns ascending, duplicates merged; returns its length
+__device__ int repr_row(const ReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
+                        int32_t *cols, d2 *vals)
+{
+    const uint8_t ci = info[i];
+    if (ci & 0x80) return row_zero_norm(R.fake_pos, dim, i, cols, vals);
+    const double si = (double)(ci & 0x7f);
+    const uint64_t a = reps[i];
+    int n = 1;
+    cols[0] = (int32_t)i;
+    d2 dg = {0.0, 0.0};
+    for (int bnd = 0; bnd < R.h.n_bonds; ++bnd) {
+        const int x = R.h.sa[bnd], y = R.h.sb[bnd];
+        if (((a >> x) ^ (a >> y)) & 1ULL) {
+            dg.x -= R.h.diag[bnd];
+            const uint64_t c = a ^ (1ULL << x) ^ (1ULL << y);
+            int g = 0;
+            const uint64_t b = sector_canonical(R, tab, c, &g);
+            const int64_t lo = sector_find(reps, dim, b);
+            const uint8_t cj = info[lo];
+            if (cj & 0x80) continue;      // zero-norm target: dropped (src/model.cc:806)
+            const double f = R.h.offd[bnd] * sqrt((double)(cj & 0x7f) / si);
+            const d2 v = {f * R.chr[2 * g], -f * R.chr[2 * g + 1]};          // h * conj(chi(g*)) * sqrt(|S_b|/|S_a|)
+            row_add(cols, vals, n, kReprMaxRow, i, lo, v, dg);
+        } else {
+            dg.x += R.h.diag[bnd];
         }
     }
+    return row_finish(cols, vals, n, dg);
+}
+
+__device__ __forceinline__ int sector_row(const ReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim,
+                                          int64_t i, int32_t *cols, d2 *vals)
+{
+    return repr_row(R, tab, reps, info, dim, i, cols, vals);
 }
 
 // moprXvec_repr for S^z_q (src/model.cc:1715-1846, diagonal branch :1756-1759): in the basis of ALL representatives the
 // operator sum_s c_s S^z_s with c_{g(s)} = eta(g) c_s maps |a, k> to z_a |a, k * eta>, z_a = sum_s c_s s^z_s(a) evaluated on
 // the representative itself (the stabiliser, hence the normalisation, does not depend on the momentum); representatives
-// whose norm vanishes at the NEW momentum get 0.  code[] comes from k_repr_flag run with the new characters.
+// whose norm vanishes at the NEW momentum get 0.  info_new[] comes from the enumeration with the new characters.
 struct SpinCoefR { double re[64], im[64]; };
-__global__ __launch_bounds__(256) void k_repr_apply_sz(const ReprDev *Rp, int64_t nstates, const uint8_t *code, const int64_t *pos,
+__global__ __launch_bounds__(256) void k_repr_apply_sz(int n_sites, const uint64_t *reps, const uint8_t *info_new, int64_t dim,
                                                        SpinCoefR cf, const d2 *x_old, d2 *y_new)
 {
-    const ReprDev &R = *Rp;
-    constexpr int RUN = 32;
-    const int64_t nruns = (nstates + RUN - 1) / RUN;
     const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t run = (int64_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += stride) {
-        const int64_t r0 = run * RUN, r1 = (r0 + RUN < nstates) ? r0 + RUN : nstates;
-        uint64_t s = heis_unrank(R.h, (uint64_t)r0);
-        for (int64_t r = r0; r < r1; ++r) {
-            const uint8_t c = code[r];
-            if (c) {
-                const int64_t p = pos[r];
-                d2 out = {0.0, 0.0};
-                if (!(c & 0x80)) {
-                    double zr = 0.0, zi = 0.0;
-                    for (int site = 0; site < R.h.n_sites; ++site) {
-                        const double sz = ((s >> site) & 1ULL) ? -0.5 : 0.5;
-                        zr += sz * cf.re[site];
-                        zi += sz * cf.im[site];
-                    }
-                    const d2 x = x_old[p];
-                    out = d2{zr * x.x - zi * x.y, zr * x.y + zi * x.x};
-                }
-                y_new[p] = out;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < dim; i += stride) {
+        d2 out = {0.0, 0.0};
+        if (!(info_new[i] & 0x80)) {
+            const uint64_t s = reps[i];
+            double zr = 0.0, zi = 0.0;
+            for (int site = 0; site < n_sites; ++site) {
+                const double sz = ((s >> site) & 1ULL) ? -0.5 : 0.5;
+                zr += sz * cf.re[site];
+                zi += sz * cf.im[site];
             }
-            const uint64_t t2 = s | (s - 1ULL);
-            s = (t2 + 1ULL) | (((~t2 & (t2 + 1ULL)) - 1ULL) >> (__ffsll((long long)s)));
+            const d2 x = x_old[i];
+            out = d2{zr * x.x - zi * x.y, zr * x.y + zi * x.x};
         }
+        y_new[i] = out;
     }
 }
 
@@ -1106,13 +1186,8 @@ __global__ __launch_bounds__(128) void k_repr_apply_flip(const ReprDev *Rnew, co
             if (lower ? down : !down) continue;   // S^- acts on an up spin (bit 0), S^+ on a down spin (bit 1)
             const uint64_t c = a ^ (1ULL << site);
             int g = 0;
-            const uint64_t b = repr_canonical(R, tab, c, &g);
-            int64_t lo = 0, hi = dim_new;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (reps_new[mid] < b) lo = mid + 1;
-                else hi = mid;
-            }
+            const uint64_t b = sector_canonical(R, tab, c, &g);
+            const int64_t lo = sector_find(reps_new, dim_new, b);
             const uint8_t cj = info_new[lo];
             if (cj & 0x80) continue;           // zero norm at the target momentum
             const double f = sqrt((double)(cj & 0x7f) / sa);
@@ -1125,247 +1200,19 @@ __global__ __launch_bounds__(128) void k_repr_apply_flip(const ReprDev *Rnew, co
     }
 }
 
-// one row of the sector Hamiltonian into (cols, vals), columns ascending, duplicates merged; returns its length
-__device__ int repr_row(const ReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
-                        int32_t *cols, d2 *vals)
-{
-    const uint8_t ci = info[i];
-    if (ci & 0x80) {                      // zero norm at this momentum: decoupled row, fake diagonal
-        cols[0] = (int32_t)i;
-        vals[0] = d2{R.fake_pos + (double)i / (double)dim, 0.0};
-        return 1;
-    }
-    const double si = (double)(ci & 0x7f);
-    const uint64_t a = reps[i];
-    int n = 1;
-    cols[0] = (int32_t)i;
-    d2 dg = {0.0, 0.0};
-    for (int bnd = 0; bnd < R.h.n_bonds; ++bnd) {
-        const int x = R.h.sa[bnd], y = R.h.sb[bnd];
-        if (((a >> x) ^ (a >> y)) & 1ULL) {
-            dg.x -= R.h.diag[bnd];
-            const uint64_t c = a ^ (1ULL << x) ^ (1ULL << y);
-            int g = 0;
-            const uint64_t b = repr_canonical(R, tab, c, &g);
-            int64_t lo = 0, hi = dim;     // index of b in the ascending representative list
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (reps[mid] < b) lo = mid + 1;
-                else hi = mid;
-            }
-            const uint8_t cj = info[lo];
-            if (cj & 0x80) continue;      // zero-norm target: dropped (src/model.cc:806)
-            const double f = R.h.offd[bnd] * sqrt((double)(cj & 0x7f) / si);
-            const d2 v = {f * R.chr[2 * g], -f * R.chr[2 * g + 1]};          // h * conj(chi(g*)) * sqrt(|S_b|/|S_a|)
-            if (lo == i) {
-                dg += v;
-                continue;
-            }
-            int q = 1;
-            while (q < n && cols[q] != (int32_t)lo) ++q;
-            if (q < n) {
-                vals[q] += v;
-            } else if (n < kReprMaxRow) {
-                cols[n] = (int32_t)lo;
-                vals[n] = v;
-                ++n;
-            }
-        } else {
-            dg.x += R.h.diag[bnd];
-        }
-    }
-    vals[0] = dg;
-    // drop cancelled off-diagonal entries (lil_mat::add, src/sparse.cc:72-77), then sort by column
-    int m = 1;
-    for (int q = 1; q < n; ++q)
-        if (vals[q].x * vals[q].x + vals[q].y * vals[q].y >= 1e-28) {
-            cols[m] = cols[q];
-            vals[m] = vals[q];
-            ++m;
-        }
-    for (int q = 1; q < m; ++q) {         // insertion sort (rows are short)
-        const int32_t c = cols[q];
-        const d2 v = vals[q];
-        int p = q - 1;
-        while (p >= 0 && cols[p] > c) {
-            cols[p + 1] = cols[p];
-            vals[p + 1] = vals[p];
-            --p;
-        }
-        cols[p + 1] = c;
-        vals[p + 1] = v;
-    }
-    return m;
-}
-
-}  // namespace
-}  // namespace qbh
-
-// S^z_q on a translation-symmetric sector (see k_repr_apply_sz).  perms / chars_new as in qbh_gen_heisenberg_repr, with
-// the characters of the TARGET momentum; the vectors are indexed like the rows of the sector operators (all
-// representatives of the n_dn sector, ascending).
-extern "C" int qbh_mopr_sz_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars_new,
-                                    const qbh_z *coef, const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_out)
-{
-    using namespace qbh;
-    if (!perms || !chars_new || !coef || !d_vec_old || !d_vec_new || n_sites <= 0 || n_sites > 62 || n_dn < 0 || n_dn > n_sites ||
-        n_dn > 33 || n_trans < 1 || n_trans > kReprMaxTrans) {
-        set_error("qbh_mopr_sz_repr_dev: invalid argument");
-        return QBH_EINVAL;
-    }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
-    const char *who = "qbh_mopr_sz_repr_dev";
-    std::vector<ReprDev> rr(1);
-    std::vector<uint64_t> tab;
-    QBH_TRY(repr_symmetry(rr[0], tab, n_sites, n_dn, n_trans, perms, chars_new, who));
-    const int64_t nstates = (int64_t)binom_u64(n_sites, n_dn);
-    SpinCoefR cf{};
-    for (int sidx = 0; sidx < n_sites; ++sidx) {
-        cf.re[sidx] = coef[sidx].re;
-        cf.im[sidx] = coef[sidx].im;
-    }
-    DevBufs bufs;
-    ReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr;
-    uint8_t *d_code = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr;
-    QBH_TRY(upload(rr, &d_R, bufs.pool));
-    QBH_TRY(upload(tab, &d_tab, bufs.pool));
-    QBH_HIP_WHO(who, bufs.alloc(&d_code, (size_t)nstates));
-    QBH_HIP_WHO(who, bufs.alloc(&d_cnt, (size_t)nstates * sizeof(int32_t)));
-    QBH_HIP_WHO(who, bufs.alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_repr_flag, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, d_tab, nstates, d_code, d_cnt);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_TRY(exclusive_scan(d_cnt, nstates, d_pos, 0));
-    int64_t dim = 0;
-    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost));
-    hipLaunchKernelGGL(k_repr_apply_sz, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, d_R, nstates, d_code, d_pos, cf,
-                       reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_HIP_WHO(who, hipDeviceSynchronize());
-    if (dim_out) *dim_out = dim;
-    return QBH_OK;
-}
-
-
-namespace qbh {
-namespace {
-// representatives (ascending) and their info bytes (|S| | zero-norm << 7) of the sector described by R; d_R, d_tab, d_reps and
-// d_info join `pool`
-int repr_enumerate(const ReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, ReprDev **d_R_out,
-                   uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
-{
-    const int64_t nstates = (int64_t)binom_u64(R.h.n_sites, R.h.n_dn);
-    QBH_TRY(upload(std::vector<ReprDev>(1, R), d_R_out, pool));
-    QBH_TRY(upload(tab, d_tab_out, pool));
-    DevBufs tmp;
-    uint8_t *d_code = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr;
-    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
-    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nstates * sizeof(int32_t)));
-    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nstates + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_repr_flag, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, *d_R_out, *d_tab_out, nstates, d_code, d_cnt);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_TRY(exclusive_scan(d_cnt, nstates, d_pos, 0));
-    int64_t dim = 0;
-    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nstates, sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (dim <= 0) {
-        set_error("%s: empty sector", who);
-        return QBH_EINVAL;
-    }
-    QBH_HIP_WHO(who, qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
-    pool.push_back(*d_reps_out);
-    QBH_HIP_WHO(who, qbh::dev_alloc(d_info_out, (size_t)dim));
-    pool.push_back(*d_info_out);
-    hipLaunchKernelGGL(k_repr_compact, dim3(blas_grid((nstates + 31) / 32)), dim3(256), 0, 0, *d_R_out, nstates, d_code, d_pos, *d_reps_out,
-                       *d_info_out);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_HIP_WHO(who, hipDeviceSynchronize());
-    *dim_out = dim;
-    return QBH_OK;
-}
-}  // namespace
-}  // namespace qbh
-
-// S^-_q (kind -1: n_dn -> n_dn + 1) and S^+_q (kind +1: n_dn -> n_dn - 1) between momentum sectors; see k_repr_apply_flip.
-extern "C" int qbh_mopr_flip_repr_dev(int n_sites, int n_dn_old, int kind, int n_trans, const int32_t *perms, const double *chars_old,
-                                      const double *chars_new, const qbh_z *coef, const qbh_z *d_vec_old, qbh_z *d_vec_new,
-                                      int64_t *dim_old_out, int64_t *dim_new_out)
-{
-    using namespace qbh;
-    const int n_new = n_dn_old - kind;
-    if (!perms || !chars_old || !chars_new || !coef || !d_vec_old || !d_vec_new || (kind != -1 && kind != 1) || n_sites <= 0 ||
-        n_sites > 62 || n_dn_old < 0 || n_dn_old > n_sites || n_new < 0 || n_new > n_sites || n_dn_old > 33 || n_new > 33 || n_trans < 1 ||
-        n_trans > kReprMaxTrans) {
-        set_error("qbh_mopr_flip_repr_dev: invalid argument");
-        return QBH_EINVAL;
-    }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
-    SpinCoefR cf{};
-    for (int sidx = 0; sidx < n_sites; ++sidx) {
-        cf.re[sidx] = coef[sidx].re;
-        cf.im[sidx] = coef[sidx].im;
-    }
-    const char *who = "qbh_mopr_flip_repr_dev";
-    std::vector<ReprDev> ro(1), rn(1);
-    std::vector<uint64_t> tab_o, tab_n;
-    QBH_TRY(repr_symmetry(ro[0], tab_o, n_sites, n_dn_old, n_trans, perms, chars_old, who));
-    QBH_TRY(repr_symmetry(rn[0], tab_n, n_sites, n_new, n_trans, perms, chars_new, who));
-    std::vector<void *> pool;
-    ReprDev *R_old = nullptr, *R_new = nullptr;
-    uint64_t *tab_old = nullptr, *tab_new = nullptr, *reps_old = nullptr, *reps_new = nullptr;
-    uint8_t *info_old = nullptr, *info_new = nullptr;
-    int64_t dim_old = 0, dim_new = 0;
-    int rc = repr_enumerate(ro[0], tab_o, pool, &R_old, &tab_old, &reps_old, &info_old, &dim_old, who);
-    if (rc == QBH_OK) rc = repr_enumerate(rn[0], tab_n, pool, &R_new, &tab_new, &reps_new, &info_new, &dim_new, who);
-    hipError_t e = hipSuccess;
-    if (rc == QBH_OK) {
-        e = hipMemset(d_vec_new, 0, (size_t)dim_new * sizeof(d2));
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_repr_apply_flip, dim3(blas_grid(dim_old)), dim3(128), 0, 0, R_new, tab_new, reps_old, info_old, dim_old,
-                               reps_new, info_new, dim_new, kind < 0 ? 1 : 0, cf, reinterpret_cast<const d2 *>(d_vec_old),
-                               reinterpret_cast<double *>(d_vec_new));
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
-    }
-    free_pool(pool);
-    if (rc != QBH_OK) return rc;
-    if (e != hipSuccess) {
-        set_error("qbh_mopr_flip_repr_dev: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;
-    }
-    if (dim_old_out) *dim_old_out = dim_old;
-    if (dim_new_out) *dim_new_out = dim_new;
-    return QBH_OK;
-}
-
 // ------------------------------------ Hubbard family in translation-symmetric sectors --
 // Device counterpart of model::enumerate_basis_repr + generate_Ham_sparse_repr (src/model.cc:687-836) for two-species
 // fermions (the reference's examples/trans_symmetric/latt_square/square_Fermi_Hubbard.cc).  A basis state is the pair of
 // occupation patterns (u, d) with the operator order "all up (ascending site), then all down", stored as the word
-// s = u | d << n_sites; a translation g maps c^dag_{i,sigma} to c^dag_{g(i),sigma}, so
-//     T_g |u, d> = sgn(g, u) sgn(g, d) |g(u), g(d)>,   sgn = parity of the inversions among the images of the occupied sites.
-// Basis: ALL orbit representatives (smallest word), ascending; a representative whose signed character sum over its
-// stabiliser vanishes has zero norm at this momentum and stays as a decoupled row with the fake diagonal (as in
-// qbh_gen_heisenberg_repr).  The operator is a list of directed one-body terms  amp_sigma * c^dag_{i,sigma} c_{j,sigma}
-// plus U sum_i n_{i,up} n_{i,dn}; it must commute with the translations (a Hamiltonian does; a single-site operator has to
-// be translation-averaged first, exactly as measure_repr_static does, src/model.cc:1874-1888).  With |a,k> =
-// (|G||S_a|)^(-1/2) sum_g chi_k(g) T_g |a>, row a holds
+// s = u | d << n_sites (ascending words: rank = rank(d) * C(n, n_up) + rank(u)); a translation g maps c^dag_{i,sigma} to
+// c^dag_{g(i),sigma}, so
+//     T_g |u, d> = sgn(g, u) sgn(g, d) |g(u), g(d)>,   sgn = parity of the inversions among the images of the occupied sites,
+// and the norm of a representative is the SIGNED character sum over its stabiliser.  The operator is a list of directed
+// one-body terms  amp_sigma * c^dag_{i,sigma} c_{j,sigma}  plus U sum_i n_{i,up} n_{i,dn}; it must commute with the
+// translations (a Hamiltonian does; a single-site operator has to be translation-averaged first, exactly as
+// measure_repr_static does, src/model.cc:1874-1888).  With |a,k> = (|G||S_a|)^(-1/2) sum_g chi_k(g) T_g |a>, row a holds
 //     O[a][b] = sum over terms that move a particle of a from i to j, giving c with T_{g*} |c> = sigma |b>:
 //               amp * (hop sign) * sigma * conj(chi_k(g*)) * sqrt(|S_b| / |S_a|).
-namespace qbh {
-namespace {
-
 constexpr int kHubReprMaxTerms = 512;
 constexpr int kHubReprMaxPairs = 256;
 constexpr int kHubReprMaxRow = 160;       // distinct columns in one row: one move per bond and species, one exchange, the diagonal
@@ -1385,24 +1232,46 @@ struct HubReprDev {
     double chr[2 * kReprMaxTrans];
     int8_t perm[kReprMaxTrans * 32];                       // perm[g * n_sites + site]
 };
+template <> constexpr int max_row<HubReprDev> = kHubReprMaxRow;
 
-__device__ __forceinline__ uint64_t unrank_k(const uint64_t (*binom)[34], int n_sites, int k, uint64_t r)
+uint64_t sector_word_count(const HubReprDev &R, std::vector<uint64_t> &)
 {
-    uint64_t bits = 0;
-    int p = n_sites - 1;
-    for (; k >= 1; --k) {
-        while (binom[p][k] > r) --p;
-        bits |= 1ULL << p;
-        r -= binom[p][k];
-        --p;
-    }
-    return bits;
+    const uint64_t cu = binom_u64(R.n_sites, R.n_up), cd = binom_u64(R.n_sites, R.n_dn);
+    return cu > UINT64_MAX / cd ? UINT64_MAX : cu * cd;
 }
 
-__device__ __forceinline__ uint64_t next_same_popcount(uint64_t s)
+struct HubCursor { uint64_t u, d, ru; };                   // the two patterns and the rank of the up pattern
+
+__device__ __forceinline__ HubCursor sector_seek(const HubReprDev &R, uint64_t r)
 {
-    const uint64_t t2 = s | (s - 1ULL);
-    return (t2 + 1ULL) | (((~t2 & (t2 + 1ULL)) - 1ULL) >> (__ffsll((long long)s)));
+    const uint64_t cu = R.binom[R.n_sites][R.n_up];
+    HubCursor c;
+    c.ru = r % cu;
+    c.u = unrank_k(R.binom, R.n_sites, R.n_up, c.ru);
+    c.d = unrank_k(R.binom, R.n_sites, R.n_dn, r / cu);
+    return c;
+}
+__device__ __forceinline__ uint64_t sector_word(const HubReprDev &R, const HubCursor &c) { return c.u | (c.d << R.n_sites); }
+__device__ __forceinline__ void sector_step(const HubReprDev &R, HubCursor &c)
+{
+    if (++c.ru == R.binom[R.n_sites][R.n_up]) {            // next down pattern, up patterns start over
+        c.ru = 0;
+        c.u = (R.n_up > 0) ? ((1ULL << R.n_up) - 1ULL) : 0ULL;
+        c.d = R.n_dn > 0 ? next_same_popcount(c.d) & ((1ULL << R.n_sites) - 1ULL) : 0ULL;
+    } else {
+        c.u = next_same_popcount(c.u);
+    }
+}
+// t-J: words with a doubly occupied site are not in the space
+__device__ __forceinline__ bool sector_allowed(const HubReprDev &R, uint64_t s)
+{
+    return !(R.no_double && (s & (s >> R.n_sites) & ((1ULL << R.n_sites) - 1ULL)));
+}
+__device__ __forceinline__ uint64_t sector_translate(const HubReprDev &R, const uint64_t *tab, int g, uint64_t s)
+{
+    const uint64_t m = (1ULL << R.n_sites) - 1ULL;
+    const uint64_t u = repr_translate(tab, R.n_chunks, g, s & m), d = repr_translate(tab, R.n_chunks, g, s >> R.n_sites);
+    return u | (d << R.n_sites);
 }
 
 // parity (0 / 1) of the permutation that sorts the images of the occupied sites of `occ` under translation g
@@ -1420,119 +1289,17 @@ __device__ __forceinline__ int hubrepr_parity(const HubReprDev &R, int g, uint64
     }
     return par;
 }
-
-__device__ __forceinline__ uint64_t hubrepr_translate(const HubReprDev &R, const uint64_t *tab, int g, uint64_t s)
+__device__ __forceinline__ int sector_parity(const HubReprDev &R, int g, uint64_t s)
 {
-    const uint64_t m = (1ULL << R.n_sites) - 1ULL;
-    const uint64_t u = repr_translate(tab, R.n_chunks, g, s & m), d = repr_translate(tab, R.n_chunks, g, s >> R.n_sites);
-    return u | (d << R.n_sites);
+    return hubrepr_parity(R, g, s & ((1ULL << R.n_sites) - 1ULL)) ^ hubrepr_parity(R, g, s >> R.n_sites);
 }
 
 // smallest image, the translation that produces it and the sign of T_{g*}
 __device__ __forceinline__ uint64_t hubrepr_canonical(const HubReprDev &R, const uint64_t *tab, uint64_t s, int *gstar, int *parity)
 {
-    uint64_t best = s;
-    int gb = 0;
-    for (int g = 1; g < R.n_trans; ++g) {
-        const uint64_t t = hubrepr_translate(R, tab, g, s);
-        if (t < best) {
-            best = t;
-            gb = g;
-        }
-    }
-    *gstar = gb;
-    const uint64_t m = (1ULL << R.n_sites) - 1ULL;
-    *parity = gb ? (hubrepr_parity(R, gb, s & m) ^ hubrepr_parity(R, gb, s >> R.n_sites)) : 0;
+    const uint64_t best = sector_canonical(R, tab, s, gstar);
+    *parity = *gstar ? sector_parity(R, *gstar, s) : 0;
     return best;
-}
-
-// pass 1 over all C(n, n_up) * C(n, n_dn) words in ascending order (rank = rank(d) * C(n, n_up) + rank(u)), one workgroup
-// per chunk of kHubChunk consecutive words: code = 0 if not a representative, else |S| | (zero-norm << 7); the number of
-// representatives per CHUNK (no per-word arrays besides the code byte: 4x5 at half filling has 3.4e10 words)
-constexpr int kHubRun = 16, kHubChunk = kHubRun * 256;
-
-__global__ __launch_bounds__(256) void k_hubrepr_flag(const HubReprDev *Rp, const uint64_t *tab, int64_t nstates, uint8_t *code,
-                                                      int32_t *chunk_cnt, int64_t nchunks)
-{
-    const HubReprDev &R = *Rp;
-    __shared__ int wsum[4];
-    const uint64_t cu = R.binom[R.n_sites][R.n_up];
-    const uint64_t mlow = (1ULL << R.n_sites) - 1ULL;
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const int64_t r0 = chunk * kHubChunk + (int64_t)threadIdx.x * kHubRun;
-        const int64_t r1 = (r0 + kHubRun < nstates) ? r0 + kHubRun : nstates;
-        int mine = 0;
-        if (r0 < nstates) {
-            uint64_t ru = (uint64_t)r0 % cu;
-            uint64_t u = unrank_k(R.binom, R.n_sites, R.n_up, ru), d = unrank_k(R.binom, R.n_sites, R.n_dn, (uint64_t)r0 / cu);
-            for (int64_t r = r0; r < r1; ++r) {
-                const uint64_t s = u | (d << R.n_sites);
-                bool rep = !(R.no_double && (u & d));     // t-J: words with a doubly occupied site are not in the space
-                int nstab = 1;
-                double sr = R.chr[0], si = R.chr[1];
-                for (int g = 1; rep && g < R.n_trans; ++g) {
-                    const uint64_t t = hubrepr_translate(R, tab, g, s);
-                    if (t < s) {
-                        rep = false;
-                        break;
-                    }
-                    if (t == s) {
-                        const double sg = (hubrepr_parity(R, g, u) ^ hubrepr_parity(R, g, d)) ? -1.0 : 1.0;
-                        nstab++;
-                        sr += sg * R.chr[2 * g];
-                        si += sg * R.chr[2 * g + 1];
-                    }
-                }
-                code[r] = rep ? (uint8_t)(nstab | ((sr * sr + si * si < 1e-20) ? 0x80 : 0)) : 0;
-                mine += rep ? 1 : 0;
-                if (++ru == cu) {                          // next down pattern, up patterns start over
-                    ru = 0;
-                    u = (R.n_up > 0) ? ((1ULL << R.n_up) - 1ULL) : 0ULL;
-                    d = R.n_dn > 0 ? next_same_popcount(d) & mlow : 0ULL;
-                } else {
-                    u = next_same_popcount(u);
-                }
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
-        __syncthreads();
-        if (threadIdx.x == 0) chunk_cnt[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
-}
-
-// pass 2: the representatives of a chunk go to reps[chunk_pos[chunk] ...] in ascending order
-__global__ __launch_bounds__(256) void k_hubrepr_compact(const HubReprDev *Rp, int64_t nstates, const uint8_t *code,
-                                                         const int64_t *chunk_pos, int64_t nchunks, uint64_t *reps, uint8_t *info)
-{
-    const HubReprDev &R = *Rp;
-    __shared__ int scan[256];
-    const uint64_t cu = R.binom[R.n_sites][R.n_up];
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const int64_t r0 = chunk * kHubChunk + (int64_t)threadIdx.x * kHubRun;
-        const int64_t r1 = (r0 + kHubRun < nstates) ? r0 + kHubRun : nstates;
-        int mine = 0;
-        for (int64_t r = r0; r < r1; ++r) mine += code[r] ? 1 : 0;
-        __syncthreads();
-        scan[threadIdx.x] = mine;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {          // inclusive Hillis-Steele scan
-            const int v = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-            __syncthreads();
-            scan[threadIdx.x] += v;
-            __syncthreads();
-        }
-        int64_t at = chunk_pos[chunk] + scan[threadIdx.x] - mine;
-        for (int64_t r = r0; r < r1; ++r) {
-            if (!code[r]) continue;
-            const uint64_t u = unrank_k(R.binom, R.n_sites, R.n_up, (uint64_t)r % cu);
-            const uint64_t d = unrank_k(R.binom, R.n_sites, R.n_dn, (uint64_t)r / cu);
-            reps[at] = u | (d << R.n_sites);
-            info[at] = code[r];
-            ++at;
-        }
-    }
 }
 
 // one row of the sector operator into (cols, vals), columns ascending, duplicates merged; returns its length
@@ -1540,11 +1307,7 @@ __device__ int hubrepr_row(const HubReprDev &R, const uint64_t *tab, const uint6
                            int32_t *cols, d2 *vals)
 {
     const uint8_t ci = info[i];
-    if (ci & 0x80) {
-        cols[0] = (int32_t)i;
-        vals[0] = d2{R.fake_pos + (double)i / (double)dim, 0.0};
-        return 1;
-    }
+    if (ci & 0x80) return row_zero_norm(R.fake_pos, dim, i, cols, vals);
     const double sa = (double)(ci & 0x7f);
     const uint64_t a = reps[i];
     const uint64_t mlow = (1ULL << R.n_sites) - 1ULL;
@@ -1578,31 +1341,14 @@ __device__ int hubrepr_row(const HubReprDev &R, const uint64_t *tab, const uint6
             int g = 0, pt = 0;
             const uint64_t b = hubrepr_canonical(R, tab, c, &g, &pt);
             par ^= pt;
-            int64_t lo = 0, hi = dim;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (reps[mid] < b) lo = mid + 1;
-                else hi = mid;
-            }
+            const int64_t lo = sector_find(reps, dim, b);
             const uint8_t cj = info[lo];
             if (cj & 0x80) continue;                       // zero-norm target
             const double f = (par ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
             // amp * conj(chi(g*)) * f
             const double cr = R.chr[2 * g], cim = -R.chr[2 * g + 1];
             const d2 v = {f * (ar * cr - ai * cim), f * (ar * cim + ai * cr)};
-            if (lo == i) {
-                dg += v;
-                continue;
-            }
-            int q = 1;
-            while (q < n && cols[q] != (int32_t)lo) ++q;
-            if (q < n) {
-                vals[q] += v;
-            } else if (n < kHubReprMaxRow) {
-                cols[n] = (int32_t)lo;
-                vals[n] = v;
-                ++n;
-            }
+            row_add(cols, vals, n, kHubReprMaxRow, i, lo, v, dg);
         }
     }
     // spin exchange xa * (S+_i S-_j + S-_i S+_j): the up particle of one site and the down particle of the other trade
@@ -1620,73 +1366,111 @@ __device__ int hubrepr_row(const HubReprDev &R, const uint64_t *tab, const uint6
             int g = 0, pt = 0;
             const uint64_t b = hubrepr_canonical(R, tab, c, &g, &pt);
             par ^= pt;
-            int64_t lo = 0, hi = dim;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (reps[mid] < b) lo = mid + 1;
-                else hi = mid;
-            }
+            const int64_t lo = sector_find(reps, dim, b);
             const uint8_t cj = info[lo];
             if (cj & 0x80) continue;
             const double f = (par ? -1.0 : 1.0) * R.xa[e] * sqrt((double)(cj & 0x7f) / sa);
             const d2 v = {f * R.chr[2 * g], -f * R.chr[2 * g + 1]};
-            if (lo == i) {
-                dg += v;
-                continue;
-            }
-            int q = 1;
-            while (q < n && cols[q] != (int32_t)lo) ++q;
-            if (q < n) {
-                vals[q] += v;
-            } else if (n < kHubReprMaxRow) {
-                cols[n] = (int32_t)lo;
-                vals[n] = v;
-                ++n;
-            }
+            row_add(cols, vals, n, kHubReprMaxRow, i, lo, v, dg);
         }
     }
-    vals[0] = dg;
-    int m = 1;
-    for (int q = 1; q < n; ++q)
-        if (vals[q].x * vals[q].x + vals[q].y * vals[q].y >= 1e-28) {
-            cols[m] = cols[q];
-            vals[m] = vals[q];
-            ++m;
-        }
-    for (int q = 1; q < m; ++q) {
-        const int32_t c = cols[q];
-        const d2 v = vals[q];
-        int p = q - 1;
-        while (p >= 0 && cols[p] > c) {
-            cols[p + 1] = cols[p];
-            vals[p + 1] = vals[p];
-            --p;
-        }
-        cols[p + 1] = c;
-        vals[p + 1] = v;
-    }
-    return m;
+    return row_finish(cols, vals, n, dg);
 }
 
-// the row function and the row capacity of each sector family, for the row kernels they share
-__device__ __forceinline__ int sector_row(const ReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim,
-                                          int64_t i, int32_t *cols, d2 *vals)
-{
-    return repr_row(R, tab, reps, info, dim, i, cols, vals);
-}
 __device__ __forceinline__ int sector_row(const HubReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
                                           int64_t dim, int64_t i, int32_t *cols, d2 *vals)
 {
     return hubrepr_row(R, tab, reps, info, dim, i, cols, vals);
 }
-template <class Dev> constexpr int max_row = 0;
-template <> constexpr int max_row<ReprDev> = kReprMaxRow;
-template <> constexpr int max_row<HubReprDev> = kHubReprMaxRow;
+
+// moprXvec_repr (src/model.cc:1715-1846, diagonal branch :1756-1759) for O = sum_s ( c_up[s] n_{s,up} + c_dn[s] n_{s,dn} )
+// with c_{g(s)} = eta(g) c_s (a density or S^z Fourier component).  Then O T_g = eta(g) T_g O, so O |a, k> = z_a |a, k*eta>
+// with z_a evaluated on the representative itself: |S_a| does not depend on the momentum (the fermion signs sit inside
+// T_g on both sides).  Representatives whose norm vanishes at the TARGET momentum get 0.
+struct HubCoef { double up_re[32], up_im[32], dn_re[32], dn_im[32]; };
+
+__global__ __launch_bounds__(256) void k_hubrepr_apply_diag(int n_sites, const uint64_t *reps, const uint8_t *info_new, int64_t dim,
+                                                            HubCoef cf, const d2 *x_old, d2 *y_new)
+{
+    const uint64_t mlow = (1ULL << n_sites) - 1ULL;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < dim; i += stride) {
+        d2 y = {0.0, 0.0};
+        if (!(info_new[i] & 0x80)) {
+            const uint64_t a = reps[i];
+            uint64_t u = a & mlow, d = a >> n_sites;
+            double zr = 0.0, zi = 0.0;
+            while (u) {
+                const int s = __ffsll((long long)u) - 1;
+                u &= u - 1;
+                zr += cf.up_re[s];
+                zi += cf.up_im[s];
+            }
+            while (d) {
+                const int s = __ffsll((long long)d) - 1;
+                d &= d - 1;
+                zr += cf.dn_re[s];
+                zi += cf.dn_im[s];
+            }
+            const d2 x = x_old[i];
+            y = d2{zr * x.x - zi * x.y, zr * x.y + zi * x.x};
+        }
+        y_new[i] = y;
+    }
+}
+
+// moprXvec_repr (src/model.cc:1715-1846, general branch) for  O = sum_s coef[s] c_{s,sigma}  (kind -1) or
+// sum_s coef[s] c^dag_{s,sigma} (kind +1) with coef_{g(s)} = eta(g) coef_s -- the operators of the single-particle spectral
+// function.  O T_g = eta(g) T_g O, so with chi' = chi * eta
+//     O |a, k> = sum_s coef_s sgn_s(a) sigma(g_c) chi'(g_c) sqrt(|S_b| / |S_a|) |b, k'>,   c = a -/+ s,  T_{g_c} |c> = sigma |b>,
+// sgn_s = (-1)^(operators left of (s, sigma) in the word's operator string: all up ascending, then all down ascending).
+// One lane per old representative scatters into the new sector with fp64 atomics.
+__global__ __launch_bounds__(128) void k_hubrepr_apply_c(const HubReprDev *Rnew, const uint64_t *tab, const uint64_t *reps_old,
+                                                         const uint8_t *info_old, int64_t dim_old, const uint64_t *reps_new,
+                                                         const uint8_t *info_new, int64_t dim_new, int species, int create,
+                                                         HubCoef cf, const d2 *x_old, double *y_new)
+{
+    const HubReprDev &R = *Rnew;
+    const int n = R.n_sites;
+    const uint64_t mlow = (1ULL << n) - 1ULL;
+    const int64_t stride = (int64_t)gridDim.x * 128;
+    for (int64_t i = (int64_t)blockIdx.x * 128 + threadIdx.x; i < dim_old; i += stride) {
+        const uint8_t ci = info_old[i];
+        if (ci & 0x80) continue;
+        const d2 x = x_old[i];
+        if (x.x == 0.0 && x.y == 0.0) continue;
+        const double sa = (double)(ci & 0x7f);
+        const uint64_t a = reps_old[i];
+        const uint64_t au = a & mlow, ad = a >> n;
+        const uint64_t occ = species ? ad : au;
+        const int left0 = species ? __popcll(au) : 0;      // the whole up block stands left of every down operator
+        for (int s = 0; s < n; ++s) {
+            const bool has = (occ >> s) & 1ULL;
+            if (create ? has : !has) continue;
+            const double cr0 = species ? cf.dn_re[s] : cf.up_re[s], ci0 = species ? cf.dn_im[s] : cf.up_im[s];
+            if (cr0 == 0.0 && ci0 == 0.0) continue;
+            int par = (left0 + __popcll(occ & ((1ULL << s) - 1ULL))) & 1;
+            const uint64_t occ2 = occ ^ (1ULL << s);
+            const uint64_t c = species ? (au | (occ2 << n)) : (occ2 | (ad << n));
+            int g = 0, pt = 0;
+            const uint64_t b = hubrepr_canonical(R, tab, c, &g, &pt);
+            par ^= pt;
+            const int64_t lo = sector_find(reps_new, dim_new, b);
+            const uint8_t cj = info_new[lo];
+            if (cj & 0x80) continue;
+            const double f = (par ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
+            // w = coef * chi'(g_c) * f
+            const double wr = f * (cr0 * R.chr[2 * g] - ci0 * R.chr[2 * g + 1]);
+            const double wi = f * (cr0 * R.chr[2 * g + 1] + ci0 * R.chr[2 * g]);
+            atomicAdd(&y_new[2 * lo], wr * x.x - wi * x.y);
+            atomicAdd(&y_new[2 * lo + 1], wr * x.y + wi * x.x);
+        }
+    }
+}
 
 // ------------------------------------ d-level sites in translation-symmetric sectors (qbh_gen_qudit_repr) --
 // Words packed as in qbh_gen_qudit (site s in bits [s b, (s+1) b), qbh_qudit.hpp), so the chunk tables of sector_symmetry
-// with `bits` = b translate them and the integer order of the words is the generator's order.  Basis: ALL orbit
-// representatives (smallest image) of the charge-`total` words, ascending; zero-norm ones are decoupled fake rows.  Row a:
+// with `bits` = b translate them and the integer order of the words is the generator's order.  Row a:
 //     O[a][b] = sum over the pair entries <a|M|c> that move a to c, b = g* c:  <a|M|c> * conj(chi(g*)) * sqrt(|S_b|/|S_a|)
 // (the Heisenberg convention above; no signs: bosons and spins).
 constexpr int kQuditReprMaxRow = 160;     // entries of one row before merging, counted from the merged terms
@@ -1702,120 +1486,31 @@ struct QuditReprDev {
 };
 template <> constexpr int max_row<QuditReprDev> = kQuditReprMaxRow;
 
-__device__ __forceinline__ uint64_t qrepr_canonical(const QuditReprDev &R, const uint64_t *tab, uint64_t s, int *gstar)
+uint64_t sector_word_count(const QuditReprDev &R, std::vector<uint64_t> &cum)    // cum: the counting table of qd_unrank
 {
-    uint64_t best = s;
-    int gb = 0;
-    for (int g = 1; g < R.n_trans; ++g) {
-        const uint64_t t = repr_translate(tab, R.n_chunks, g, s);
-        if (t < best) {
-            best = t;
-            gb = g;
-        }
-    }
-    *gstar = gb;
-    return best;
+    std::vector<uint64_t> dims;
+    qudit_table(R.n_sites, R.d, R.tw, cum, dims);
+    return dims[(size_t)R.total];
 }
-
-// pass 1 over the words of the sector in ascending order, one workgroup per chunk of kHubChunk consecutive words (the
-// layout of k_hubrepr_flag: one code byte per word, one count per chunk).  A lane unranks the first of its kHubRun words
-// and steps to the next word of the same charge from there.
-__global__ __launch_bounds__(256) void k_qrepr_flag(const QuditReprDev *Rp, const uint64_t *tab, int64_t nstates, uint8_t *code,
-                                                    int32_t *chunk_cnt, int64_t nchunks)
+int sector_tables(QuditReprDev &R, const std::vector<uint64_t> &cum, std::vector<void *> &pool)
 {
-    const QuditReprDev &R = *Rp;
-    __shared__ int wsum[4];
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const int64_t r0 = chunk * kHubChunk + (int64_t)threadIdx.x * kHubRun;
-        const int64_t r1 = (r0 + kHubRun < nstates) ? r0 + kHubRun : nstates;
-        int mine = 0;
-        if (r0 < nstates) {
-            uint64_t s = qd_unrank(R.cum, R.n_sites, R.d, R.bits, R.tw, R.total, (uint64_t)r0);
-            for (int64_t r = r0; r < r1; ++r) {
-                bool rep = true;
-                int nstab = 1;
-                double sr = R.chr[0], si = R.chr[1];
-                for (int g = 1; g < R.n_trans; ++g) {
-                    const uint64_t t = repr_translate(tab, R.n_chunks, g, s);
-                    if (t < s) {
-                        rep = false;
-                        break;
-                    }
-                    if (t == s) {
-                        nstab++;
-                        sr += R.chr[2 * g];
-                        si += R.chr[2 * g + 1];
-                    }
-                }
-                code[r] = rep ? (uint8_t)(nstab | ((sr * sr + si * si < 1e-20) ? 0x80 : 0)) : 0;
-                mine += rep ? 1 : 0;
-                s = qd_next(s, R.n_sites, R.d, R.bits);
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
-        __syncthreads();
-        if (threadIdx.x == 0) chunk_cnt[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
+    uint64_t *d_cum = nullptr;
+    QBH_TRY(upload(cum, &d_cum, pool));
+    R.cum = d_cum;
+    return QBH_OK;
 }
-
-// pass 2: the representatives of a chunk go to reps[chunk_pos[chunk] ...] in ascending order
-__global__ __launch_bounds__(256) void k_qrepr_compact(const QuditReprDev *Rp, int64_t nstates, const uint8_t *code,
-                                                       const int64_t *chunk_pos, int64_t nchunks, uint64_t *reps, uint8_t *info)
+__device__ __forceinline__ uint64_t sector_seek(const QuditReprDev &R, uint64_t r)
 {
-    const QuditReprDev &R = *Rp;
-    __shared__ int scan[256];
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const int64_t r0 = chunk * kHubChunk + (int64_t)threadIdx.x * kHubRun;
-        const int64_t r1 = (r0 + kHubRun < nstates) ? r0 + kHubRun : nstates;
-        int mine = 0;
-        for (int64_t r = r0; r < r1; ++r) mine += code[r] ? 1 : 0;
-        __syncthreads();
-        scan[threadIdx.x] = mine;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {          // inclusive Hillis-Steele scan
-            const int v = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-            __syncthreads();
-            scan[threadIdx.x] += v;
-            __syncthreads();
-        }
-        if (mine == 0) continue;
-        int64_t at = chunk_pos[chunk] + scan[threadIdx.x] - mine;
-        uint64_t s = qd_unrank(R.cum, R.n_sites, R.d, R.bits, R.tw, R.total, (uint64_t)r0);
-        for (int64_t r = r0; r < r1; ++r) {
-            if (code[r]) {
-                reps[at] = s;
-                info[at] = code[r];
-                ++at;
-            }
-            s = qd_next(s, R.n_sites, R.d, R.bits);
-        }
-    }
+    return qd_unrank(R.cum, R.n_sites, R.d, R.bits, R.tw, R.total, r);
 }
-
-// position of representative b in the ascending list reps[0, dim)
-__device__ __forceinline__ int64_t qrepr_find(const uint64_t *reps, int64_t dim, uint64_t b)
-{
-    int64_t lo = 0, hi = dim;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (reps[mid] < b) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
+__device__ __forceinline__ void sector_step(const QuditReprDev &R, uint64_t &cur) { cur = qd_next(cur, R.n_sites, R.d, R.bits); }
 
 // one row of the sector operator into (cols, vals), columns ascending, duplicates merged; returns its length
 __device__ int qrepr_row(const QuditReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
                          int32_t *cols, d2 *vals)
 {
     const uint8_t ci = info[i];
-    if (ci & 0x80) {
-        cols[0] = (int32_t)i;
-        vals[0] = d2{R.fake_pos + (double)i / (double)dim, 0.0};
-        return 1;
-    }
+    if (ci & 0x80) return row_zero_norm(R.fake_pos, dim, i, cols, vals);
     const double sa = (double)(ci & 0x7f);
     const uint64_t a = reps[i];
     const int d2n = R.d * R.d;
@@ -1835,50 +1530,18 @@ __device__ int qrepr_row(const QuditReprDev &R, const uint64_t *tab, const uint6
             const uint64_t c = (a & ~((field << (si * R.bits)) | (field << (sj * R.bits)))) | ((uint64_t)(o & 0xff) << (si * R.bits)) |
                                ((uint64_t)(o >> 8) << (sj * R.bits));
             int g = 0;
-            const uint64_t b = qrepr_canonical(R, tab, c, &g);
-            const int64_t lo = qrepr_find(reps, dim, b);
+            const uint64_t b = sector_canonical(R, tab, c, &g);
+            const int64_t lo = sector_find(reps, dim, b);
             const uint8_t cj = info[lo];
             if (cj & 0x80) continue;      // zero-norm target: dropped
             const double f = sqrt((double)(cj & 0x7f) / sa);
             const d2 h = R.eval[e];
             const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];        // conj(chi(g*)) * sqrt(|S_b|/|S_a|)
             const d2 v = {h.x * cr - h.y * cim, h.x * cim + h.y * cr};
-            if (lo == i) {
-                dg += v;
-                continue;
-            }
-            int q = 1;
-            while (q < n && cols[q] != (int32_t)lo) ++q;
-            if (q < n) {
-                vals[q] += v;
-            } else if (n < kQuditReprMaxRow) {
-                cols[n] = (int32_t)lo;
-                vals[n] = v;
-                ++n;
-            }
+            row_add(cols, vals, n, kQuditReprMaxRow, i, lo, v, dg);
         }
     }
-    vals[0] = dg;
-    int m = 1;                            // drop cancelled off-diagonal entries, then sort by column
-    for (int q = 1; q < n; ++q)
-        if (vals[q].x * vals[q].x + vals[q].y * vals[q].y >= 1e-28) {
-            cols[m] = cols[q];
-            vals[m] = vals[q];
-            ++m;
-        }
-    for (int q = 1; q < m; ++q) {
-        const int32_t c = cols[q];
-        const d2 v = vals[q];
-        int p = q - 1;
-        while (p >= 0 && cols[p] > c) {
-            cols[p + 1] = cols[p];
-            vals[p + 1] = vals[p];
-            --p;
-        }
-        cols[p + 1] = c;
-        vals[p + 1] = v;
-    }
-    return m;
+    return row_finish(cols, vals, n, dg);
 }
 
 __device__ __forceinline__ int sector_row(const QuditReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
@@ -1912,8 +1575,8 @@ __global__ __launch_bounds__(256) void k_qrepr_mopr(const QuditReprDev *Rold, co
                 if ((lr == 0.0 && li == 0.0) || (cf.ca[s] == 0.0 && cf.cb[s] == 0.0)) continue;
                 const uint64_t c = (b & ~(field << (s * R.bits))) | ((uint64_t)ls << (s * R.bits));
                 int g = 0;
-                const uint64_t a = qrepr_canonical(R, tab, c, &g);
-                const int64_t lo = qrepr_find(reps_old, dim_old, a);
+                const uint64_t a = sector_canonical(R, tab, c, &g);
+                const int64_t lo = sector_find(reps_old, dim_old, a);
                 const uint8_t ca = info_old[lo];
                 if (ca & 0x80) continue;
                 const double f = sqrt((double)(ca & 0x7f) / sb);
@@ -1926,6 +1589,97 @@ __global__ __launch_bounds__(256) void k_qrepr_mopr(const QuditReprDev *Rold, co
             }
         }
         y_new[i] = d2{ar, ai};
+    }
+}
+
+// ------------------------------------ the enumeration and the row kernels every family shares --
+// The basis of a sector is ALL orbit representatives (the smallest word of each orbit) of the family's words, ascending; a
+// representative whose (signed) character sum over its stabiliser vanishes has zero norm at this momentum and stays in the
+// basis as a decoupled fake row (row_zero_norm).  Two passes over the words in ascending order, one workgroup per chunk of
+// kSectorChunk consecutive words, a lane seeking the first of its kSectorRun words and stepping from there.  Nothing is
+// kept per word besides one code byte (4x5 Hubbard at half filling has 3.4e10 words): the counts are per chunk.
+constexpr int kSectorRun = 16, kSectorChunk = kSectorRun * 256;
+
+// pass 1: code[r] = 0 if the word of rank r is not a representative, else |S| | (zero-norm << 7); chunk_cnt = the number of
+// representatives of each chunk
+template <class Dev>
+__global__ __launch_bounds__(256) void k_sector_flag(const Dev *Rp, const uint64_t *tab, int64_t nstates, uint8_t *code,
+                                                     int32_t *chunk_cnt, int64_t nchunks)
+{
+    const Dev &R = *Rp;
+    __shared__ int wsum[4];
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int64_t r0 = chunk * kSectorChunk + (int64_t)threadIdx.x * kSectorRun;
+        const int64_t r1 = (r0 + kSectorRun < nstates) ? r0 + kSectorRun : nstates;
+        int mine = 0;
+        if (r0 < nstates) {
+            auto cur = sector_seek(R, (uint64_t)r0);
+            for (int64_t r = r0; r < r1; ++r) {
+                const uint64_t s = sector_word(R, cur);
+                bool rep = sector_allowed(R, s);
+                int nstab = 1;
+                double sr = R.chr[0], si = R.chr[1];
+                for (int g = 1; rep && g < R.n_trans; ++g) {
+                    const uint64_t t = sector_translate(R, tab, g, s);
+                    if (t < s) {
+                        rep = false;
+                        break;
+                    }
+                    if (t == s) {
+                        const double sg = sector_parity(R, g, s) ? -1.0 : 1.0;
+                        nstab++;
+                        sr += sg * R.chr[2 * g];
+                        si += sg * R.chr[2 * g + 1];
+                    }
+                }
+                code[r] = rep ? (uint8_t)(nstab | ((sr * sr + si * si < 1e-20) ? 0x80 : 0)) : 0;
+                mine += rep ? 1 : 0;
+                sector_step(R, cur);
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
+        __syncthreads();
+        if (threadIdx.x == 0) chunk_cnt[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+
+// pass 2: the representatives of a chunk go to reps[chunk_pos[chunk] ...] in ascending order, their codes to info[].  Every
+// lane takes every barrier of every chunk; only the walk through its own run depends on what the lane found.
+template <class Dev>
+__global__ __launch_bounds__(256) void k_sector_compact(const Dev *Rp, int64_t nstates, const uint8_t *code, const int64_t *chunk_pos,
+                                                        int64_t nchunks, uint64_t *reps, uint8_t *info)
+{
+    const Dev &R = *Rp;
+    __shared__ int scan[256];
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int64_t r0 = chunk * kSectorChunk + (int64_t)threadIdx.x * kSectorRun;
+        const int64_t r1 = (r0 + kSectorRun < nstates) ? r0 + kSectorRun : nstates;
+        int mine = 0;
+        for (int64_t r = r0; r < r1; ++r) mine += code[r] ? 1 : 0;
+        __syncthreads();
+        scan[threadIdx.x] = mine;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {          // inclusive Hillis-Steele scan
+            const int v = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
+            __syncthreads();
+            scan[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (mine > 0) {                                    // then r0 < nstates, and the walk ends at the lane's last one
+            int64_t at = chunk_pos[chunk] + scan[threadIdx.x] - mine;
+            auto cur = sector_seek(R, (uint64_t)r0);
+            for (int64_t r = r0; mine > 0; ++r) {
+                if (code[r]) {
+                    reps[at] = sector_word(R, cur);
+                    info[at] = code[r];
+                    ++at;
+                    --mine;
+                }
+                sector_step(R, cur);
+            }
+        }
     }
 }
 
@@ -1986,6 +1740,77 @@ __global__ __launch_bounds__(128) void k_sector_fill_coded(const Dev *Rp, const 
     }
 }
 
+// number of words of the sector, refused beyond what one code byte per word can enumerate; ctab as in sector_word_count
+template <class Dev>
+int sector_words(const Dev &R, std::vector<uint64_t> &ctab, int64_t *nstates, const char *who)
+{
+    const uint64_t n = sector_word_count(R, ctab);
+    if (n >= (1ULL << 40)) {
+        set_error("%s: sector too large to enumerate", who);
+        return QBH_EUNSUPP;
+    }
+    *nstates = (int64_t)n;
+    return QBH_OK;
+}
+
+// a sector on the device: the family's struct, the translation tables, the representatives and their info bytes
+template <class Dev>
+struct SectorDev {
+    Dev *R = nullptr;
+    uint64_t *tab = nullptr, *reps = nullptr;
+    uint8_t *info = nullptr;          // |S| | zero-norm << 7
+    int64_t dim = 0;
+};
+
+// enumerates the sector described by R (its term pointers already set, or unused); everything in S joins `pool`
+template <class Dev>
+int sector_enumerate(const Dev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, SectorDev<Dev> &S, const char *who)
+{
+    int64_t nstates = 0;
+    std::vector<uint64_t> ctab;
+    QBH_TRY(sector_words(R, ctab, &nstates, who));
+    std::vector<Dev> rr(1, R);
+    QBH_TRY(sector_tables(rr[0], ctab, pool));
+    QBH_TRY(upload(rr, &S.R, pool));
+    QBH_TRY(upload(tab, &S.tab, pool));
+    const int64_t nchunks = (nstates + kSectorChunk - 1) / kSectorChunk;
+    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
+    DevBufs tmp;
+    uint8_t *d_code = nullptr;
+    int32_t *d_cnt = nullptr;
+    int64_t *d_pos = nullptr;
+    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
+    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
+    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
+    hipLaunchKernelGGL(k_sector_flag<Dev>, dim3(egrid), dim3(256), 0, 0, S.R, S.tab, nstates, d_code, d_cnt, nchunks);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_TRY(exclusive_scan(d_cnt, nchunks, d_pos, 0));
+    QBH_HIP_WHO(who, hipMemcpy(&S.dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (S.dim <= 0 || S.dim >= 2147483647LL) {         // row and column indices are int32
+        set_error("%s: sector dimension %lld out of range", who, (long long)S.dim);
+        return QBH_EUNSUPP;
+    }
+    QBH_HIP_WHO(who, qbh::dev_alloc(&S.reps, (size_t)S.dim * sizeof(uint64_t)));
+    pool.push_back(S.reps);
+    QBH_HIP_WHO(who, qbh::dev_alloc(&S.info, (size_t)S.dim));
+    pool.push_back(S.info);
+    hipLaunchKernelGGL(k_sector_compact<Dev>, dim3(egrid), dim3(256), 0, 0, S.R, nstates, d_code, d_pos, nchunks, S.reps, S.info);
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    return QBH_OK;
+}
+
+// R zeroed, then the symmetry part of the fixed-n_dn spin sector filled in (bonds and fake_pos are the caller's)
+int repr_symmetry(ReprDev &R, std::vector<uint64_t> &tab, int n_sites, int n_dn, int n_trans, const int32_t *perms,
+                  const double *chars, const char *who)
+{
+    memset(&R, 0, sizeof(R));
+    R.h.n_sites = n_sites;
+    R.h.n_dn = n_dn;
+    R.n_trans = n_trans;
+    return sector_symmetry(n_sites, n_trans, perms, chars, who, R.h.binom, R.chr, nullptr, R.n_chunks, tab);
+}
+
 // R zeroed, then the symmetry part of the (n_up, n_dn) sector filled in (the operator's terms are the caller's)
 int hubrepr_symmetry(HubReprDev &R, std::vector<uint64_t> &tab, int n_sites, int n_up, int n_dn, int n_trans, const int32_t *perms,
                      const double *chars, const char *who)
@@ -1996,49 +1821,6 @@ int hubrepr_symmetry(HubReprDev &R, std::vector<uint64_t> &tab, int n_sites, int
     R.n_dn = n_dn;
     R.n_trans = n_trans;
     return sector_symmetry(n_sites, n_trans, perms, chars, who, R.binom, R.chr, R.perm, R.n_chunks, tab);
-}
-
-// representatives (ascending) and their info bytes of the sector described by R; d_R, d_tab, d_reps and d_info join `pool`
-int hubrepr_enumerate(const HubReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, HubReprDev **d_R_out,
-                      uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
-{
-    const long double nst = (long double)binom_u64(R.n_sites, R.n_up) * (long double)binom_u64(R.n_sites, R.n_dn);
-    if (nst >= (long double)(1ULL << 40)) {
-        set_error("%s: sector too large to enumerate", who);
-        return QBH_EUNSUPP;
-    }
-    const int64_t nstates = (int64_t)(binom_u64(R.n_sites, R.n_up) * binom_u64(R.n_sites, R.n_dn));
-    QBH_TRY(upload(std::vector<HubReprDev>(1, R), d_R_out, pool));
-    QBH_TRY(upload(tab, d_tab_out, pool));
-    // one code byte per word, counts per chunk of kHubChunk words
-    const int64_t nchunks = (nstates + kHubChunk - 1) / kHubChunk;
-    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
-    DevBufs tmp;
-    uint8_t *d_code = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr;
-    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
-    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
-    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_hubrepr_flag, dim3(egrid), dim3(256), 0, 0, *d_R_out, *d_tab_out, nstates, d_code, d_cnt, nchunks);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_TRY(exclusive_scan(d_cnt, nchunks, d_pos, 0));
-    int64_t dim = 0;
-    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (dim <= 0 || dim >= 2147483647LL) {
-        set_error("%s: sector dimension %lld out of range", who, (long long)dim);
-        return QBH_EUNSUPP;
-    }
-    QBH_HIP_WHO(who, qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
-    pool.push_back(*d_reps_out);
-    QBH_HIP_WHO(who, qbh::dev_alloc(d_info_out, (size_t)dim));
-    pool.push_back(*d_info_out);
-    hipLaunchKernelGGL(k_hubrepr_compact, dim3(egrid), dim3(256), 0, 0, *d_R_out, nstates, d_code, d_pos, nchunks, *d_reps_out,
-                       *d_info_out);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_HIP_WHO(who, hipDeviceSynchronize());
-    *dim_out = dim;
-    return QBH_OK;
 }
 
 // one-body terms amp * c^dag_i c_j merged on the same (i, j): (up re, up im, dn re, dn im)
@@ -2118,64 +1900,6 @@ int qrepr_invariant(const QuditTerms &T, int n_sites, int d, int n_trans, const 
                     return QBH_EINVAL;
                 }
     }
-    return QBH_OK;
-}
-
-// number of words of the sector, refused beyond what one code byte per word can enumerate
-int qrepr_words(int n_sites, int d, int total, int64_t *nstates, const char *who)
-{
-    std::vector<uint64_t> cum, dims;
-    qudit_table(n_sites, d, total + 1, cum, dims);
-    if (dims[(size_t)total] >= (1ULL << 40)) {
-        set_error("%s: sector too large to enumerate (%llu words)", who, (unsigned long long)dims[(size_t)total]);
-        return QBH_EUNSUPP;
-    }
-    *nstates = (int64_t)dims[(size_t)total];
-    return QBH_OK;
-}
-
-// representatives (ascending) and their info bytes of the sector described by R (its term pointers already set, or unused);
-// the counting table, d_R, d_tab, d_reps and d_info join `pool`
-int qrepr_enumerate(const QuditReprDev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, QuditReprDev **d_R_out,
-                    uint64_t **d_tab_out, uint64_t **d_reps_out, uint8_t **d_info_out, int64_t *dim_out, const char *who)
-{
-    int64_t nstates = 0;
-    QBH_TRY(qrepr_words(R.n_sites, R.d, R.total, &nstates, who));
-    std::vector<uint64_t> cum, dims;
-    qudit_table(R.n_sites, R.d, R.tw, cum, dims);
-    std::vector<QuditReprDev> rr(1, R);
-    uint64_t *d_cum = nullptr;
-    QBH_TRY(upload(cum, &d_cum, pool));
-    rr[0].cum = d_cum;
-    QBH_TRY(upload(rr, d_R_out, pool));
-    QBH_TRY(upload(tab, d_tab_out, pool));
-    const int64_t nchunks = (nstates + kHubChunk - 1) / kHubChunk;
-    const int egrid = (int)std::min<int64_t>(nchunks, 256 * 32);
-    DevBufs tmp;
-    uint8_t *d_code = nullptr;
-    int32_t *d_cnt = nullptr;
-    int64_t *d_pos = nullptr;
-    QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
-    QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
-    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_qrepr_flag, dim3(egrid), dim3(256), 0, 0, *d_R_out, *d_tab_out, nstates, d_code, d_cnt, nchunks);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_TRY(exclusive_scan(d_cnt, nchunks, d_pos, 0));
-    int64_t dim = 0;
-    QBH_HIP_WHO(who, hipMemcpy(&dim, d_pos + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (dim <= 0 || dim >= 2147483647LL) {
-        set_error("%s: sector dimension %lld out of range", who, (long long)dim);
-        return QBH_EUNSUPP;
-    }
-    QBH_HIP_WHO(who, qbh::dev_alloc(d_reps_out, (size_t)dim * sizeof(uint64_t)));
-    pool.push_back(*d_reps_out);
-    QBH_HIP_WHO(who, qbh::dev_alloc(d_info_out, (size_t)dim));
-    pool.push_back(*d_info_out);
-    hipLaunchKernelGGL(k_qrepr_compact, dim3(egrid), dim3(256), 0, 0, *d_R_out, nstates, d_code, d_pos, nchunks, *d_reps_out,
-                       *d_info_out);
-    QBH_HIP_WHO(who, hipGetLastError());
-    QBH_HIP_WHO(who, hipDeviceSynchronize());
-    *dim_out = dim;
     return QBH_OK;
 }
 
@@ -2294,6 +2018,7 @@ static int assemble_sector_rows(const char *who, std::vector<void *> &pool, cons
     return qbh_csr_create_device(out, nloc, dim, r0, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
 }
 
+// ---- the entry points: validate -> symmetry -> the family's terms -> sector_enumerate -> the rows, or the operator's kernel ----
 static int gen_heisenberg_repr_impl(qbh_csr **out, int n_sites, int n_dn, int n_bonds, const int32_t *bonds, double J,
                                        int n_trans, const int32_t *perms, const double *chars, double fake_pos,
                                        int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
@@ -2328,19 +2053,10 @@ static int gen_heisenberg_repr_impl(qbh_csr **out, int n_sites, int n_dn, int n_
         R.h.n_bonds++;
     }
     R.fake_pos = fake_pos;
-    if (binom_u64(n_sites, n_dn) >= (1ULL << 40)) {
-        set_error("qbh_gen_heisenberg_repr: sector too large to enumerate");
-        return QBH_EUNSUPP;
-    }
-    std::vector<void *> pool;
-    ReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr, *d_reps = nullptr;
-    uint8_t *d_info = nullptr;
-    int64_t dim = 0;
-    int rc = repr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, who);
-    if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
-    free_pool(pool);
-    return rc;
+    DevBufs bufs;
+    SectorDev<ReprDev> S;
+    QBH_TRY(sector_enumerate(R, tab, bufs.pool, S, who));
+    return assemble_sector_rows(who, bufs.pool, S.R, S.tab, S.reps, S.info, S.dim, shard, n_shards, row_cuts, opts, out, dim_out);
 }
 
 static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn, int n_terms, const int32_t *term_sites,
@@ -2407,18 +2123,12 @@ static int gen_hubbard_repr_impl(qbh_csr **out, int n_sites, int n_up, int n_dn,
     }
     R.n_exch = n_exch;
     R.no_double = no_double ? 1 : 0;
-    std::vector<void *> pool;
-    HubReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr, *d_reps = nullptr;
-    uint8_t *d_info = nullptr;
-    int64_t dim = 0;
-    int rc = hubrepr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, who);
-    if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
-    free_pool(pool);
-    return rc;
+    DevBufs bufs;
+    SectorDev<HubReprDev> S;
+    QBH_TRY(sector_enumerate(R, tab, bufs.pool, S, who));
+    return assemble_sector_rows(who, bufs.pool, S.R, S.tab, S.reps, S.info, S.dim, shard, n_shards, row_cuts, opts, out, dim_out);
 }
 
-// ------------------------------ d-level sites in momentum sectors: qbh_gen_qudit_repr, qbh_mopr_qudit_repr_dev --
 static int gen_qudit_repr_impl(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
                                const qbh_z *pair_mat, int n_single, const int32_t *single_sites, const double *single_diag,
                                int n_trans, const int32_t *perms, const double *chars, double fake_pos, int shard, int n_shards,
@@ -2451,7 +2161,8 @@ static int gen_qudit_repr_impl(qbh_csr **out, int n_sites, int d, int total, int
         return QBH_EUNSUPP;
     }
     int64_t nstates = 0;
-    QBH_TRY(qrepr_words(n_sites, d, total, &nstates, who));
+    std::vector<uint64_t> ctab;
+    QBH_TRY(sector_words(R, ctab, &nstates, who));       // every refusal comes before the device is looked for
     if (qbh_device_count() <= 0) {
         set_error("no HIP device visible");
         return QBH_ENODEVICE;
@@ -2459,25 +2170,20 @@ static int gen_qudit_repr_impl(qbh_csr **out, int n_sites, int d, int total, int
     if (opts && opts->device >= 0) QBH_HIP_WHO(who, hipSetDevice(opts->device));
     R.n_pairs = (int)T.pm.size();
     R.fake_pos = fake_pos;
-    std::vector<void *> pool;
+    DevBufs bufs;
     int32_t *pij = nullptr, *eo = nullptr, *eu = nullptr;
     double *pd = nullptr, *sd = nullptr;
     d2 *ev = nullptr;
-    int rc = upload(T.pair_ij, &pij, pool);
-    if (rc == QBH_OK) rc = upload(T.eoff, &eo, pool);
-    if (rc == QBH_OK) rc = upload(T.eout, &eu, pool);
-    if (rc == QBH_OK) rc = upload(T.pdiag, &pd, pool);
-    if (rc == QBH_OK) rc = upload(T.sdiag, &sd, pool);
-    if (rc == QBH_OK) rc = upload(T.eval, &ev, pool);
+    QBH_TRY(upload(T.pair_ij, &pij, bufs.pool));
+    QBH_TRY(upload(T.eoff, &eo, bufs.pool));
+    QBH_TRY(upload(T.eout, &eu, bufs.pool));
+    QBH_TRY(upload(T.pdiag, &pd, bufs.pool));
+    QBH_TRY(upload(T.sdiag, &sd, bufs.pool));
+    QBH_TRY(upload(T.eval, &ev, bufs.pool));
     R.pair_ij = pij; R.eoff = eo; R.eout = eu; R.pdiag = pd; R.sdiag = sd; R.eval = ev;
-    QuditReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr, *d_reps = nullptr;
-    uint8_t *d_info = nullptr;
-    int64_t dim = 0;
-    if (rc == QBH_OK) rc = qrepr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, who);
-    if (rc == QBH_OK) rc = assemble_sector_rows(who, pool, d_R, d_tab, d_reps, d_info, dim, shard, n_shards, row_cuts, opts, out, dim_out);
-    free_pool(pool);
-    return rc;
+    SectorDev<QuditReprDev> S;
+    QBH_TRY(sector_enumerate(R, tab, bufs.pool, S, who));
+    return assemble_sector_rows(who, bufs.pool, S.R, S.tab, S.reps, S.info, S.dim, shard, n_shards, row_cuts, opts, out, dim_out);
 }
 
 extern "C" int qbh_gen_qudit_repr(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
@@ -2496,6 +2202,84 @@ extern "C" int qbh_gen_qudit_repr_cuts(qbh_csr **out, int n_sites, int d, int to
 {
     return gen_qudit_repr_impl(out, n_sites, d, total, n_pairs, pair_sites, pair_mat, n_single, single_sites, single_diag, n_trans,
                                perms, chars, fake_pos, shard, n_shards, row_cuts, dim_out, opts);
+}
+
+// ---- operators between sectors.  perms / chars as in the generators; the vectors are indexed like the rows of the sector
+// operators (all representatives, ascending) ----
+// S^z_q (see k_repr_apply_sz), with the characters of the TARGET momentum
+extern "C" int qbh_mopr_sz_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars_new,
+                                    const qbh_z *coef, const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_out)
+{
+    using namespace qbh;
+    const char *who = "qbh_mopr_sz_repr_dev";
+    if (!perms || !chars_new || !coef || !d_vec_old || !d_vec_new || n_sites <= 0 || n_sites > 62 || n_dn < 0 || n_dn > n_sites ||
+        n_dn > 33 || n_trans < 1 || n_trans > kReprMaxTrans) {
+        set_error("qbh_mopr_sz_repr_dev: invalid argument");
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    std::vector<ReprDev> rr(1);
+    std::vector<uint64_t> tab;
+    QBH_TRY(repr_symmetry(rr[0], tab, n_sites, n_dn, n_trans, perms, chars_new, who));
+    SpinCoefR cf{};
+    for (int sidx = 0; sidx < n_sites; ++sidx) {
+        cf.re[sidx] = coef[sidx].re;
+        cf.im[sidx] = coef[sidx].im;
+    }
+    DevBufs bufs;
+    SectorDev<ReprDev> S;
+    QBH_TRY(sector_enumerate(rr[0], tab, bufs.pool, S, who));
+    hipLaunchKernelGGL(k_repr_apply_sz, dim3(blas_grid(S.dim)), dim3(256), 0, 0, n_sites, S.reps, S.info, S.dim, cf,
+                       reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    if (dim_out) *dim_out = S.dim;
+    return QBH_OK;
+}
+
+// S^-_q (kind -1: n_dn -> n_dn + 1) and S^+_q (kind +1: n_dn -> n_dn - 1) between momentum sectors; see k_repr_apply_flip.
+extern "C" int qbh_mopr_flip_repr_dev(int n_sites, int n_dn_old, int kind, int n_trans, const int32_t *perms, const double *chars_old,
+                                      const double *chars_new, const qbh_z *coef, const qbh_z *d_vec_old, qbh_z *d_vec_new,
+                                      int64_t *dim_old_out, int64_t *dim_new_out)
+{
+    using namespace qbh;
+    const char *who = "qbh_mopr_flip_repr_dev";
+    const int n_new = n_dn_old - kind;
+    if (!perms || !chars_old || !chars_new || !coef || !d_vec_old || !d_vec_new || (kind != -1 && kind != 1) || n_sites <= 0 ||
+        n_sites > 62 || n_dn_old < 0 || n_dn_old > n_sites || n_new < 0 || n_new > n_sites || n_dn_old > 33 || n_new > 33 || n_trans < 1 ||
+        n_trans > kReprMaxTrans) {
+        set_error("qbh_mopr_flip_repr_dev: invalid argument");
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    SpinCoefR cf{};
+    for (int sidx = 0; sidx < n_sites; ++sidx) {
+        cf.re[sidx] = coef[sidx].re;
+        cf.im[sidx] = coef[sidx].im;
+    }
+    std::vector<ReprDev> ro(1), rn(1);
+    std::vector<uint64_t> tab_o, tab_n;
+    QBH_TRY(repr_symmetry(ro[0], tab_o, n_sites, n_dn_old, n_trans, perms, chars_old, who));
+    QBH_TRY(repr_symmetry(rn[0], tab_n, n_sites, n_new, n_trans, perms, chars_new, who));
+    DevBufs bufs;
+    SectorDev<ReprDev> So, Sn;
+    QBH_TRY(sector_enumerate(ro[0], tab_o, bufs.pool, So, who));
+    QBH_TRY(sector_enumerate(rn[0], tab_n, bufs.pool, Sn, who));
+    QBH_HIP_WHO(who, hipMemset(d_vec_new, 0, (size_t)Sn.dim * sizeof(d2)));
+    hipLaunchKernelGGL(k_repr_apply_flip, dim3(blas_grid(So.dim)), dim3(128), 0, 0, Sn.R, Sn.tab, So.reps, So.info, So.dim, Sn.reps,
+                       Sn.info, Sn.dim, kind < 0 ? 1 : 0, cf, reinterpret_cast<const d2 *>(d_vec_old),
+                       reinterpret_cast<double *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    if (dim_old_out) *dim_old_out = So.dim;
+    if (dim_new_out) *dim_new_out = Sn.dim;
+    return QBH_OK;
 }
 
 // see k_qrepr_mopr; the target characters chi_old * eta follow from coef
@@ -2555,78 +2339,34 @@ extern "C" int qbh_mopr_qudit_repr_dev(int n_sites, int d, int total_old, int dq
     }
     QBH_TRY(qrepr_symmetry(Rn, tab_n, n_sites, d, total_new, n_trans, perms, chars_new.data(), who));
     int64_t nst = 0;
-    QBH_TRY(qrepr_words(n_sites, d, total_old, &nst, who));
-    QBH_TRY(qrepr_words(n_sites, d, total_new, &nst, who));
+    std::vector<uint64_t> ctab;
+    QBH_TRY(sector_words(Ro, ctab, &nst, who));          // every refusal comes before the device is looked for
+    QBH_TRY(sector_words(Rn, ctab, &nst, who));
     if (qbh_device_count() <= 0) {
         set_error("no HIP device visible");
         return QBH_ENODEVICE;
     }
     DevBufs bufs;
-    QuditReprDev *R_old = nullptr, *R_new = nullptr;
-    uint64_t *tab_old = nullptr, *tab_new = nullptr, *reps_old = nullptr, *reps_new = nullptr;
-    uint8_t *info_old = nullptr, *info_new = nullptr;
-    int64_t dim_old = 0, dim_new = 0;
-    QBH_TRY(qrepr_enumerate(Ro, tab, bufs.pool, &R_old, &tab_old, &reps_old, &info_old, &dim_old, who));
-    QBH_TRY(qrepr_enumerate(Rn, tab_n, bufs.pool, &R_new, &tab_new, &reps_new, &info_new, &dim_new, who));
+    SectorDev<QuditReprDev> So, Sn;
+    QBH_TRY(sector_enumerate(Ro, tab, bufs.pool, So, who));
+    QBH_TRY(sector_enumerate(Rn, tab_n, bufs.pool, Sn, who));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_qrepr_mopr, dim3(blas_grid(dim_new)), dim3(256), 0, st, R_old, tab_old, reps_old, info_old, dim_old, reps_new,
-                       info_new, dim_new, dq, cf, reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
+    hipLaunchKernelGGL(k_qrepr_mopr, dim3(blas_grid(Sn.dim)), dim3(256), 0, st, So.R, So.tab, So.reps, So.info, So.dim, Sn.reps, Sn.info,
+                       Sn.dim, dq, cf, reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
     QBH_HIP_WHO(who, hipGetLastError());
     QBH_HIP_WHO(who, hipStreamSynchronize(st));
-    if (dim_old_out) *dim_old_out = dim_old;
-    if (dim_new_out) *dim_new_out = dim_new;
+    if (dim_old_out) *dim_old_out = So.dim;
+    if (dim_new_out) *dim_new_out = Sn.dim;
     return QBH_OK;
 }
 
-// ------------------------- diagonal one-body operators between Hubbard momentum sectors --
-// moprXvec_repr (src/model.cc:1715-1846, diagonal branch :1756-1759) for the sectors of qbh_gen_hubbard_repr:
-// O = sum_s ( c_up[s] n_{s,up} + c_dn[s] n_{s,dn} ) with c_{g(s)} = eta(g) c_s (a density or S^z Fourier component).  Then
-// O T_g = eta(g) T_g O, so O |a, k> = z_a |a, k*eta> with z_a evaluated on the representative itself: the basis keeps ALL
-// representatives in every sector and |S_a| does not depend on the momentum (the fermion signs sit inside T_g on both
-// sides).  Representatives whose norm vanishes at the TARGET momentum get 0.
-namespace qbh {
-namespace {
-
-struct HubCoef { double up_re[32], up_im[32], dn_re[32], dn_im[32]; };
-
-__global__ __launch_bounds__(256) void k_hubrepr_apply_diag(int n_sites, const uint64_t *reps, const uint8_t *info_new, int64_t dim,
-                                                            HubCoef cf, const d2 *x_old, d2 *y_new)
-{
-    const uint64_t mlow = (1ULL << n_sites) - 1ULL;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < dim; i += stride) {
-        d2 y = {0.0, 0.0};
-        if (!(info_new[i] & 0x80)) {
-            const uint64_t a = reps[i];
-            uint64_t u = a & mlow, d = a >> n_sites;
-            double zr = 0.0, zi = 0.0;
-            while (u) {
-                const int s = __ffsll((long long)u) - 1;
-                u &= u - 1;
-                zr += cf.up_re[s];
-                zi += cf.up_im[s];
-            }
-            while (d) {
-                const int s = __ffsll((long long)d) - 1;
-                d &= d - 1;
-                zr += cf.dn_re[s];
-                zi += cf.dn_im[s];
-            }
-            const d2 x = x_old[i];
-            y = d2{zr * x.x - zi * x.y, zr * x.y + zi * x.x};
-        }
-        y_new[i] = y;
-    }
-}
-
-}  // namespace
-}  // namespace qbh
-
+// N_q / S^z_q between Hubbard momentum sectors (see k_hubrepr_apply_diag), with the characters of the TARGET momentum
 extern "C" int qbh_mopr_diag_hubrepr_dev(int n_sites, int n_up, int n_dn, int n_trans, const int32_t *perms, const double *chars_new,
                                          const qbh_z *coef_up, const qbh_z *coef_dn, const qbh_z *d_vec_old, qbh_z *d_vec_new,
                                          int64_t *dim_out)
 {
     using namespace qbh;
+    const char *who = "qbh_mopr_diag_hubrepr_dev";
     if (!perms || !chars_new || !coef_up || !coef_dn || !d_vec_old || !d_vec_new || n_sites <= 0 || n_sites > 31 || n_up < 0 ||
         n_up > n_sites || n_dn < 0 || n_dn > n_sites || n_trans < 1 || n_trans > kReprMaxTrans) {
         set_error("qbh_mopr_diag_hubrepr_dev: invalid argument");
@@ -2661,104 +2401,32 @@ extern "C" int qbh_mopr_diag_hubrepr_dev(int n_sites, int n_up, int n_dn, int n_
     }
     std::vector<HubReprDev> rr(1);
     std::vector<uint64_t> tab;
-    QBH_TRY(hubrepr_symmetry(rr[0], tab, n_sites, n_up, n_dn, n_trans, perms, chars_new, "qbh_mopr_diag_hubrepr_dev"));
-    std::vector<void *> pool;
-    HubReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr, *d_reps = nullptr;
-    uint8_t *d_info = nullptr;
-    int64_t dim = 0;
-    int rc = hubrepr_enumerate(rr[0], tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim, "qbh_mopr_diag_hubrepr_dev");
-    hipError_t e = hipSuccess;
-    if (rc == QBH_OK) {
-        HubCoef cf{};
-        for (int s = 0; s < n_sites; ++s) {
-            cf.up_re[s] = coef_up[s].re;
-            cf.up_im[s] = coef_up[s].im;
-            cf.dn_re[s] = coef_dn[s].re;
-            cf.dn_im[s] = coef_dn[s].im;
-        }
-        hipLaunchKernelGGL(k_hubrepr_apply_diag, dim3(blas_grid(dim)), dim3(256), 0, 0, n_sites, d_reps, d_info, dim, cf,
-                           reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
+    QBH_TRY(hubrepr_symmetry(rr[0], tab, n_sites, n_up, n_dn, n_trans, perms, chars_new, who));
+    HubCoef cf{};
+    for (int s = 0; s < n_sites; ++s) {
+        cf.up_re[s] = coef_up[s].re;
+        cf.up_im[s] = coef_up[s].im;
+        cf.dn_re[s] = coef_dn[s].re;
+        cf.dn_im[s] = coef_dn[s].im;
     }
-    free_pool(pool);
-    if (rc != QBH_OK) return rc;
-    if (e != hipSuccess) {
-        set_error("qbh_mopr_diag_hubrepr_dev: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return QBH_EHIP;
-    }
-    if (dim_out) *dim_out = dim;
+    DevBufs bufs;
+    SectorDev<HubReprDev> S;
+    QBH_TRY(sector_enumerate(rr[0], tab, bufs.pool, S, who));
+    hipLaunchKernelGGL(k_hubrepr_apply_diag, dim3(blas_grid(S.dim)), dim3(256), 0, 0, n_sites, S.reps, S.info, S.dim, cf,
+                       reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    if (dim_out) *dim_out = S.dim;
     return QBH_OK;
 }
 
-// --------------------- single-fermion operators between Hubbard momentum sectors ---------
-// moprXvec_repr (src/model.cc:1715-1846, general branch) for  O = sum_s coef[s] c_{s,sigma}  (kind -1) or
-// sum_s coef[s] c^dag_{s,sigma} (kind +1) with coef_{g(s)} = eta(g) coef_s -- the operators of the single-particle spectral
-// function.  O T_g = eta(g) T_g O, so with chi' = chi * eta
-//     O |a, k> = sum_s coef_s sgn_s(a) sigma(g_c) chi'(g_c) sqrt(|S_b| / |S_a|) |b, k'>,   c = a -/+ s,  T_{g_c} |c> = sigma |b>,
-// sgn_s = (-1)^(operators left of (s, sigma) in the word's operator string: all up ascending, then all down ascending).
-// One lane per old representative scatters into the new sector with fp64 atomics.
-namespace qbh {
-namespace {
-
-__global__ __launch_bounds__(128) void k_hubrepr_apply_c(const HubReprDev *Rnew, const uint64_t *tab, const uint64_t *reps_old,
-                                                         const uint8_t *info_old, int64_t dim_old, const uint64_t *reps_new,
-                                                         const uint8_t *info_new, int64_t dim_new, int species, int create,
-                                                         HubCoef cf, const d2 *x_old, double *y_new)
-{
-    const HubReprDev &R = *Rnew;
-    const int n = R.n_sites;
-    const uint64_t mlow = (1ULL << n) - 1ULL;
-    const int64_t stride = (int64_t)gridDim.x * 128;
-    for (int64_t i = (int64_t)blockIdx.x * 128 + threadIdx.x; i < dim_old; i += stride) {
-        const uint8_t ci = info_old[i];
-        if (ci & 0x80) continue;
-        const d2 x = x_old[i];
-        if (x.x == 0.0 && x.y == 0.0) continue;
-        const double sa = (double)(ci & 0x7f);
-        const uint64_t a = reps_old[i];
-        const uint64_t au = a & mlow, ad = a >> n;
-        const uint64_t occ = species ? ad : au;
-        const int left0 = species ? __popcll(au) : 0;      // the whole up block stands left of every down operator
-        for (int s = 0; s < n; ++s) {
-            const bool has = (occ >> s) & 1ULL;
-            if (create ? has : !has) continue;
-            const double cr0 = species ? cf.dn_re[s] : cf.up_re[s], ci0 = species ? cf.dn_im[s] : cf.up_im[s];
-            if (cr0 == 0.0 && ci0 == 0.0) continue;
-            int par = (left0 + __popcll(occ & ((1ULL << s) - 1ULL))) & 1;
-            const uint64_t occ2 = occ ^ (1ULL << s);
-            const uint64_t c = species ? (au | (occ2 << n)) : (occ2 | (ad << n));
-            int g = 0, pt = 0;
-            const uint64_t b = hubrepr_canonical(R, tab, c, &g, &pt);
-            par ^= pt;
-            int64_t lo = 0, hi = dim_new;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (reps_new[mid] < b) lo = mid + 1;
-                else hi = mid;
-            }
-            const uint8_t cj = info_new[lo];
-            if (cj & 0x80) continue;
-            const double f = (par ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
-            // w = coef * chi'(g_c) * f
-            const double wr = f * (cr0 * R.chr[2 * g] - ci0 * R.chr[2 * g + 1]);
-            const double wi = f * (cr0 * R.chr[2 * g + 1] + ci0 * R.chr[2 * g]);
-            atomicAdd(&y_new[2 * lo], wr * x.x - wi * x.y);
-            atomicAdd(&y_new[2 * lo + 1], wr * x.y + wi * x.x);
-        }
-    }
-}
-
-}  // namespace
-}  // namespace qbh
-
+// c_{q,sigma} (kind -1) / c^dag_{q,sigma} (kind +1) between Hubbard momentum sectors; see k_hubrepr_apply_c
 extern "C" int qbh_mopr_c_hubrepr_dev(int n_sites, int n_up_old, int n_dn_old, int species, int kind, int n_trans, const int32_t *perms,
                                       const double *chars_old, const double *chars_new, const qbh_z *coef, const qbh_z *d_vec_old,
                                       qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out)
 {
     using namespace qbh;
+    const char *who = "qbh_mopr_c_hubrepr_dev";
     if (!perms || !chars_old || !chars_new || !coef || !d_vec_old || !d_vec_new || n_sites <= 0 || n_sites > 31 || n_up_old < 0 ||
         n_up_old > n_sites || n_dn_old < 0 || n_dn_old > n_sites || n_trans < 1 || n_trans > kReprMaxTrans ||
         (species != 0 && species != 1) || (kind != 1 && kind != -1)) {
@@ -2772,40 +2440,25 @@ extern "C" int qbh_mopr_c_hubrepr_dev(int n_sites, int n_up_old, int n_dn_old, i
     }
     std::vector<HubReprDev> ro(1), rn(1);
     std::vector<uint64_t> tab_o, tab_n;
-    QBH_TRY(hubrepr_symmetry(ro[0], tab_o, n_sites, n_up_old, n_dn_old, n_trans, perms, chars_old, "qbh_mopr_c_hubrepr_dev"));
-    QBH_TRY(hubrepr_symmetry(rn[0], tab_n, n_sites, n_up_new, n_dn_new, n_trans, perms, chars_new, "qbh_mopr_c_hubrepr_dev"));
-    std::vector<void *> pool;
-    HubReprDev *d_Ro = nullptr, *d_Rn = nullptr;
-    uint64_t *d_tab_o = nullptr, *d_tab_n = nullptr, *reps_o = nullptr, *reps_n = nullptr;
-    uint8_t *info_o = nullptr, *info_n = nullptr;
-    int64_t dim_o = 0, dim_n = 0;
-    int rc = hubrepr_enumerate(ro[0], tab_o, pool, &d_Ro, &d_tab_o, &reps_o, &info_o, &dim_o, "qbh_mopr_c_hubrepr_dev");
-    if (rc == QBH_OK) rc = hubrepr_enumerate(rn[0], tab_n, pool, &d_Rn, &d_tab_n, &reps_n, &info_n, &dim_n, "qbh_mopr_c_hubrepr_dev");
-    hipError_t e = hipSuccess;
-    if (rc == QBH_OK) {
-        HubCoef cf{};
-        for (int s = 0; s < n_sites; ++s) {
-            cf.up_re[s] = cf.dn_re[s] = coef[s].re;
-            cf.up_im[s] = cf.dn_im[s] = coef[s].im;
-        }
-        e = hipMemset(d_vec_new, 0, (size_t)dim_n * sizeof(d2));
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_hubrepr_apply_c, dim3(blas_grid(dim_o)), dim3(128), 0, 0, d_Rn, d_tab_n, reps_o, info_o, dim_o, reps_n,
-                               info_n, dim_n, species, kind > 0 ? 1 : 0, cf, reinterpret_cast<const d2 *>(d_vec_old),
-                               reinterpret_cast<double *>(d_vec_new));
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
+    QBH_TRY(hubrepr_symmetry(ro[0], tab_o, n_sites, n_up_old, n_dn_old, n_trans, perms, chars_old, who));
+    QBH_TRY(hubrepr_symmetry(rn[0], tab_n, n_sites, n_up_new, n_dn_new, n_trans, perms, chars_new, who));
+    HubCoef cf{};
+    for (int s = 0; s < n_sites; ++s) {
+        cf.up_re[s] = cf.dn_re[s] = coef[s].re;
+        cf.up_im[s] = cf.dn_im[s] = coef[s].im;
     }
-    free_pool(pool);
-    if (rc != QBH_OK) return rc;
-    if (e != hipSuccess) {
-        set_error("qbh_mopr_c_hubrepr_dev: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return e == hipErrorOutOfMemory ? QBH_ENOMEM : QBH_EHIP;
-    }
-    if (dim_old_out) *dim_old_out = dim_o;
-    if (dim_new_out) *dim_new_out = dim_n;
+    DevBufs bufs;
+    SectorDev<HubReprDev> So, Sn;
+    QBH_TRY(sector_enumerate(ro[0], tab_o, bufs.pool, So, who));
+    QBH_TRY(sector_enumerate(rn[0], tab_n, bufs.pool, Sn, who));
+    QBH_HIP_WHO(who, hipMemset(d_vec_new, 0, (size_t)Sn.dim * sizeof(d2)));
+    hipLaunchKernelGGL(k_hubrepr_apply_c, dim3(blas_grid(So.dim)), dim3(128), 0, 0, Sn.R, Sn.tab, So.reps, So.info, So.dim, Sn.reps,
+                       Sn.info, Sn.dim, species, kind > 0 ? 1 : 0, cf, reinterpret_cast<const d2 *>(d_vec_old),
+                       reinterpret_cast<double *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    if (dim_old_out) *dim_old_out = So.dim;
+    if (dim_new_out) *dim_new_out = Sn.dim;
     return QBH_OK;
 }
 
@@ -2855,39 +2508,15 @@ __device__ int hubrepr_row_rem(const HubReprDev &R, const uint64_t *tab, const u
         int g = 0, pt = 0;
         const uint64_t b = hubrepr_canonical(R, tab, c, &g, &pt);
         par ^= pt;
-        int64_t l2 = 0, h2 = dim;
-        while (l2 < h2) {
-            const int64_t mid = (l2 + h2) >> 1;
-            if (reps[mid] < b) l2 = mid + 1;
-            else h2 = mid;
-        }
+        const int64_t l2 = sector_find(reps, dim, b);
         const uint8_t cj = info[l2];
         if (cj & 0x80) continue;
         const double f = (par ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
         const double cr = R.chr[2 * g], cim = -R.chr[2 * g + 1];
         const d2 v = {f * (ar * cr - ai * cim), f * (ar * cim + ai * cr)};
-        int q = 0;
-        while (q < n && cols[q] != (int32_t)l2) ++q;
-        if (q < n) {
-            vals[q] += v;
-        } else if (n < kHubReprMaxRow) {
-            cols[n] = (int32_t)l2;
-            vals[n] = v;
-            ++n;
-        }
+        row_merge(cols, vals, n, kHubReprMaxRow, 0, l2, v);    // no diagonal slot: the target is in another block
     }
-    for (int q = 1; q < n; ++q) {                      // ascending columns
-        const int32_t c = cols[q];
-        const d2 v = vals[q];
-        int p = q - 1;
-        while (p >= 0 && cols[p] > c) {
-            cols[p + 1] = cols[p];
-            vals[p + 1] = vals[p];
-            --p;
-        }
-        cols[p + 1] = c;
-        vals[p + 1] = v;
-    }
+    row_sort(cols, vals, n);
     return n;
 }
 
@@ -3777,10 +3406,7 @@ extern "C" int qbh_mf_hubbard_repr(qbh_csr **out, int n_sites, int n_up, int n_d
 
     // ---- device: representatives (for the remainder), tables, remainder CSR
     std::vector<void *> pool;
-    HubReprDev *d_R = nullptr;
-    uint64_t *d_tab = nullptr, *d_reps = nullptr, *d_flags = nullptr;
-    uint8_t *d_info = nullptr;
-    int64_t dim_dev = 0;
+    uint64_t *d_flags = nullptr;
     MfSec *ms = new MfSec();
     auto drop_tables = [&]() {
         for (void *q : {(void *)ms->blk, (void *)ms->hop, (void *)ms->item, (void *)ms->ucfg, (void *)ms->upell, (void *)ms->prank,
@@ -3788,9 +3414,10 @@ extern "C" int qbh_mf_hubbard_repr(qbh_csr **out, int n_sites, int n_up, int n_d
             if (q) (void)hipFree(q);
         delete ms;
     };
-    int rc = hubrepr_enumerate(R, tab, pool, &d_R, &d_tab, &d_reps, &d_info, &dim_dev, who);
-    if (rc == QBH_OK && dim_dev != dim) {
-        set_error("%s: block table (%lld rows) and enumeration (%lld representatives) disagree", who, (long long)dim, (long long)dim_dev);
+    SectorDev<HubReprDev> S;
+    int rc = sector_enumerate(R, tab, pool, S, who);
+    if (rc == QBH_OK && S.dim != dim) {
+        set_error("%s: block table (%lld rows) and enumeration (%lld representatives) disagree", who, (long long)dim, (long long)S.dim);
         rc = QBH_EHIP;
     }
     int32_t *d_cnt = nullptr, *d_flg = nullptr;
@@ -3828,7 +3455,7 @@ extern "C" int qbh_mf_hubbard_repr(qbh_csr **out, int n_sites, int n_up, int n_d
     if (rc == QBH_OK && e == hipSuccess) e = qbh::dev_alloc(&d_pos, (size_t)(dim + 1) * sizeof(int64_t));
     const int rgrid = (int)std::min<int64_t>((dim + 127) / 128, 256 * 16);
     if (rc == QBH_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_secrem_count, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, ms->blk, n_blocks, d_flags, d_cnt);
+        hipLaunchKernelGGL(k_secrem_count, dim3(rgrid), dim3(128), 0, 0, S.R, S.tab, S.reps, S.info, dim, ms->blk, n_blocks, d_flags, d_cnt);
         hipLaunchKernelGGL(k_secrem_flag, dim3(blas_grid(dim)), dim3(256), 0, 0, d_cnt, dim, d_flg);
         e = hipGetLastError();
     }
@@ -3843,7 +3470,7 @@ extern "C" int qbh_mf_hubbard_repr(qbh_csr **out, int n_sites, int n_up, int n_d
     if (rc == QBH_OK && e == hipSuccess) e = qbh::dev_alloc(&ms->rja, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t));
     if (rc == QBH_OK && e == hipSuccess) e = qbh::dev_alloc(&ms->rval, (size_t)std::max<int64_t>(nnz, 1) * sizeof(d2));
     if (rc == QBH_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_secrem_fill, dim3(rgrid), dim3(128), 0, 0, d_R, d_tab, d_reps, d_info, dim, ms->blk, n_blocks, d_flags, d_ia, d_pos,
+        hipLaunchKernelGGL(k_secrem_fill, dim3(rgrid), dim3(128), 0, 0, S.R, S.tab, S.reps, S.info, dim, ms->blk, n_blocks, d_flags, d_ia, d_pos,
                            ms->rrow, ms->ria, ms->rja, ms->rval);
         e = hipGetLastError();
     }
