@@ -788,6 +788,59 @@ int qbh_mopr_qudit_repr_dev(int n_sites, int d, int total_old, int dq, int n_tra
                             const double *chars_old, const qbh_z *coef /* [n_sites] */, const qbh_z *local /* [d*d] */,
                             const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out,
                             void *stream);
+/* The Kondo lattice model assembled on the device: conduction electrons plus a localized spin-1/2 on every site (the
+ * reference's add_orbital("electron") + add_orbital("spin-1/2") sites, examples/trans_absent/latt_chain/chain_Kondo.cc).
+ * n_sites in [1, 21].  A word is three n-bit fields  w = u | d << n | s << 2n : u, d the sites occupied by an up / down
+ * electron, s the sites whose local spin is DOWN.  The sector (n_elec, two_sz) holds the words with popcount(u) + popcount(d) =
+ * n_elec and (popcount(u) - popcount(d)) + (n - 2 popcount(s)) = two_sz: a union of particle-number blocks, one per
+ * popcount(s).  Basis: ascending w.  Fermion order as in qbh_gen_hubbard (all up operators, then all down, sites ascending);
+ * the local spins commute with everything.  The operator is
+ *     H = sum_t ( amp_up[t] c^dag_{i,up} c_{j,up} + amp_dn[t] c^dag_{i,dn} c_{j,dn} ),  (i, j) = term_sites[2t], term_sites[2t+1]
+ *       + U sum_i n_{i,up} n_{i,dn}
+ *       + sum_i ( kz[i] S^z_i s^z_i + kxy[i]/2 (S^+_i s^-_i + S^-_i s^+_i) )        s^+_i = c^dag_{i,up} c_{i,dn}: the electron's spin
+ *       + sum_b ( bz[b] S^z_i S^z_j + bxy[b]/2 (S^+_i S^-_j + S^-_i S^+_j) ),  (i, j) = sbond_sites[2b], sbond_sites[2b+1], i != j
+ * with terms on the same (i, j) summed.  The merged one-body part must be Hermitian (QBH_ENOTHERM).
+ * Output: FULL storage of global rows [row_begin, row_end) (row_end = -1: the whole sector), columns ascending, the diagonal
+ * always stored, zero amplitudes dropped elsewhere; *dim_out (may be NULL) receives the sector dimension.  The arrays are
+ * adopted as by qbh_csr_create_device, so the default value coding, row shards, qbh_csr_download and every solver apply.
+ * Codes: n_sites outside [1, 21], n_elec outside [0, 2 n_sites], n_elec + two_sz - n_sites odd, a term outside the lattice:
+ * QBH_EINVAL; an empty sector, dim >= 2^31, more than 160 entries in the worst row counted from the merged terms (one move
+ * per site pair and species, one flip per site with kxy != 0, one exchange per bond with bxy != 0, the diagonal): QBH_EUNSUPP.
+ * Every argument and term check runs before the device is looked for. */
+int qbh_gen_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz,
+                  int n_terms, const int32_t *term_sites /* [2*n_terms] */, const qbh_z *amp_up, const qbh_z *amp_dn, double U,
+                  const double *kz /* [n_sites] */, const double *kxy /* [n_sites] */,
+                  int n_sbonds, const int32_t *sbond_sites /* [2*n_sbonds] */, const double *bz, const double *bxy,
+                  int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
+/* Momentum sectors of qbh_gen_kondo: the same terms and checks; translations as in qbh_gen_heisenberg_repr (1 .. 64 of them,
+ * more: QBH_EUNSUPP), acting on the sites of all three fields, with the fermion sign of the two electron fields as in
+ * qbh_gen_hubbard_repr.  Every merged term must be carried onto an equal one by every translation, else QBH_EINVAL.
+ * Basis: ALL orbit representatives (the smallest word of the orbit), ascending; a representative whose signed character sum
+ * over its stabiliser vanishes stays as a decoupled row holding only the fake diagonal fake_pos + i/dim.  An entry is
+ * amplitude x fermion sign x sigma(g*) x conj(chi(g*)) x sqrt(|S_b|/|S_a|) as in qbh_gen_hubbard_repr.  Shards, row_cuts, value
+ * coding and adoption as in qbh_gen_heisenberg_repr(_cuts).  A sector of 2^40 words or more cannot be enumerated
+ * (QBH_EUNSUPP). */
+int qbh_gen_kondo_repr(qbh_csr **out, int n_sites, int n_elec, int two_sz,
+                       int n_terms, const int32_t *term_sites, const qbh_z *amp_up, const qbh_z *amp_dn, double U,
+                       const double *kz, const double *kxy,
+                       int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy,
+                       int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                       int shard, int n_shards, int64_t *dim_out, const qbh_opts *opts);
+/* ... with the caller's row cuts (see qbh_gen_heisenberg_repr_cuts) */
+int qbh_gen_kondo_repr_cuts(qbh_csr **out, int n_sites, int n_elec, int two_sz,
+                            int n_terms, const int32_t *term_sites, const qbh_z *amp_up, const qbh_z *amp_dn, double U,
+                            const double *kz, const double *kxy,
+                            int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy,
+                            int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                            int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts);
+/* moprXvec_repr (src/model.cc:1715-1846, diagonal branch) between two momentum sectors of qbh_gen_kondo_repr with the same
+ * (n_elec, two_sz) for O = sum_s ( coef_up[s] n_{s,up} + coef_dn[s] n_{s,dn} + coef_spin[s] S^z_s ): the density N_q and the
+ * S^z_q of the electrons and of the local spins.  Contract of qbh_mopr_diag_hubrepr_dev: the three coefficient sets transform
+ * with one character (checked, QBH_EINVAL), chars_new are the characters of the TARGET momentum, every target row is
+ * computed on its own (no atomics) and target rows of zero norm get 0. */
+int qbh_mopr_diag_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int n_trans, const int32_t *perms,
+                                 const double *chars_new, const qbh_z *coef_up, const qbh_z *coef_dn, const qbh_z *coef_spin,
+                                 const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_out);
 /* Measurement harness (SURVEY 7 hard-part 1): the operator of qbh_gen_heisenberg (kind 0) / qbh_gen_hubbard (kind 1), built with
  * complex128 values on one GPU, re-expressed ON THE DEVICE in the reference's own basis order and fermion convention, i.e.
  * exactly the matrix the unchanged host code assembles (src/model.cc:619-685) at sizes that code cannot reach: basis sorted

@@ -26,6 +26,7 @@
 #include "qbh_internal.hpp"
 #include "qbh_dict.hpp"
 #include "qbh_qudit.hpp"
+#include "qbh_kondo.hpp"
 
 namespace qbh {
 namespace {
@@ -1592,6 +1593,144 @@ __global__ __launch_bounds__(256) void k_qrepr_mopr(const QuditReprDev *Rold, co
     }
 }
 
+// ------------------------------------ Kondo lattice in translation-symmetric sectors (qbh_gen_kondo_repr) --
+// Words w = u | d << n | s << 2n as in qbh_gen_kondo (qbh_kondo.hpp): a translation permutes the sites of all three fields,
+// the two electron fields carry the fermion sign of hubrepr_parity, the local spins none.  The sector is a union of
+// particle-number blocks, so the cursor keeps the rank and seeks again where a block of s ends.  Row a as in
+// qbh_gen_hubbard_repr: O[a][b] = sum of <a|H|c> sigma(g*) conj(chi(g*)) sqrt(|S_b|/|S_a|), b = g* c.
+struct KondoReprDev {
+    KondoDev k;                           // shape, counting tables, terms
+    int n_trans, n_chunks;
+    double chr[2 * kReprMaxTrans];
+    double fake_pos;
+    int8_t perm[kReprMaxTrans * kKondoMaxSites];           // perm[g * n_sites + site]
+};
+template <> constexpr int max_row<KondoReprDev> = kKondoMaxRow;
+
+uint64_t sector_word_count(const KondoReprDev &R, std::vector<uint64_t> &) { return R.k.total; }
+
+struct KondoCursor { uint64_t u, d, s, ru, rd, r; };       // the three fields, the ranks of u and d in their block, the word's rank
+
+__device__ __forceinline__ KondoCursor sector_seek(const KondoReprDev &R, uint64_t r)
+{
+    KondoCursor c;
+    c.r = r;
+    kd_unrank(R.k, R.k.A, R.k.binom, r, &c.u, &c.d, &c.s, &c.ru, &c.rd);
+    return c;
+}
+__device__ __forceinline__ uint64_t sector_word(const KondoReprDev &R, const KondoCursor &c)
+{
+    return c.u | (c.d << R.k.n_sites) | (c.s << (2 * R.k.n_sites));
+}
+__device__ __forceinline__ void sector_step(const KondoReprDev &R, KondoCursor &c)
+{
+    if (c.r + 1 >= R.k.total) return;                      // the last word stays
+    ++c.r;
+    const int n = R.k.n_sites, nu = R.k.nu0 + __popcll(c.s);
+    if (++c.ru < R.k.binom[n * kKondoTab + nu]) {
+        c.u = next_same_popcount(c.u);
+    } else if (++c.rd < R.k.binom[n * kKondoTab + R.k.n_elec - nu]) {      // next down pattern, up patterns start over
+        c.ru = 0;
+        c.u = (1ULL << nu) - 1ULL;
+        c.d = next_same_popcount(c.d);
+    } else {
+        c = sector_seek(R, c.r);                           // the block of this s is done: the next s may lie in another block
+    }
+}
+__device__ __forceinline__ uint64_t sector_translate(const KondoReprDev &R, const uint64_t *tab, int g, uint64_t w)
+{
+    const int n = R.k.n_sites;
+    const uint64_t m = (1ULL << n) - 1ULL;
+    return repr_translate(tab, R.n_chunks, g, w & m) | (repr_translate(tab, R.n_chunks, g, (w >> n) & m) << n) |
+           (repr_translate(tab, R.n_chunks, g, w >> (2 * n)) << (2 * n));
+}
+// parity (0 / 1) of the permutation that sorts the images of the occupied sites of `occ` under translation g
+__device__ __forceinline__ int kondo_parity(const KondoReprDev &R, int g, uint64_t occ)
+{
+    const int8_t *p = R.perm + g * R.k.n_sites;
+    uint64_t seen = 0;
+    int par = 0;
+    while (occ) {
+        const int i = __ffsll((long long)occ) - 1;
+        occ &= occ - 1;
+        const int img = p[i];
+        par ^= __popcll(seen >> img) & 1;
+        seen |= 1ULL << img;
+    }
+    return par;
+}
+__device__ __forceinline__ int sector_parity(const KondoReprDev &R, int g, uint64_t w)
+{
+    const uint64_t m = (1ULL << R.k.n_sites) - 1ULL;
+    return kondo_parity(R, g, w & m) ^ kondo_parity(R, g, (w >> R.k.n_sites) & m);
+}
+
+// one row of the sector operator into (cols, vals), columns ascending, duplicates merged; returns its length
+__device__ int kondo_row(const KondoReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
+                         int32_t *cols, d2 *vals)
+{
+    const uint8_t ci = info[i];
+    if (ci & 0x80) return row_zero_norm(R.fake_pos, dim, i, cols, vals);
+    const double sa = (double)(ci & 0x7f);
+    const uint64_t a = reps[i];
+    const int nb = R.k.n_sites;
+    const uint64_t mlow = (1ULL << nb) - 1ULL;
+    int n = 1;
+    cols[0] = (int32_t)i;
+    d2 off = {0.0, 0.0};                  // what the moves add to the diagonal (a word that comes back to its own orbit)
+    const d2 dg0 = kd_row_terms(R.k, a & mlow, (a >> nb) & mlow, a >> (2 * nb), [&](uint64_t u2, uint64_t d2w, uint64_t s2, int code) {
+        const uint64_t c = u2 | (d2w << nb) | (s2 << (2 * nb));
+        int g = 0;
+        const uint64_t b = sector_canonical(R, tab, c, &g);
+        const int pt = g ? sector_parity(R, g, c) : 0;
+        const int64_t lo = sector_find(reps, dim, b);
+        const uint8_t cj = info[lo];
+        if (cj & 0x80) return;            // zero-norm target: dropped
+        const double f = (pt ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
+        const d2 h = kd_value(R.k, code);
+        const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];          // sigma(g*) conj(chi(g*)) sqrt(|S_b|/|S_a|)
+        const d2 v = {h.x * cr - h.y * cim, h.x * cim + h.y * cr};
+        row_add(cols, vals, n, kKondoMaxRow, i, lo, v, off);
+    });
+    return row_finish(cols, vals, n, dg0 + off);
+}
+
+__device__ __forceinline__ int sector_row(const KondoReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info,
+                                          int64_t dim, int64_t i, int32_t *cols, d2 *vals)
+{
+    return kondo_row(R, tab, reps, info, dim, i, cols, vals);
+}
+
+// moprXvec_repr, diagonal branch, for O = sum_s ( c_up[s] n_{s,up} + c_dn[s] n_{s,dn} + c_sp[s] S^z_s ) with every coefficient
+// set transforming with the same character: O |a, k> = z_a |a, k * eta>, z_a evaluated on the representative (see
+// k_hubrepr_apply_diag).  Representatives whose norm vanishes at the TARGET momentum get 0.
+struct KondoCoef { double up_re[kKondoMaxSites], up_im[kKondoMaxSites], dn_re[kKondoMaxSites], dn_im[kKondoMaxSites],
+                          sp_re[kKondoMaxSites], sp_im[kKondoMaxSites]; };
+
+__global__ __launch_bounds__(256) void k_kondo_apply_diag(int n_sites, const uint64_t *reps, const uint8_t *info_new, int64_t dim,
+                                                          KondoCoef cf, const d2 *x_old, d2 *y_new)
+{
+    const uint64_t mlow = (1ULL << n_sites) - 1ULL;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < dim; i += stride) {
+        d2 y = {0.0, 0.0};
+        if (!(info_new[i] & 0x80)) {
+            const uint64_t a = reps[i];
+            const uint64_t u = a & mlow, d = (a >> n_sites) & mlow, sp = a >> (2 * n_sites);
+            double zr = 0.0, zi = 0.0;
+            for (int s = 0; s < n_sites; ++s) {
+                const double nu = (double)((u >> s) & 1ULL), nd = (double)((d >> s) & 1ULL);
+                const double sz = ((sp >> s) & 1ULL) ? -0.5 : 0.5;
+                zr += nu * cf.up_re[s] + nd * cf.dn_re[s] + sz * cf.sp_re[s];
+                zi += nu * cf.up_im[s] + nd * cf.dn_im[s] + sz * cf.sp_im[s];
+            }
+            const d2 x = x_old[i];
+            y = d2{zr * x.x - zi * x.y, zr * x.y + zi * x.x};
+        }
+        y_new[i] = y;
+    }
+}
+
 // ------------------------------------ the enumeration and the row kernels every family shares --
 // The basis of a sector is ALL orbit representatives (the smallest word of each orbit) of the family's words, ascending; a
 // representative whose (signed) character sum over its stabiliser vanishes has zero norm at this momentum and stays in the
@@ -2357,6 +2496,148 @@ extern "C" int qbh_mopr_qudit_repr_dev(int n_sites, int d, int total_old, int dq
     QBH_HIP_WHO(who, hipStreamSynchronize(st));
     if (dim_old_out) *dim_old_out = So.dim;
     if (dim_new_out) *dim_new_out = Sn.dim;
+    return QBH_OK;
+}
+
+// ------------------------------ Kondo lattice: qbh_gen_kondo_repr(_cuts), qbh_mopr_diag_kondo_repr_dev --
+// the symmetry part of the sector on top of R.k (shape and terms already in place)
+static int kondo_symmetry(qbh::KondoReprDev &R, std::vector<uint64_t> &tab, int n_trans, const int32_t *perms, const double *chars,
+                          const char *who)
+{
+    using namespace qbh;
+    if (!perms || !chars || n_trans < 1) {
+        set_error("%s: invalid symmetry argument", who);
+        return QBH_EINVAL;
+    }
+    if (n_trans > kReprMaxTrans) {
+        set_error("%s: %d translations; at most %d are supported", who, n_trans, kReprMaxTrans);
+        return QBH_EUNSUPP;
+    }
+    R.n_trans = n_trans;
+    return sector_symmetry(R.k.n_sites, n_trans, perms, chars, who, nullptr, R.chr, R.perm, R.n_chunks, tab);
+}
+
+static int gen_kondo_repr_impl(qbh_csr **out, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites,
+                               const qbh_z *amp_up, const qbh_z *amp_dn, double U, const double *kz, const double *kxy, int n_sbonds,
+                               const int32_t *sbond_sites, const double *bz, const double *bxy, int n_trans, const int32_t *perms,
+                               const double *chars, double fake_pos, int shard, int n_shards, const int64_t *row_cuts,
+                               int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    const char *who = "qbh_gen_kondo_repr";
+    if (!out || n_shards < 1 || shard < 0 || shard >= n_shards) {
+        set_error("%s: invalid output or shard argument", who);
+        return QBH_EINVAL;
+    }
+    std::vector<KondoReprDev> rr(1);
+    KondoReprDev &R = rr[0];
+    memset(&R, 0, sizeof(R));
+    const int max_row = kondo_setup(who, n_sites, n_elec, two_sz, n_terms, term_sites, amp_up, amp_dn, U, kz, kxy, n_sbonds,
+                                    sbond_sites, bz, bxy, R.k);
+    if (max_row <= 0) return max_row;
+    std::vector<uint64_t> tab;
+    QBH_TRY(kondo_symmetry(R, tab, n_trans, perms, chars, who));
+    QBH_TRY(kondo_invariant(who, R.k, n_trans, perms));
+    int64_t nstates = 0;
+    std::vector<uint64_t> ctab;
+    QBH_TRY(sector_words(R, ctab, &nstates, who));       // every refusal comes before the device is looked for
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_HIP_WHO(who, hipSetDevice(opts->device));
+    R.fake_pos = fake_pos;
+    DevBufs bufs;
+    SectorDev<KondoReprDev> S;
+    QBH_TRY(sector_enumerate(R, tab, bufs.pool, S, who));
+    return assemble_sector_rows(who, bufs.pool, S.R, S.tab, S.reps, S.info, S.dim, shard, n_shards, row_cuts, opts, out, dim_out);
+}
+
+extern "C" int qbh_gen_kondo_repr(qbh_csr **out, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites,
+                                  const qbh_z *amp_up, const qbh_z *amp_dn, double U, const double *kz, const double *kxy,
+                                  int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy, int n_trans,
+                                  const int32_t *perms, const double *chars, double fake_pos, int shard, int n_shards,
+                                  int64_t *dim_out, const qbh_opts *opts)
+{
+    return gen_kondo_repr_impl(out, n_sites, n_elec, two_sz, n_terms, term_sites, amp_up, amp_dn, U, kz, kxy, n_sbonds, sbond_sites, bz,
+                               bxy, n_trans, perms, chars, fake_pos, shard, n_shards, nullptr, dim_out, opts);
+}
+
+extern "C" int qbh_gen_kondo_repr_cuts(qbh_csr **out, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites,
+                                       const qbh_z *amp_up, const qbh_z *amp_dn, double U, const double *kz, const double *kxy,
+                                       int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy, int n_trans,
+                                       const int32_t *perms, const double *chars, double fake_pos, int shard, int n_shards,
+                                       const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts)
+{
+    return gen_kondo_repr_impl(out, n_sites, n_elec, two_sz, n_terms, term_sites, amp_up, amp_dn, U, kz, kxy, n_sbonds, sbond_sites, bz,
+                               bxy, n_trans, perms, chars, fake_pos, shard, n_shards, row_cuts, dim_out, opts);
+}
+
+// N_q and the two S^z_q of a Kondo lattice between momentum sectors (see k_kondo_apply_diag), with the characters of the TARGET
+// momentum
+extern "C" int qbh_mopr_diag_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int n_trans, const int32_t *perms,
+                                            const double *chars_new, const qbh_z *coef_up, const qbh_z *coef_dn, const qbh_z *coef_spin,
+                                            const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_out)
+{
+    using namespace qbh;
+    const char *who = "qbh_mopr_diag_kondo_repr_dev";
+    if (!coef_up || !coef_dn || !coef_spin || !d_vec_old || !d_vec_new) {
+        set_error("%s: invalid argument", who);
+        return QBH_EINVAL;
+    }
+    std::vector<KondoReprDev> rr(1);
+    KondoReprDev &R = rr[0];
+    memset(&R, 0, sizeof(R));
+    QBH_TRY(kondo_shape(who, n_sites, n_elec, two_sz, R.k));
+    std::vector<uint64_t> tab;
+    QBH_TRY(kondo_symmetry(R, tab, n_trans, perms, chars_new, who));
+    // the three coefficient sets must transform with one character: c_{g(s)} = eta(g) c_s
+    const qbh_z *sets[3] = {coef_up, coef_dn, coef_spin};
+    for (int g = 0; g < n_trans; ++g) {
+        const int32_t *pg = perms + (size_t)g * n_sites;
+        std::complex<double> eta = 1.0;
+        double best = 0.0;
+        for (int q = 0; q < 3; ++q)
+            for (int s = 0; s < n_sites; ++s) {
+                const std::complex<double> c(sets[q][s].re, sets[q][s].im);
+                if (std::abs(c) > best) {                  // eta(g) from the largest coefficient
+                    best = std::abs(c);
+                    eta = std::complex<double>(sets[q][pg[s]].re, sets[q][pg[s]].im) / c;
+                }
+            }
+        for (int q = 0; q < 3; ++q)
+            for (int s = 0; s < n_sites; ++s) {
+                const std::complex<double> c(sets[q][s].re, sets[q][s].im), ci(sets[q][pg[s]].re, sets[q][pg[s]].im);
+                if (std::abs(ci - eta * c) > 1e-10 * std::max(1.0, best)) {
+                    set_error("%s: the coefficients do not transform with a character under translation %d", who, g);
+                    return QBH_EINVAL;
+                }
+            }
+    }
+    int64_t nstates = 0;
+    std::vector<uint64_t> ctab;
+    QBH_TRY(sector_words(R, ctab, &nstates, who));       // every refusal comes before the device is looked for
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    KondoCoef cf{};
+    for (int s = 0; s < n_sites; ++s) {
+        cf.up_re[s] = coef_up[s].re;
+        cf.up_im[s] = coef_up[s].im;
+        cf.dn_re[s] = coef_dn[s].re;
+        cf.dn_im[s] = coef_dn[s].im;
+        cf.sp_re[s] = coef_spin[s].re;
+        cf.sp_im[s] = coef_spin[s].im;
+    }
+    DevBufs bufs;
+    SectorDev<KondoReprDev> S;
+    QBH_TRY(sector_enumerate(R, tab, bufs.pool, S, who));
+    hipLaunchKernelGGL(k_kondo_apply_diag, dim3(blas_grid(S.dim)), dim3(256), 0, 0, n_sites, S.reps, S.info, S.dim, cf,
+                       reinterpret_cast<const d2 *>(d_vec_old), reinterpret_cast<d2 *>(d_vec_new));
+    QBH_HIP_WHO(who, hipGetLastError());
+    QBH_HIP_WHO(who, hipDeviceSynchronize());
+    if (dim_out) *dim_out = S.dim;
     return QBH_OK;
 }
 

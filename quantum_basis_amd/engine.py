@@ -355,6 +355,66 @@ class csr_mat:
         dg = 0.5 * U * n * (n - 1) - mu * n
         return cls.qudit_repr(n_sites, n_max + 1, n_bosons, perms, chars, pairs, [(s, dg) for s in range(n_sites)], **kw)
 
+    @staticmethod
+    def _kondo_args(n_sites, bonds, t, J_K, J_RKKY, terms):
+        from . import kondo as kd
+        T = terms if terms is not None else kd.terms(n_sites, bonds, t, J_K, J_RKKY)
+        hops, sb = list(T.hops), list(T.sbonds)
+        sites = np.ascontiguousarray(np.array([[a[0], a[1]] for a in hops], dtype=np.int32).reshape(-1, 2))
+        aup = np.ascontiguousarray(np.array([a[2] for a in hops], dtype=np.complex128))
+        adn = np.ascontiguousarray(np.array([a[3] for a in hops], dtype=np.complex128))
+        kz = np.ascontiguousarray(T.kz, dtype=np.float64)
+        kxy = np.ascontiguousarray(T.kxy, dtype=np.float64)
+        assert kz.size == n_sites and kxy.size == n_sites
+        ss = np.ascontiguousarray(np.array([[a[0], a[1]] for a in sb], dtype=np.int32).reshape(-1, 2))
+        bz = np.ascontiguousarray(np.array([a[2] for a in sb], dtype=np.float64))
+        bxy = np.ascontiguousarray(np.array([a[3] for a in sb], dtype=np.float64))
+        keep = (sites, aup, adn, kz, kxy, ss, bz, bxy)
+        return keep, (len(hops), _p(sites), _p(aup), _p(adn)), (_p(kz), _p(kxy), len(sb), _p(ss), _p(bz), _p(bxy))
+
+    @classmethod
+    def kondo(cls, n_sites, n_elec, two_sz, bonds, t=1.0, J_K=1.1, J_RKKY=0.0, U=0.0, rows=None, opts=None, terms=None):
+        """Kondo lattice model assembled on the device (qbh_gen_kondo; the reference's chain_Kondo.cc): n_elec conduction
+        electrons and a localized spin-1/2 on every site in the sector 2 S^z_total = two_sz.  Hops -t both ways on every
+        bond, J_K S_i . s_i on every site, J_RKKY S_i . S_j between local spins on every bond, U n_up n_dn.  terms =
+        kondo.Terms(hops, kz, kxy, sbonds) replaces all three lists (anisotropic couplings, complex hops, observables).
+        Basis: quantum_basis_amd.kondo.words(n_sites, n_elec, two_sz).  rows=(r0, r1): that row block only.
+
+        An observable needs no entry point of its own: <psi| S_i . s_i |psi> is
+            O = csr_mat.kondo(n, n_elec, two_sz, [], terms=kondo.local_singlet_terms(n, i))
+            O.spmv(psi.ptr, tmp.ptr); value = O.dotc(psi.ptr, tmp.ptr)
+        with psi, tmp DeviceVec: an operator with no hops, applied through the same SpMV as the Hamiltonian."""
+        _lib.require_gpu()
+        opts = opts if opts is not None else make_opts()
+        keep, hop, rest = cls._kondo_args(n_sites, bonds, t, J_K, J_RKKY, terms)
+        r0, r1 = (0, -1) if rows is None else rows
+        h = C.c_void_p()
+        dim = C.c_int64(0)
+        check(lib().qbh_gen_kondo(C.byref(h), n_sites, n_elec, two_sz, *hop, float(U), *rest, C.c_int64(r0), C.c_int64(r1),
+                                  C.byref(dim), C.byref(opts)), "qbh_gen_kondo")
+        return cls(0, None, None, None, opts=opts, _handle=h)
+
+    @classmethod
+    def kondo_repr(cls, n_sites, n_elec, two_sz, bonds, perms, chars, t=1.0, J_K=1.1, J_RKKY=0.0, U=0.0, fake_pos=100.0,
+                   shard=(0, 1), opts=None, row_cuts=None, terms=None):
+        """The operator of kondo in a momentum sector (qbh_gen_kondo_repr; the reference's
+        examples/trans_symmetric/latt_chain/chain_Kondo.cc): perms / chars / fake_pos / shard / row_cuts as in
+        heisenberg_repr.  The terms must be invariant under every translation."""
+        _lib.require_gpu()
+        opts = opts if opts is not None else make_opts()
+        keep, hop, rest = cls._kondo_args(n_sites, bonds, t, J_K, J_RKKY, terms)
+        p = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+        c = np.ascontiguousarray(np.asarray(chars, dtype=np.complex128))
+        assert p.shape == (len(c), n_sites)
+        cuts = None if row_cuts is None else np.ascontiguousarray(row_cuts, dtype=np.int64)      # see heisenberg_repr
+        assert cuts is None or cuts.size == int(shard[1]) + 1
+        h = C.c_void_p()
+        dim = C.c_int64(0)
+        check(lib().qbh_gen_kondo_repr_cuts(C.byref(h), n_sites, n_elec, two_sz, *hop, float(U), *rest, len(c), _p(p), _p(c),
+                                            fake_pos, int(shard[0]), int(shard[1]), _p(cuts) if cuts is not None else None,
+                                            C.byref(dim), C.byref(opts)), "qbh_gen_kondo_repr")
+        return cls(0, None, None, None, opts=opts, _handle=h)
+
     # ---- reference interface -------------------------------------------------------------
     def dimension(self):
         return self.dim
@@ -843,6 +903,22 @@ def moprXvec_diag_hubrepr(n_sites, n_up, n_dn, perms, chars_new, coef_up, coef_d
     dim = C.c_int64(0)
     check(lib().qbh_mopr_diag_hubrepr_dev(n_sites, n_up, n_dn, len(ch), _p(p), _p(ch), _p(cu), _p(cd), d_vec_old, d_vec_new,
                                           C.byref(dim)), "qbh_mopr_diag_hubrepr_dev")
+    return dim.value
+
+
+def moprXvec_diag_kondo_repr(n_sites, n_elec, two_sz, perms, chars_new, coef_up, coef_dn, coef_spin, d_vec_old, d_vec_new):
+    """moprXvec_repr for sum_s (coef_up[s] n_{s,up} + coef_dn[s] n_{s,dn} + coef_spin[s] S^z_s) between momentum sectors of
+    qbh_gen_kondo_repr (N_q and the S^z_q of the electrons and of the local spins); chars_new = characters of the target
+    momentum.  Returns the number of representatives."""
+    p = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+    ch = np.ascontiguousarray(np.asarray(chars_new, dtype=np.complex128))
+    cu = np.ascontiguousarray(coef_up, dtype=np.complex128)
+    cd = np.ascontiguousarray(coef_dn, dtype=np.complex128)
+    cs = np.ascontiguousarray(coef_spin, dtype=np.complex128)
+    assert p.shape == (len(ch), n_sites) and cu.size == n_sites and cd.size == n_sites and cs.size == n_sites
+    dim = C.c_int64(0)
+    check(lib().qbh_mopr_diag_kondo_repr_dev(n_sites, n_elec, two_sz, len(ch), _p(p), _p(ch), _p(cu), _p(cd), _p(cs), d_vec_old,
+                                             d_vec_new, C.byref(dim)), "qbh_mopr_diag_kondo_repr_dev")
     return dim.value
 
 

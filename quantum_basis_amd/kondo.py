@@ -1,0 +1,104 @@
+"""Basis and term lists of the Kondo lattice model (qbh_gen_kondo, qbh_gen_kondo_repr).  Pure numpy, no device.
+
+Every site carries a conduction-electron orbital and a localized spin-1/2.  A basis word is three n-bit fields
+
+    w = u | d << n | s << 2n        u, d: sites occupied by an up / down electron;  s: sites whose local spin is DOWN
+
+and the sector (n_elec, two_sz) holds the words with popcount(u) + popcount(d) = n_elec and
+(popcount(u) - popcount(d)) + (n - 2 popcount(s)) = two_sz, in ascending order of w.  popcount(s) = m fixes the electron
+numbers, so the sector is a union of blocks (n_up, n_dn, m): sector_blocks.
+
+The operator (include/qbhip.h, qbh_gen_kondo) is given by a Terms tuple:
+    hops    [(i, j, amp_up, amp_dn), ...]   amp * c+_i c_j per species (i == j: a number operator)
+    kz, kxy [n_sites] each                  kz S^z_i s^z_i + kxy/2 (S+_i s-_i + S-_i s+_i), s = the electron's spin on site i
+    sbonds  [(i, j, bz, bxy), ...]          bz S^z_i S^z_j + bxy/2 (S+_i S-_j + S-_i S+_j) between local spins
+and U sum_i n_up n_dn, passed separately.
+"""
+from collections import namedtuple
+from math import comb
+
+import numpy as np
+
+MAX_SITES = 21
+
+Terms = namedtuple("Terms", "hops kz kxy sbonds")
+
+
+def sector_blocks(n_sites, n_elec, two_sz):
+    """[(n_up, n_dn, m), ...] for every number m of down local spins that the sector admits, m ascending."""
+    twice_up0 = n_elec + two_sz - n_sites            # 2 n_up = n_elec + two_sz - n + 2 m
+    if twice_up0 % 2:
+        return []
+    out = []
+    for m in range(n_sites + 1):
+        n_up = twice_up0 // 2 + m
+        n_dn = n_elec - n_up
+        if 0 <= n_up <= n_sites and 0 <= n_dn <= n_sites:
+            out.append((n_up, n_dn, m))
+    return out
+
+
+def sector_dim(n_sites, n_elec, two_sz):
+    """Number of words of the sector (n = n_elec, two_sz = 0: the Franel numbers sum_m C(n, m)^3)."""
+    return sum(comb(n_sites, m) * comb(n_sites, n_up) * comb(n_sites, n_dn) for (n_up, n_dn, m) in sector_blocks(n_sites, n_elec, two_sz))
+
+
+def _patterns(n_sites):
+    """patterns[k] = the n-bit integers with k set bits, ascending"""
+    a = np.arange(1 << n_sites, dtype=np.uint64)
+    pc = np.zeros(a.size, dtype=np.int64)
+    for b in range(n_sites):
+        pc += ((a >> np.uint64(b)) & np.uint64(1)).astype(np.int64)
+    return [a[pc == k] for k in range(n_sites + 1)]
+
+
+def words(n_sites, n_elec, two_sz):
+    """The words of the sector, ascending (uint64): row i of csr_mat.kondo is words(...)[i]."""
+    assert 1 <= n_sites <= MAX_SITES
+    blocks = {m: (n_up, n_dn) for (n_up, n_dn, m) in sector_blocks(n_sites, n_elec, two_sz)}
+    pat = _patterns(n_sites)
+    n = np.uint64(n_sites)
+    out = []
+    for s in range(1 << n_sites):
+        m = bin(s).count("1")
+        if m not in blocks:
+            continue
+        n_up, n_dn = blocks[m]
+        ud = (pat[n_dn][:, None] << n) | pat[n_up][None, :]
+        out.append(ud.reshape(-1) | (np.uint64(s) << (n + n)))
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.uint64)
+
+
+def fields(w, n_sites):
+    """(u, d, s) of a word or an array of words"""
+    w = np.asarray(w, dtype=np.uint64)
+    m = np.uint64((1 << n_sites) - 1)
+    n = np.uint64(n_sites)
+    return w & m, (w >> n) & m, w >> (n + n)
+
+
+def hop_terms(bonds, t=1.0):
+    """-t (c+_i c_j + c+_j c_i) for both species on every bond (a bond listed twice counts twice)"""
+    out = []
+    for (i, j) in np.asarray(bonds, dtype=np.int64).reshape(-1, 2):
+        out.append((int(i), int(j), -t, -t))
+        out.append((int(j), int(i), -t, -t))
+    return out
+
+
+def exchange_terms(bonds, J):
+    """isotropic J S_i . S_j between the local spins on every bond"""
+    return [(int(i), int(j), J, J) for (i, j) in np.asarray(bonds, dtype=np.int64).reshape(-1, 2)]
+
+
+def terms(n_sites, bonds, t=1.0, J_K=1.1, J_RKKY=0.0):
+    """The Kondo lattice model of the reference's examples: hops -t both ways on every bond, J_K S_i . s_i on every site,
+    J_RKKY S_i . S_j between the local spins on every bond."""
+    return Terms(hop_terms(bonds, t), [J_K] * n_sites, [J_K] * n_sites, exchange_terms(bonds, J_RKKY) if J_RKKY != 0.0 else [])
+
+
+def local_singlet_terms(n_sites, site):
+    """Terms of the observable S_i . s_i on one site (no hops): apply it with spmv and take dotc for <S_i . s_i>."""
+    k = [0.0] * n_sites
+    k[site] = 1.0
+    return Terms([], k, list(k), [])
