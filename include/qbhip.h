@@ -746,6 +746,21 @@ int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total,
                   int n_pairs, const int32_t *pair_sites /* [2*n_pairs] */, const qbh_z *pair_mat /* [n_pairs * d^4] */,
                   int n_single, const int32_t *single_sites /* [n_single] */, const double *single_diag /* [n_single * d] */,
                   int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
+/* The operator of qbh_gen_qudit applied without a stored matrix: terms, basis order, argument meaning, error codes and the
+ * order of the checks are those of qbh_gen_qudit (every argument and term check runs before the device is looked for).  Each
+ * row is unranked from a counting table of at most 33 KB, and a neighbour's column is the row plus a rank difference over the
+ * sites between the pair; rows, ranks and differences are 64-bit, nothing is staged per row and no column is stored, so the
+ * limits dim < 2^31 and 240 entries per row of qbh_gen_qudit do not apply (d in [2, 8], n_sites * ceil(log2 d) <= 64 and at
+ * most 1024 distinct site pairs remain; dim < 2^62).  The term tables are kept once per distinct merged pair matrix.
+ * The handle behaves like that of qbh_mf_heisenberg: SpMV with its fused epilogue and reductions, qbh_multmv(2), every
+ * solver, qbh_csr_set_comm on row shards [row_begin, row_end); qbh_csr_download returns QBH_EUNSUPP.  qbh_csr_get_info
+ * reports kernel = QBH_KERNEL_MATRIX_FREE, nnz = the entries qbh_gen_qudit would store for these rows (counted on the
+ * device) and bytes_matrix = the tables held.  The real fast path and the packed-real drivers apply when every merged pair
+ * matrix is real; a complex operator (Peierls phases) runs on complex vectors only. */
+int qbh_mf_qudit(qbh_csr **out, int n_sites, int d, int total,
+                 int n_pairs, const int32_t *pair_sites /* [2*n_pairs] */, const qbh_z *pair_mat /* [n_pairs * d^4] */,
+                 int n_single, const int32_t *single_sites /* [n_single] */, const double *single_diag /* [n_single * d] */,
+                 int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
 /* moprXvec_full (src/model.cc:1468-1538) for the sectors of qbh_gen_qudit: vec_new = sum_s coef[s] O_s vec_old with the
  * same local d x d matrix O on every site, local[l' d + l] = <l'|O|l>, nonzero only where l' = l + dq (else QBH_EINVAL).
  * vec_old lives in the sector total_old, vec_new in total_old + dq (*dim_new_out, may be NULL, its dimension); both are

@@ -722,6 +722,10 @@ extern "C" void qbh_csr_destroy(qbh_csr *A)
         (void)hipFree(A->mfh.offd);
         (void)hipFree(A->mfh.diag);
     }
+    if (A->kind == 4)
+        for (void *q : {(void *)A->mfq.cum, (void *)A->mfq.pairs, (void *)A->mfq.nrow, (void *)A->mfq.slot, (void *)A->mfq.sdiag,
+                        (void *)A->mfq.pdiag, (void *)A->mfq.eout, (void *)A->mfq.eval})
+            (void)hipFree(q);
     if (A->ev2) (void)hipEventDestroy(A->ev2);
     if (A->ev3) (void)hipEventDestroy(A->ev3);
     for (auto &o : A->ev_old)
@@ -916,8 +920,9 @@ int qbh::adopt_mf_sector(qbh_csr **out, qbh::MfSec *host_tables, qbh::MfSec *dev
     return QBH_OK;
 }
 
-int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
-                          int64_t nnz_equiv, const qbh_opts *opts)
+// what the row-parallel matrix-free forms share: a handle with workspace and no arrays (the caller sets kind and its tables)
+static int adopt_mf_rows(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t row_offset, int64_t nnz_equiv, bool values_real,
+                         const qbh_opts *opts)
 {
     qbh_csr *A = nullptr;
     QBH_TRY(new_handle(&A, opts));
@@ -926,7 +931,7 @@ int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows,
     A->row_offset = row_offset;
     A->nnz = A->nnz_total = nnz_equiv;         // what the CSR of the same operator would hold (for the byte accounting)
     A->kernel = QBH_KERNEL_ROWS;
-    A->values_real = true;                     // t and U are real
+    A->values_real = values_real;
     A->n_blocks = (nrows + qbh::kBlock - 1) / qbh::kBlock;
     A->grid = (int)std::min<int64_t>(A->n_blocks, 256 * 8);
     auto fail = [&](int code) {
@@ -944,43 +949,35 @@ int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows,
     if (qbh::dev_alloc(&A->d_partials, nparts * 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
     A->stats = qbh_stats{};
     A->stats.ms_spmv_min = std::numeric_limits<double>::infinity();
-    A->kind = 1;                // from here on the handle owns the tables (on any failure above the caller still does)
-    A->mf = t;
     *out = A;
+    return QBH_OK;
+}
+
+// In the three below the handle owns the tables once the call succeeds; on failure the caller still does.
+int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
+                          int64_t nnz_equiv, const qbh_opts *opts)
+{
+    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, true, opts));      // t and U are real
+    (*out)->kind = 1;
+    (*out)->mf = t;
     return QBH_OK;
 }
 
 int qbh::adopt_mf_heis(qbh_csr **out, const qbh::MfHeis &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                           int64_t nnz_equiv, const qbh_opts *opts)
 {
-    qbh_csr *A = nullptr;
-    QBH_TRY(new_handle(&A, opts));
-    A->nrows = nrows;
-    A->ncols = ncols;
-    A->row_offset = row_offset;
-    A->nnz = A->nnz_total = nnz_equiv;         // what the CSR of the same operator would hold (for the byte accounting)
-    A->kernel = QBH_KERNEL_ROWS;
-    A->values_real = true;                     // J is real
-    A->n_blocks = (nrows + qbh::kBlock - 1) / qbh::kBlock;
-    A->grid = (int)std::min<int64_t>(A->n_blocks, 256 * 8);
-    auto fail = [&](int code) {
-        qbh_csr_destroy(A);
-        return code;
-    };
-    if (qbh::dev_alloc(&A->d_scal, 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
-    if (hipHostMalloc(&A->h_scal, 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
-    if (qbh::dev_alloc(&A->d_flag, sizeof(int)) != hipSuccess) return fail(QBH_ENOMEM);
-    if (hipMemsetAsync(A->d_flag, 0, sizeof(int), A->stream) != hipSuccess) return fail(QBH_EHIP);      // on the handle's stream: the null stream is not ordered with it
-    if (hipEventCreate(&A->ev0) != hipSuccess || hipEventCreate(&A->ev1) != hipSuccess ||
-        hipEventCreate(&A->ev2) != hipSuccess || hipEventCreate(&A->ev3) != hipSuccess)
-        return fail(QBH_EHIP);
-    const size_t nparts = (size_t)std::max(A->grid, qbh::kMaxRedBlocks);
-    if (qbh::dev_alloc(&A->d_partials, nparts * 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
-    A->stats = qbh_stats{};
-    A->stats.ms_spmv_min = std::numeric_limits<double>::infinity();
-    A->kind = 2;                // from here on the handle owns the tables (on any failure above the caller still does)
-    A->mfh = t;
-    *out = A;
+    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, true, opts));      // J is real
+    (*out)->kind = 2;
+    (*out)->mfh = t;
+    return QBH_OK;
+}
+
+int qbh::adopt_mf_qudit(qbh_csr **out, const qbh::MfQudit &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
+                        int64_t nnz_equiv, const qbh_opts *opts)
+{
+    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
+    (*out)->kind = 4;
+    (*out)->mfq = t;
     return QBH_OK;
 }
 
@@ -1001,6 +998,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
     if (A->kind == 2)
         info->bytes_matrix = ((int64_t)(A->mfh.n_sites + 1) * (A->mfh.n_dn + 1) + (int64_t)A->mfh.n_chunks * (A->mfh.n_dn + 1) * 64 +
                               3 * (int64_t)A->mfh.n_bonds) * 8;
+    if (A->kind == 4) info->bytes_matrix = A->mfq.bytes;
     if (A->kind == 3 && A->mfsec) {
         const qbh::MfSec &m = *A->mfsec;
         info->bytes_matrix = m.n_blocks * (int64_t)sizeof(qbh::MfSecBlock) + m.n_items * 8 + m.n_rrows * 12 + m.rnnz * 20 +

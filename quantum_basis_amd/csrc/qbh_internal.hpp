@@ -622,6 +622,39 @@ struct MfHeisArgs {
 int launch_mf_heis(const MfHeisArgs &a, hipStream_t s, int *nparts_out);
 int adopt_mf_heis(qbh_csr **out, const MfHeis &t, int64_t nrows, int64_t ncols, int64_t row_offset, int64_t nnz_equiv,
                   const qbh_opts *opts);
+// matrix-free operator on sites with d levels and one conserved charge, basis and terms of qbh_gen_qudit (qbh_qudit.hip):
+// unrank the row from cum[s][q], take every pair's levels from the packed word, column = row + qd_move_delta.  The merged
+// pair matrices are kept once per DISTINCT matrix (class); a pair with at most m off-diagonal entries in a row of its class
+// takes m slots (at least one), slot k of a class holding entry k of every row `in` (amplitude 0 where the row has fewer).
+struct MfQudit {
+    int       n_sites = 0, d = 0, bits = 0, total = 0, tw = 0;
+    int       n_pairs = 0, n_cls = 0, n_ent = 0;
+    int       n_slots = 0;         // padded to a multiple of 8 with slots that point at the zero block ent[0 .. d^2)
+    int       tables_lds = 0;      // 1: pdiag / eout / eval fit LDS beside cum; 0: they are read from global memory
+    int       has_single = 0;
+    uint64_t *cum = nullptr;       // [n_sites * tw]
+    int32_t  *pairs = nullptr;     // [n_pairs] i | j << 8 | class << 16, i < j (the count pass)
+    int32_t  *nrow = nullptr;      // [n_cls * d^2] off-diagonal nonzeros of row `in` of a class (the count pass)
+    int32_t  *slot = nullptr;      // [2 * n_slots] (i | j << 8 | class << 16 | first slot of the pair << 30, entry base)
+    double   *sdiag = nullptr;     // [n_sites * d]
+    double   *pdiag = nullptr;     // [n_cls * d^2]
+    int32_t  *eout = nullptr;      // [n_ent] the column's level at site j
+    d2       *eval = nullptr;      // [n_ent] <in|M|out>, entry base + in
+    int64_t   bytes = 0;           // of the tables above
+};
+struct MfQuditArgs {
+    MfQudit t;
+    int64_t row_begin, nrows;
+    const d2 *xg, *xl;
+    const double *xr;
+    d2 *y;
+    double alpha, beta, gamma;
+    double *partials;
+    double *y_re;
+};
+int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out);
+int adopt_mf_qudit(qbh_csr **out, const MfQudit &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
+                   int64_t nnz_equiv, const qbh_opts *opts);
 // adopt a matrix-free operator (tables already in HBM) behind a qbh_csr handle (qbh_api.cpp)
 int adopt_mf_hubbard(qbh_csr **out, const MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                      int64_t nnz_equiv, const qbh_opts *opts);
@@ -768,11 +801,12 @@ struct qbh_csr {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     // matrix-free operator (kind 1) instead of CSR arrays (kind 0)
-    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector
-    qbh::MfSec *mfsec = nullptr;     // kind 3: block tables + compact remainder (host copy of the descriptor, device arrays)
+    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites
+    qbh::MfSec *mfsec = nullptr;    // kind 3: block tables + compact remainder (host copy of the descriptor, device arrays)
     qbh::MfSec *d_mfsec = nullptr;   // its device copy (kernel argument)
     qbh::MfHubbard mf;
     qbh::MfHeis    mfh;
+    qbh::MfQudit   mfq;
 
     // split shard: the arrays above hold the locally-owned columns, `rem` the remote ones
     bool     has_rem = false;

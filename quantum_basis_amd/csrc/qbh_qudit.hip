@@ -1,5 +1,6 @@
-// qbh_qudit.hip -- device assembly for sites with d local levels and one conserved charge (spin S, bosons with at most
-// n_max per site): qbh_gen_qudit and the operator x vector step qbh_mopr_qudit_dev.
+// qbh_qudit.hip -- sites with d local levels and one conserved charge (spin S, bosons with at most n_max per site): device
+// assembly (qbh_gen_qudit), the same operator applied without a stored matrix (qbh_mf_qudit, k_mf_qudit) and the operator x
+// vector step qbh_mopr_qudit_dev.
 //
 // Basis (documented in include/qbhip.h): site s holds a level l_s in [0, d), the charge of a word is sum_s l_s, and the
 // words of one charge are ranked in ascending order of sum_s l_s d^s (site n-1 most significant).  With
@@ -15,6 +16,7 @@
 #include <complex>
 #include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "qbh_internal.hpp"
@@ -196,6 +198,169 @@ __global__ __launch_bounds__(256) void k_qudit_mopr(int n_sites, int d, int bits
     }
 }
 
+// ------------------------------------------------------------------------------------ matrix-free apply (kind 4) --
+// y <- alpha H x + beta y + gamma x without a stored matrix.  One lane per row, grid-stride over a resident grid.  LDS holds
+// cum, the single-site diagonal and the slot list; the class tables (pdiag, eout, eval) too when they fit (TLDS), else
+// they are read from global memory (read-only, cached: every lane of every workgroup reads the same few hundred KB).
+// A slot is uniform over the lanes: (pair, k) = entry k of the row `in` of the pair's class, amplitude 0 where that row
+// has fewer entries -- then the lane gathers x[row] with weight 0, as k_mf_heis does for a bond that does not flip.
+// Eight slots form a batch: indices and amplitudes first, then the eight x loads, then the FMAs.
+constexpr int kMfQuditBlock = 512;
+constexpr size_t kMfQuditLdsCap = (size_t)150 * 1024;        // the budget of launch_mf_heis
+
+__device__ __forceinline__ double qd_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// LDS layout, 16-byte items first: eval[n_ent] (TLDS) | cum | sdiag | pdiag (TLDS) | slot | eout (TLDS)
+inline size_t mf_qudit_lds_bytes(const MfQudit &t, bool tables)
+{
+    const size_t d2n = (size_t)t.d * t.d;
+    size_t b = ((size_t)t.n_sites * t.tw + (size_t)t.n_sites * t.d) * 8 + (size_t)t.n_slots * 8;
+    if (tables) b += (size_t)t.n_ent * 20 + (size_t)t.n_cls * d2n * 8;
+    return b;
+}
+
+template <bool REALX, bool TLDS>
+__global__ __launch_bounds__(kMfQuditBlock) void k_mf_qudit(MfQuditArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t qd_lds[];
+    __shared__ double red[3 * (kMfQuditBlock / 64)];
+    const MfQudit &t = a.t;
+    const int tid = threadIdx.x;
+    const int d = t.d, bits = t.bits, tw = t.tw, d2n = d * d;
+    const int ncum = t.n_sites * tw, nsd = t.n_sites * d, npd = t.n_cls * d2n;
+    d2 *l_eval = reinterpret_cast<d2 *>(qd_lds);
+    uint64_t *cum = qd_lds + (TLDS ? 2 * (size_t)t.n_ent : 0);
+    double *sdiag = reinterpret_cast<double *>(cum + ncum);
+    double *l_pdiag = sdiag + nsd;
+    int32_t *slot = reinterpret_cast<int32_t *>(l_pdiag + (TLDS ? npd : 0));
+    int32_t *l_eout = slot + 2 * t.n_slots;
+    for (int k = tid; k < ncum; k += kMfQuditBlock) cum[k] = t.cum[k];
+    for (int k = tid; k < nsd; k += kMfQuditBlock) sdiag[k] = t.sdiag[k];
+    for (int k = tid; k < 2 * t.n_slots; k += kMfQuditBlock) slot[k] = t.slot[k];
+    if (TLDS) {
+        for (int k = tid; k < npd; k += kMfQuditBlock) l_pdiag[k] = t.pdiag[k];
+        for (int k = tid; k < t.n_ent; k += kMfQuditBlock) {
+            l_eval[k] = t.eval[k];
+            l_eout[k] = t.eout[k];
+        }
+    }
+    __syncthreads();
+    const double *pdiag = TLDS ? l_pdiag : t.pdiag;
+    const int32_t *eout = TLDS ? l_eout : t.eout;
+    const d2 *eval = TLDS ? l_eval : t.eval;
+    double acc[3] = {0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kMfQuditBlock;
+    for (int64_t lrow = (int64_t)blockIdx.x * kMfQuditBlock + tid; lrow < a.nrows; lrow += stride) {
+        const int64_t grow = a.row_begin + lrow;
+        const uint64_t w = qd_unrank(cum, t.n_sites, d, bits, tw, t.total, (uint64_t)grow);
+        double dg = 0.0;
+        if (t.has_single)
+            for (int s = 0; s < t.n_sites; ++s) dg += sdiag[s * d + qd_level(w, bits, s)];
+        d2 sum = {0.0, 0.0};
+        for (int b0 = 0; b0 < t.n_slots; b0 += 8) {
+            long long idx[8];
+            d2 amp[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int sw = slot[2 * (b0 + j)], base = slot[2 * (b0 + j) + 1];
+                const int si = sw & 0xff, sj = (sw >> 8) & 0xff;
+                const int lj = qd_level(w, bits, sj);
+                const int in = qd_level(w, bits, si) * d + lj;
+                if (sw & (1 << 30)) dg += pdiag[((sw >> 16) & 0x3ff) * d2n + in];
+                d2 v = {0.0, 0.0};
+                if (REALX) v.x = eval[base + in].x;
+                else       v = eval[base + in];
+                long long q = grow;
+                if (v.x != 0.0 || v.y != 0.0)
+                    q = (long long)((uint64_t)grow +
+                                    qd_move_delta(cum, tw, bits, w, si, sj, qd_charge(w, bits, sj), lj, 0, eout[base + in]));
+                amp[j] = v;
+                idx[j] = q;
+            }
+            if (REALX) {
+                double xv[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xv[j] = a.xr[idx[j]];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sum.x += amp[j].x * xv[j];
+            } else {
+                d2 xv[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xv[j] = a.xg[idx[j]];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    sum.x += amp[j].x * xv[j].x - amp[j].y * xv[j].y;
+                    sum.y += amp[j].x * xv[j].y + amp[j].y * xv[j].x;
+                }
+            }
+        }
+        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
+        if (a.y_re != nullptr) {
+            if (a.beta != 0.0) yo.x = a.y_re[lrow];
+            xi.x = a.xr[grow];
+        } else {
+            if (a.beta != 0.0) yo = a.y[lrow];
+            if (REALX) xi.x = a.xr[grow];
+            else       xi = a.xg[grow];
+        }
+        sum += dg * xi;
+        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
+        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
+        else                   a.y[lrow] = yn;
+        acc[0] += xi.x * yn.x + xi.y * yn.y;
+        acc[1] += xi.x * yn.y - xi.y * yn.x;
+        acc[2] += yn.x * yn.x + yn.y * yn.y;
+    }
+    if (a.partials != nullptr) {
+        const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = qd_wave_sum(acc[c]);
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) red[c * (kMfQuditBlock / 64) + wave] = acc[c];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int c = 0; c < 3; ++c) {
+                double v = 0.0;
+                for (int w2 = 0; w2 < kMfQuditBlock / 64; ++w2) v += red[c * (kMfQuditBlock / 64) + w2];
+                a.partials[(size_t)blockIdx.x * 3 + c] = v;
+            }
+        }
+    }
+}
+
+// entries a stored CSR of rows [row_begin, row_end) would hold (the diagonal always, exact zeros dropped): one sum per workgroup
+__global__ __launch_bounds__(256) void k_mf_qudit_count(MfQudit t, int64_t row_begin, int64_t row_end, unsigned long long *part)
+{
+    extern __shared__ uint64_t qd_lds[];
+    __shared__ unsigned long long red[256];
+    qd_stage_table(qd_lds, t.cum, t.n_sites * t.tw, 256);
+    const int d2n = t.d * t.d;
+    unsigned long long c = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t row = row_begin + (int64_t)blockIdx.x * 256 + threadIdx.x; row < row_end; row += stride) {
+        const uint64_t w = qd_unrank(qd_lds, t.n_sites, t.d, t.bits, t.tw, t.total, (uint64_t)row);
+        c += 1;
+        for (int p = 0; p < t.n_pairs; ++p) {
+            const int ij = t.pairs[p];
+            c += t.nrow[(ij >> 16) * d2n + qd_level(w, t.bits, ij & 0xff) * t.d + qd_level(w, t.bits, (ij >> 8) & 0xff)];
+        }
+    }
+    red[threadIdx.x] = c;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
 // ------------------------------------------------------------------------------------------------------- host side --
 struct HipFree {
     std::vector<void *> p;
@@ -303,6 +468,37 @@ int qudit_merge_terms(const char *who, int n_sites, int d, int n_pairs, const in
         }
         max_row += worst;
     }
+    return QBH_OK;
+}
+
+int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out)
+{
+    static int ncu = 0;
+    if (ncu == 0) {
+        hipDeviceProp_t prop;
+        int dev = 0;
+        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                  ? prop.multiProcessorCount : 256;
+    }
+    const bool tl = a.t.tables_lds != 0;
+    const size_t lds = mf_qudit_lds_bytes(a.t, tl);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ((size_t)158 * 1024) / (lds + 1024)));
+    const int64_t nblk = (a.nrows + kMfQuditBlock - 1) / kMfQuditBlock;
+    const int g = (int)std::min<int64_t>(nblk, (int64_t)ncu * per_cu);
+#define QBH_QUDIT_LAUNCH(RX, TL)                                                                                                   \
+    do {                                                                                                                          \
+        QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_qudit<RX, TL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (int)lds));                                                                                   \
+        hipLaunchKernelGGL((k_mf_qudit<RX, TL>), dim3(g), dim3(kMfQuditBlock), lds, s, a);                                         \
+    } while (0)
+    if (a.xr != nullptr) {
+        if (tl) QBH_QUDIT_LAUNCH(true, true); else QBH_QUDIT_LAUNCH(true, false);
+    } else {
+        if (tl) QBH_QUDIT_LAUNCH(false, true); else QBH_QUDIT_LAUNCH(false, false);
+    }
+#undef QBH_QUDIT_LAUNCH
+    QBH_HIP(hipGetLastError());
+    if (nparts_out) *nparts_out = g;
     return QBH_OK;
 }
 
@@ -420,6 +616,137 @@ extern "C" int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total, int n
     qbh_opts og;
     opts_generated(opts, &og);
     return qbh_csr_create_device(out, nrows, dim, row_begin, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
+}
+
+extern "C" int qbh_mf_qudit(qbh_csr **out, int n_sites, int d, int total, int n_pairs, const int32_t *pair_sites,
+                            const qbh_z *pair_mat, int n_single, const int32_t *single_sites, const double *single_diag,
+                            int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    static const char *who = "qbh_mf_qudit";
+    if (!out) {
+        set_error("%s: out is NULL", who);
+        return QBH_EINVAL;
+    }
+    QBH_TRY(qudit_check_shape(who, n_sites, d));
+    if (total < 0 || total > n_sites * (d - 1) || n_pairs < 0 || n_single < 0 || (n_pairs > 0 && (!pair_sites || !pair_mat)) ||
+        (n_single > 0 && (!single_sites || !single_diag))) {
+        set_error("%s: invalid charge %d (0 .. %d) or term arrays", who, total, n_sites * (d - 1));
+        return QBH_EINVAL;
+    }
+    QuditTerms T;
+    QBH_TRY(qudit_merge_terms(who, n_sites, d, n_pairs, pair_sites, pair_mat, n_single, single_sites, single_diag, T));
+    const int tw = total + 1;
+    std::vector<uint64_t> cum, dims;
+    qudit_table(n_sites, d, tw, cum, dims);
+    const uint64_t dim_u = dims[(size_t)total];
+    if (dim_out) *dim_out = (int64_t)std::min<uint64_t>(dim_u, (uint64_t)INT64_MAX);
+    if (dim_u >= (1ULL << 62)) {
+        set_error("%s: dim %llu exceeds 2^62", who, (unsigned long long)dim_u);
+        return QBH_EUNSUPP;
+    }
+    const int64_t dim = (int64_t)dim_u;
+    if (row_end < 0) row_end = dim;
+    if (row_begin < 0 || row_begin >= row_end || row_end > dim) {
+        set_error("%s: bad row range [%lld, %lld) of %lld", who, (long long)row_begin, (long long)row_end, (long long)dim);
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_QHIP(who, hipSetDevice(opts->device));
+
+    // classes: the distinct merged pair matrices (compared bit for bit), each with its tables once
+    const int d2n = d * d, np = (int)T.pm.size();
+    std::map<std::string, int> cls_of;
+    std::vector<int> cls(np), rep, maxk, base;                   // per pair | per class: first pair, longest row, entry base
+    {
+        int p = 0;
+        for (const auto &kv : T.pm) {
+            const std::string key(reinterpret_cast<const char *>(kv.second.data()), kv.second.size() * sizeof(kv.second[0]));
+            const auto it = cls_of.emplace(key, (int)rep.size());
+            if (it.second) rep.push_back(p);
+            cls[p++] = it.first->second;
+        }
+    }
+    const int n_cls = (int)rep.size();
+    std::vector<int32_t> nrow((size_t)n_cls * d2n), eout((size_t)d2n, 0);
+    std::vector<double> pdiag((size_t)n_cls * d2n);
+    std::vector<d2> eval((size_t)d2n, d2{0.0, 0.0});             // entries [0, d^2): the zero block of the padding slots
+    bool values_real = true;
+    for (int c = 0; c < n_cls; ++c) {
+        const int p = rep[(size_t)c];
+        int mk = 0;
+        for (int in = 0; in < d2n; ++in) {
+            nrow[(size_t)c * d2n + in] = T.eoff[(size_t)p * d2n + in + 1] - T.eoff[(size_t)p * d2n + in];
+            pdiag[(size_t)c * d2n + in] = T.pdiag[(size_t)p * d2n + in];
+            mk = std::max(mk, (int)nrow[(size_t)c * d2n + in]);
+        }
+        maxk.push_back(mk);
+        base.push_back((int)eval.size());
+        eout.resize(eval.size() + (size_t)mk * d2n, 0);
+        eval.resize(eval.size() + (size_t)mk * d2n, d2{0.0, 0.0});
+        for (int in = 0; in < d2n; ++in)
+            for (int k = 0; k < nrow[(size_t)c * d2n + in]; ++k) {
+                const int e = T.eoff[(size_t)p * d2n + in] + k;
+                eout[(size_t)base[(size_t)c] + (size_t)k * d2n + in] = T.eout[(size_t)e] >> 8;
+                eval[(size_t)base[(size_t)c] + (size_t)k * d2n + in] = T.eval[(size_t)e];
+                if (T.eval[(size_t)e].y != 0.0) values_real = false;
+            }
+    }
+    std::vector<int32_t> pairs((size_t)np), slot;
+    for (int p = 0; p < np; ++p) {
+        const int c = cls[(size_t)p];
+        pairs[(size_t)p] = T.pair_ij[(size_t)p] | (c << 16);
+        for (int k = 0; k < std::max(1, maxk[(size_t)c]); ++k) {
+            slot.push_back(pairs[(size_t)p] | (k == 0 ? 1 << 30 : 0));
+            slot.push_back(maxk[(size_t)c] == 0 ? 0 : base[(size_t)c] + k * d2n);
+        }
+    }
+    while (slot.size() % 16) slot.push_back(0);
+
+    MfQudit t;
+    t.n_sites = n_sites;
+    t.d = d;
+    t.bits = bits_per_level(d);
+    t.total = total;
+    t.tw = tw;
+    t.n_pairs = np;
+    t.n_cls = n_cls;
+    t.n_ent = (int)eval.size();
+    t.n_slots = (int)(slot.size() / 2);
+    for (double v : T.sdiag)
+        if (v != 0.0) t.has_single = 1;
+    t.tables_lds = mf_qudit_lds_bytes(t, true) <= kMfQuditLdsCap ? 1 : 0;
+    t.bytes = (int64_t)(cum.size() * 8 + pairs.size() * 4 + nrow.size() * 4 + slot.size() * 4 + T.sdiag.size() * 8 + pdiag.size() * 8 +
+                        eout.size() * 4 + eval.size() * 16);
+    HipFree pool;
+    QBH_QHIP(who, up(pool, &t.cum, cum));
+    QBH_QHIP(who, up(pool, &t.pairs, pairs));
+    QBH_QHIP(who, up(pool, &t.nrow, nrow));
+    QBH_QHIP(who, up(pool, &t.slot, slot));
+    QBH_QHIP(who, up(pool, &t.sdiag, T.sdiag));
+    QBH_QHIP(who, up(pool, &t.pdiag, pdiag));
+    QBH_QHIP(who, up(pool, &t.eout, eout));
+    QBH_QHIP(who, up(pool, &t.eval, eval));
+
+    const int64_t nrows = row_end - row_begin;
+    const int cgrid = blas_grid(nrows);
+    unsigned long long *d_part = nullptr;
+    QBH_QHIP(who, qbh::dev_alloc(&d_part, (size_t)cgrid * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_mf_qudit_count, dim3(cgrid), dim3(256), cum.size() * sizeof(uint64_t), 0, t, row_begin, row_end, d_part);
+    std::vector<unsigned long long> part((size_t)cgrid);
+    hipError_t ce = hipGetLastError();
+    if (ce == hipSuccess) ce = hipMemcpy(part.data(), d_part, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_part);
+    QBH_QHIP(who, ce);
+    int64_t nnz = 0;
+    for (unsigned long long v : part) nnz += (int64_t)v;
+
+    const int rc = adopt_mf_qudit(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    if (rc == QBH_OK) pool.p.clear();                         // the handle owns the tables now
+    return rc;
 }
 
 extern "C" int qbh_mopr_qudit_dev(int n_sites, int d, int total_old, int dq, const qbh_z *coef, const qbh_z *local,

@@ -271,10 +271,11 @@ class csr_mat:
         return cls.hubbard_repr(n_sites, n_up, n_dn, b, perms, chars, t=t, U=0.0, pairs=pairs, exchange=exch, no_double=True, **kw)
 
     @classmethod
-    def qudit(cls, n_sites, d, total, pairs=(), singles=(), rows=None, opts=None):
+    def qudit(cls, n_sites, d, total, pairs=(), singles=(), rows=None, opts=None, matrix_free=False):
         """Sector of charge `total` of n_sites sites with d levels, assembled on the device (qbh_gen_qudit; basis and term
-        conventions in quantum_basis_amd.qudit).  pairs: (i, j, M) with M a d^2 x d^2 matrix; singles: (i, diag) with d
-        values; rows=(r0, r1): that row block only."""
+        conventions in quantum_basis_amd.qudit) or applied without a stored matrix (matrix_free=True: qbh_mf_qudit, same
+        basis, no limit of 2^31 states).  pairs: (i, j, M) with M a d^2 x d^2 matrix; singles: (i, diag) with d values;
+        rows=(r0, r1): that row block only."""
         _lib.require_gpu()
         opts = opts if opts is not None else make_opts()
         pairs, singles = list(pairs), list(singles)
@@ -287,28 +288,30 @@ class csr_mat:
         r0, r1 = (0, -1) if rows is None else rows
         h = C.c_void_p()
         dim = C.c_int64(0)
-        check(lib().qbh_gen_qudit(C.byref(h), n_sites, d, total, len(pairs), _p(ps), _p(pm), len(singles), _p(ss), _p(sd),
-                                  C.c_int64(r0), C.c_int64(r1), C.byref(dim), C.byref(opts)), "qbh_gen_qudit")
+        fn = lib().qbh_mf_qudit if matrix_free else lib().qbh_gen_qudit
+        check(fn(C.byref(h), n_sites, d, total, len(pairs), _p(ps), _p(pm), len(singles), _p(ss), _p(sd),
+                 C.c_int64(r0), C.c_int64(r1), C.byref(dim), C.byref(opts)), "qbh_mf_qudit" if matrix_free else "qbh_gen_qudit")
         return cls(0, None, None, None, opts=opts, _handle=h)
 
     @classmethod
-    def spin_heisenberg(cls, n_sites, S, two_sz, bonds, J=1.0, Jz=None, K=0.0, D=0.0, rows=None, opts=None):
+    def spin_heisenberg(cls, n_sites, S, two_sz, bonds, J=1.0, Jz=None, K=0.0, D=0.0, rows=None, opts=None, matrix_free=False):
         """Spin-S XXZ / bilinear-biquadratic chain or lattice with single-ion anisotropy in the sector 2 S^z = two_sz:
         sum_<ij> [J/2 (S+S- + S-S+) + Jz SzSz + K (S.S)^2] + D sum (S^z)^2 on qbh_gen_qudit (total = n S - S^z)."""
         from . import qudit as qd
         singles = qd.single_ion(S, n_sites, D) if D != 0.0 else []
         return cls.qudit(n_sites, qd._two_s(S) + 1, qd.spin_charge(n_sites, S, two_sz), qd.heisenberg_terms(S, bonds, J, Jz, K),
-                         singles, rows=rows, opts=opts)
+                         singles, rows=rows, opts=opts, matrix_free=matrix_free)
 
     @classmethod
-    def bose_hubbard(cls, n_sites, n_bosons, n_max, bonds, t=1.0, U=1.1, mu=0.0, rows=None, opts=None):
+    def bose_hubbard(cls, n_sites, n_bosons, n_max, bonds, t=1.0, U=1.1, mu=0.0, rows=None, opts=None, matrix_free=False):
         """-t sum_<ij> (b+_i b_j + h.c.) + U/2 sum n(n-1) - mu sum n with n_bosons bosons, at most n_max per site
         (examples/trans_absent/latt_square/square_Bose_Hubbard.cc) on qbh_gen_qudit."""
         from . import qudit as qd
         pairs, _ = qd.bose_hubbard_terms(n_max, bonds, t, U, mu)
         n = np.arange(n_max + 1, dtype=np.float64)
         dg = 0.5 * U * n * (n - 1) - mu * n
-        return cls.qudit(n_sites, n_max + 1, n_bosons, pairs, [(s, dg) for s in range(n_sites)], rows=rows, opts=opts)
+        return cls.qudit(n_sites, n_max + 1, n_bosons, pairs, [(s, dg) for s in range(n_sites)], rows=rows, opts=opts,
+                         matrix_free=matrix_free)
 
     @classmethod
     def qudit_repr(cls, n_sites, d, total, perms, chars, pairs=(), singles=(), fake_pos=100.0, shard=(0, 1), opts=None,
