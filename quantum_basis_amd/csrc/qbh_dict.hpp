@@ -1,6 +1,6 @@
 // qbh_dict.hpp -- device-side pieces of the lossless value dictionary, shared by the coder in
 // qbh_kernels.hip (values already in HBM) and by generators that emit codes directly without ever
-// materialising the 16 B/nnz value array (qbh_gen.hip).
+// materialising the 16 B/nnz value array (qbh_sector.hpp).
 //
 // A matrix with at most 256 distinct complex128 values is stored with 1-byte codes, one with at most
 // 65536 with 2-byte codes; products always use the exact original doubles.  Collection is an

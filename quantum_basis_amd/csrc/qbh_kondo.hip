@@ -1,6 +1,6 @@
 // qbh_kondo.hip -- device assembly of the Kondo lattice model (conduction electrons plus a localized spin-1/2 on every
 // site; the reference's add_orbital("electron") + add_orbital("spin-1/2") examples): qbh_gen_kondo, and the term checks
-// the momentum-sector generator in qbh_gen.hip shares.  Basis, ranking and the row terms: qbh_kondo.hpp.
+// the momentum-sector generator in qbh_sector.hip shares.  Basis, ranking and the row terms: qbh_kondo.hpp.
 //
 // Count -> scan -> fill.  The fill kernel follows k_qudit_fill: one row per lane, its entries insertion-sorted by column in
 // the lane's own LDS column as (column, entry code), the values decoded from the codes on the way out.  No private array,

@@ -1,5 +1,5 @@
 // qbh_qudit.hpp -- what the d-level generators share: the word packing and ranking of qbh_qudit.hip (the full sector,
-// qbh_gen_qudit) and of the momentum sectors in qbh_gen.hip (qbh_gen_qudit_repr), and the term merging both run.
+// qbh_gen_qudit) and of the momentum sectors in qbh_sector.hpp / qbh_sector.hip (qbh_gen_qudit_repr), and the term merging both run.
 //
 // Site s holds a level l_s in [0, d) in bits [s b, (s+1) b), b = bits_per_level(d); words of one charge are ranked in
 // ascending order of sum_s l_s d^s, which is the order of the packed words as integers.  The counting table cum[s][q] is

@@ -6,7 +6,7 @@
 // (sort_basis_Lin_order, src/basis.cc:1144-1190; split unzipper_basis, :971-996); a state's row index is its position in
 // that order (j = Lin_Ja[i_a] + Lin_Jb[i_b], src/model.cc:665-670).  Local states (src/basis.cc:52-83): spin-1/2 one bit
 // per site (1 = down); electron two bits per site (bit 0 up, bit 1 down), fermion operators ordered by site
-// (src/basis.cc:2650-2664).  The generators (qbh_gen.hip) index by colexicographic rank and put all up operators before
+// (src/basis.cc:2650-2664).  The generators (qbh_gen.hip, qbh_sector.hip) index by colexicographic rank and put all up operators before
 // all down operators, so H_ref = P D H_gen D P^T with a permutation P and a diagonal of signs D.
 //
 //   keys     one 64-bit key (sub_b, sub_a) per generator index          k_ref_keys

@@ -454,46 +454,120 @@ def _momentum_states(n, nu, nd, perms, chars):
     return words, index, psi
 
 
+def _fermion_reference(Lx, Ly, nu, nd, species, kind, k_old, qv):
+    """c_q / c^dag_q from (nu, nd; k_old) to k_old + qv as the explicit matrix <b, k+q; N -/+ 1| O |a, k; N>, built by anticommuting
+    through operator strings and projecting onto momentum states; returns it with what the device call needs"""
+    n = Lx * Ly
+    perms, shifts = lattices.translations(Lx, Ly)
+    k_new = ((k_old[0] + qv[0]) % Lx, (k_old[1] + qv[1]) % Ly)
+    ch_old = lattices.characters(shifts, k_old, (Lx, Ly))
+    ch_new = lattices.characters(shifts, k_new, (Lx, Ly))
+    coef = np.array([np.exp(-2j * np.pi * (qv[0] * (s % Lx) / Lx + qv[1] * (s // Lx) / Ly)) for s in range(n)]) / np.sqrt(n)
+    nu2, nd2 = nu + (kind if species == 0 else 0), nd + (kind if species == 1 else 0)
+    w_old, i_old, psi_old = _momentum_states(n, nu, nd, perms, ch_old)
+    w_new, i_new, psi_new = _momentum_states(n, nu2, nd2, perms, ch_new)
+    O = np.zeros((len(w_new), len(w_old)), dtype=np.complex128)
+    for a, w in enumerate(w_old):
+        for s_ in range(n):
+            r = _apply_fermion(w, n, s_, species, kind > 0)
+            if r:
+                O[i_new[r[1]], a] += coef[s_] * r[0]
+    return psi_new.conj().T @ O @ psi_old, psi_old, psi_new, perms, ch_old, ch_new, coef, nu2, nd2
+
+
+def _check_fermion_operator(Lx, Ly, nu, nd, species, kind, k_old, qv, rng, weight_on_zero_norm=False):
+    """qbh_mopr_c_hubrepr_dev against _fermion_reference.  With weight_on_zero_norm the source vector keeps its random entries
+    on representatives whose norm vanishes at k_old: their momentum states are zero columns, so the reference ignores them,
+    and the device has to skip them.  Returns, seen from the numpy side, whether a source representative with a stabiliser
+    |S| > 1 carried weight, whether a source representative of zero norm did, and whether a target representative has zero
+    norm."""
+    n = Lx * Ly
+    bonds = lattices.square(Lx, Ly)
+    Okk, psi_old, psi_new, perms, ch_old, ch_new, coef, nu2, nd2 = _fermion_reference(Lx, Ly, nu, nd, species, kind, k_old, qv)
+    d_old, d_new = psi_old.shape[1], psi_new.shape[1]
+    x = rng.standard_normal(d_old) + 1j * rng.standard_normal(d_old)
+    zero_old = np.abs(psi_old).sum(axis=0) == 0
+    if not weight_on_zero_norm:
+        x[zero_old] = 0.0
+    A = q.csr_mat.hubbard_repr(n, nu, nd, bonds, perms, ch_old)
+    B = q.csr_mat.hubbard_repr(n, nu2, nd2, bonds, perms, ch_new)
+    assert A.info().ncols == d_old and B.info().ncols == d_new
+    vx, vy = q.DeviceVec(A, d_old), q.DeviceVec(B, d_new)
+    vx.upload(x)
+    got = q.moprXvec_c_hubrepr(n, nu, nd, species, kind, perms, ch_old, ch_new, coef, vx.ptr, vy.ptr)
+    assert got == (d_old, d_new)
+    y = vy.download(0, d_new)
+    assert np.abs(y - Okk @ x).max() < 1e-12, (species, kind, k_old, qv, np.abs(y - Okk @ x).max())
+    zero_new = np.abs(psi_new).sum(axis=0) == 0
+    assert np.all(y[zero_new] == 0)
+    vx.free()
+    vy.free()
+    A.destroy()
+    B.destroy()
+    orbit = np.count_nonzero(psi_old, axis=0)                  # |G| / |S_a| words in the momentum state of a; 0 for zero norm
+    return bool(np.any((orbit > 0) & (orbit < len(perms)))), bool(np.any(zero_old & (x != 0))), bool(np.any(zero_new))
+
+
 def test_single_fermion_operators_between_sectors():
     """qbh_mopr_c_hubrepr_dev (c_q / c^dag_q, both species) against the explicit matrix <b, k+q; N -/+ 1| O |a, k; N> built by
     anticommuting through operator strings and projecting onto momentum states."""
     Lx, Ly, nu, nd = 4, 2, 3, 2
-    n = Lx * Ly
-    bonds = lattices.square(Lx, Ly)
-    perms, shifts = lattices.translations(Lx, Ly)
     rng = np.random.default_rng(11)
     for species, kind, k_old, qv in [(0, -1, (0, 0), (1, 0)), (1, -1, (1, 1), (2, 1)), (0, +1, (3, 0), (1, 1)), (1, +1, (2, 1), (0, 0)),
                                      (0, -1, (2, 0), (2, 0))]:
-        k_new = ((k_old[0] + qv[0]) % Lx, (k_old[1] + qv[1]) % Ly)
-        ch_old = lattices.characters(shifts, k_old, (Lx, Ly))
-        ch_new = lattices.characters(shifts, k_new, (Lx, Ly))
-        coef = np.array([np.exp(-2j * np.pi * (qv[0] * (s % Lx) / Lx + qv[1] * (s // Lx) / Ly)) for s in range(n)]) / np.sqrt(n)
-        nu2, nd2 = nu + (kind if species == 0 else 0), nd + (kind if species == 1 else 0)
-        w_old, i_old, psi_old = _momentum_states(n, nu, nd, perms, ch_old)
-        w_new, i_new, psi_new = _momentum_states(n, nu2, nd2, perms, ch_new)
-        O = np.zeros((len(w_new), len(w_old)), dtype=np.complex128)
-        for a, w in enumerate(w_old):
-            for s_ in range(n):
-                r = _apply_fermion(w, n, s_, species, kind > 0)
-                if r:
-                    O[i_new[r[1]], a] += coef[s_] * r[0]
-        Okk = psi_new.conj().T @ O @ psi_old
-        d_old, d_new = psi_old.shape[1], psi_new.shape[1]
-        x = rng.standard_normal(d_old) + 1j * rng.standard_normal(d_old)
-        x[np.abs(psi_old).sum(axis=0) == 0] = 0.0
-        A = q.csr_mat.hubbard_repr(n, nu, nd, bonds, perms, ch_old)
-        B = q.csr_mat.hubbard_repr(n, nu2, nd2, bonds, perms, ch_new)
-        assert A.info().ncols == d_old and B.info().ncols == d_new
-        vx, vy = q.DeviceVec(A, d_old), q.DeviceVec(B, d_new)
-        vx.upload(x)
-        got = q.moprXvec_c_hubrepr(n, nu, nd, species, kind, perms, ch_old, ch_new, coef, vx.ptr, vy.ptr)
-        assert got == (d_old, d_new)
-        y = vy.download(0, d_new)
-        assert np.abs(y - Okk @ x).max() < 1e-12, (species, kind, k_old, qv, np.abs(y - Okk @ x).max())
-        vx.free()
+        _check_fermion_operator(Lx, Ly, nu, nd, species, kind, k_old, qv, rng)
+
+
+STABILISED_FERMION_CASES = [                                  # (nu, nd, species, kind, k_old, qv) on the 4x2 torus
+    (2, 2, 1, -1, (0, 0), (1, 0)), (2, 2, 1, +1, (2, 1), (1, 1)),            # out of (2, 2): sources with |S| = 2; at (2, 1) some of zero norm
+    (2, 1, 1, +1, (1, 0), (0, 1)), (2, 3, 1, -1, (3, 1), (2, 0)),            # into (2, 2): targets whose norm vanishes
+]
+
+
+def test_single_fermion_operators_with_stabilised_representatives():
+    """(2, 2) <-> (2, 1) and (2, 3) electrons on the 4x2 torus.  Only the (2, 2) sectors hold words that a translation maps to
+    themselves (an odd number of particles of one species cannot be), so the two directions exercise different things: out
+    of (2, 2) the sqrt(|S_a| / |S_b|) of a stabilised source, into (2, 2) the targets whose norm vanishes at the new
+    momentum.  The source vectors carry weight on zero-norm sources too (k = (2, 1) has eight, k = (0, 0) none), which the
+    reference ignores.  All of it is asserted to occur, from the numpy side."""
+    rng = np.random.default_rng(12)
+    seen = [_check_fermion_operator(4, 2, *case, rng, weight_on_zero_norm=True) for case in STABILISED_FERMION_CASES]
+    # out of (2, 2): a stabilised source with weight both times, zero-norm sources with weight at k = (2, 1); no stabilised target
+    assert seen[:2] == [(True, False, False), (True, True, False)], seen
+    # into (2, 2): nothing stabilised among the sources, zero-norm targets both times
+    assert seen[2:] == [(False, False, True), (False, False, True)], seen
+
+
+@pytest.mark.parametrize("species", [0, 1])
+@pytest.mark.parametrize("kind", [-1, +1])
+def test_single_fermion_operators_are_deterministic_and_write_every_element(species, kind):
+    """The same call twice gives the same bytes, the second time into a vector filled with NaN beforehand: nothing is
+    accumulated across lanes and nothing relies on the output having been cleared."""
+    Lx, Ly, nu, nd = 4, 2, 3, 2
+    n = Lx * Ly
+    bonds = lattices.square(Lx, Ly)
+    perms, shifts = lattices.translations(Lx, Ly)
+    k_old, qv = (1, 0), (2, 1)
+    ch_old = lattices.characters(shifts, k_old, (Lx, Ly))
+    ch_new = lattices.characters(shifts, ((k_old[0] + qv[0]) % Lx, (k_old[1] + qv[1]) % Ly), (Lx, Ly))
+    coef = np.array([np.exp(-2j * np.pi * (qv[0] * (s % Lx) / Lx + qv[1] * (s // Lx) / Ly)) for s in range(n)]) / np.sqrt(n)
+    A = q.csr_mat.hubbard_repr(n, nu, nd, bonds, perms, ch_old)
+    d_old = A.info().ncols
+    rng = np.random.default_rng(13)
+    vx = q.DeviceVec(A, d_old)
+    vx.upload(rng.standard_normal(d_old) + 1j * rng.standard_normal(d_old))
+    out = []
+    for fill in (0.0, np.nan):
+        vy = q.DeviceVec(A, 4 * d_old)                         # longer than either target sector
+        vy.upload(np.full(4 * d_old, fill + 1j * fill))
+        _, d_new = q.moprXvec_c_hubrepr(n, nu, nd, species, kind, perms, ch_old, ch_new, coef, vx.ptr, vy.ptr)
+        assert d_new <= 4 * d_old
+        out.append(vy.download(0, d_new))
         vy.free()
-        A.destroy()
-        B.destroy()
+    assert not np.isnan(out[1]).any() and np.abs(out[0]).max() > 0
+    assert out[0].tobytes() == out[1].tobytes()
+    vx.free()
+    A.destroy()
 
 
 def test_photoemission_sum_rule_in_sectors():

@@ -241,17 +241,19 @@ def test_sz_q_between_momentum_sectors_matches_the_explicit_projection():
     A_old.destroy()
 
 
-@pytest.mark.parametrize("kind", [-1, +1])
-def test_spin_flip_operators_between_momentum_sectors_match_the_explicit_projection(kind):
-    """The off-diagonal branch of moprXvec_repr (src/model.cc:1760-1830): S^-_q / S^+_q from (n_dn, k) to (n_dn -+ 1... , k + q)
-    against P_new^+ A_q P_old with explicit momentum states; convention pinned by P^+ H P = H_repr as above."""
+def _check_spin_flip(n_sites, n_dn, kind, k_old, qk, weight_on_zero_norm=False):
+    """S^-_q / S^+_q from (n_dn, k_old) to (n_dn -+ 1, k_old +- qk) against P_new^+ A_q P_old with explicit momentum states;
+    convention pinned by P^+ H P = H_repr as above.  With weight_on_zero_norm the source vector keeps its random entries on
+    representatives whose norm vanishes at k_old: their columns of P_old are zero, so the reference ignores them, and the
+    device has to skip them.  Returns, seen from the numpy side, whether a source representative with a stabiliser |S| > 1
+    carried weight, whether a source representative of zero norm did, and whether a target representative has zero norm."""
     import scipy.sparse as sp
-    n_sites, n_dn, L = 12, 5, (12, 1)
+    import reprham
+    L = (n_sites, 1)
     n_new = n_dn - kind
     bonds = lattices.chain(n_sites)
-    perms, shifts = lattices.translations(12, 1)
+    perms, shifts = lattices.translations(n_sites, 1)
     perms = np.asarray(perms)
-    k_old, qk = 1, 4
     ch_old = np.asarray(lattices.characters(shifts, (k_old, 0), L))
     F = q.csr_mat.heisenberg(n_sites, n_dn, bonds)
     ia, ja, val = F.download()
@@ -267,9 +269,12 @@ def test_spin_flip_operators_between_momentum_sectors_match_the_explicit_project
             conj = c
     assert conj is not None
     P_old, reps_old, zero_old = _momentum_states(n_sites, n_dn, perms, ch_old, conj)
+    stab_old = np.asarray(reprham.repr_basis(n_sites, n_dn, perms, ch_old)[1])
     rng = np.random.default_rng(11 + kind)
-    x = (rng.normal(size=len(reps_old)) + 1j * rng.normal(size=len(reps_old))) * (~zero_old)
-    found = False
+    x = rng.normal(size=len(reps_old)) + 1j * rng.normal(size=len(reps_old))
+    if not weight_on_zero_norm:
+        x = x * (~zero_old)
+    found, zero_target = False, False
     for sign in (+1, -1):
         k_new = (k_old + sign * qk) % n_sites
         ch_new = np.asarray(lattices.characters(shifts, (k_new, 0), L))
@@ -281,6 +286,7 @@ def test_spin_flip_operators_between_momentum_sectors_match_the_explicit_project
             if abs(np.linalg.norm(want) - np.linalg.norm(phi)) > 1e-10 * max(np.linalg.norm(phi), 1e-30):
                 continue                                  # this (coef sign, target momentum) pair does not match: A_q |k> is not in k_new
             found = True
+            zero_target = zero_target or bool(np.any(zero_new))
             vx = q.DeviceVec(A_old, len(reps_old))
             vy = q.DeviceVec(A_old, len(reps_new))
             vx.upload(x)
@@ -294,6 +300,55 @@ def test_spin_flip_operators_between_momentum_sectors_match_the_explicit_project
     assert found
     F.destroy()
     A_old.destroy()
+    return bool(np.any((stab_old > 1) & ~zero_old)), bool(np.any(zero_old & (x != 0))), zero_target
+
+
+@pytest.mark.parametrize("kind", [-1, +1])
+def test_spin_flip_operators_between_momentum_sectors_match_the_explicit_projection(kind):
+    """The off-diagonal branch of moprXvec_repr (src/model.cc:1760-1830): S^-_q / S^+_q from (n_dn, k) to (n_dn -+ 1... , k + q)
+    against P_new^+ A_q P_old with explicit momentum states; convention pinned by P^+ H P = H_repr as above."""
+    _check_spin_flip(12, 5, kind, 1, 4)
+
+
+def test_spin_flip_operators_with_stabilised_representatives():
+    """Ring of 8, n_dn 3 <-> 4.  Only n_dn = 4 holds patterns that a translation maps to themselves (00110011, 01010101), so
+    the two directions exercise different things: S^+_q out of n_dn = 4 the sqrt(|S_a| / |S_b|) of a stabilised source (at
+    k = 2 one of the two carries weight, the other has zero norm and is skipped), S^-_q into n_dn = 4 at an odd momentum the
+    targets whose norm vanishes.  The source vector carries weight on the zero-norm source as well, which the reference
+    ignores.  All three are asserted to occur, from the numpy side; n_dn = 3 holds no stabilised pattern at all."""
+    out_of_4 = _check_spin_flip(8, 4, +1, 2, 1, weight_on_zero_norm=True)
+    into_4 = _check_spin_flip(8, 3, -1, 2, 1, weight_on_zero_norm=True)
+    assert out_of_4 == (True, True, False), out_of_4          # a stabilised source with weight, a zero-norm source with weight
+    assert into_4 == (False, False, True), into_4             # a zero-norm target
+
+
+@pytest.mark.parametrize("kind", [-1, +1])
+def test_spin_flip_operators_are_deterministic_and_write_every_element(kind):
+    """The same call twice gives the same bytes, the second time into a vector filled with NaN beforehand: nothing is
+    accumulated across lanes and nothing relies on the output having been cleared."""
+    n_sites, n_dn, k_old, qk = 12, 5, 1, 4
+    perms, shifts = lattices.translations(n_sites, 1)
+    perms = np.asarray(perms)
+    ch_old = np.asarray(lattices.characters(shifts, (k_old, 0), (n_sites, 1)))
+    ch_new = np.asarray(lattices.characters(shifts, ((k_old + qk) % n_sites, 0), (n_sites, 1)))
+    coef = np.exp(2j * np.pi * qk * np.arange(n_sites) / n_sites) / np.sqrt(n_sites)
+    A = q.csr_mat.heisenberg_repr(n_sites, n_dn, lattices.chain(n_sites), perms, ch_old)
+    rng = np.random.default_rng(17)
+    vx = q.DeviceVec(A, A.dim)
+    vx.upload(rng.normal(size=A.dim) + 1j * rng.normal(size=A.dim))
+    cap = math.comb(n_sites, 6)                                # longer than either target sector
+    out = []
+    for fill in (0.0, np.nan):
+        vy = q.DeviceVec(A, cap)
+        vy.upload(np.full(cap, fill + 1j * fill))
+        _, d_new = q.moprXvec_flip_repr(n_sites, n_dn, kind, perms, ch_old, ch_new, coef, vx.ptr, vy.ptr)
+        assert d_new <= cap
+        out.append(vy.download(0, d_new))
+        vy.free()
+    assert not np.isnan(out[1]).any() and np.abs(out[0]).max() > 0
+    assert out[0].tobytes() == out[1].tobytes()
+    vx.free()
+    A.destroy()
 
 
 def test_measure_full_static_reproduces_the_references_asserted_correlators():
