@@ -1,5 +1,5 @@
 // qbh_dict.hpp -- device-side pieces of the lossless value dictionary, shared by the coder in
-// qbh_kernels.hip (values already in HBM) and by generators that emit codes directly without ever
+// qbh_csrprep.hip (values already in HBM) and by generators that emit codes directly without ever
 // materialising the 16 B/nnz value array (qbh_sector.hpp).
 //
 // A matrix with at most 256 distinct complex128 values is stored with 1-byte codes, one with at most
@@ -124,7 +124,7 @@ __device__ __forceinline__ uint32_t dict_encode_one(DictEncode &E, const DictTab
     return (uint32_t)code;
 }
 
-// ---- host side (qbh_kernels.hip) ----
+// ---- host side (qbh_csrprep.hip) ----
 struct DictBuild {
     DictTab tab{nullptr, nullptr, nullptr, nullptr, 0};
 };

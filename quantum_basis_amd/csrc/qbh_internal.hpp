@@ -72,6 +72,15 @@ inline void opts_generated(const qbh_opts *opts, qbh_opts *out)      // options 
         if (_rc != QBH_OK) return _rc; \
     } while (0)
 
+// launch kernel k on grid x block (no dynamic LDS) and report a launch error: the tail of every fixed-shape launcher
+template <typename... P, typename... A>
+inline int launch_kernel(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, const A &...args)
+{
+    hipLaunchKernelGGL(k, grid, block, 0, s, args...);
+    QBH_HIP(hipGetLastError());
+    return QBH_OK;
+}
+
 // descriptor of one wave block of k_spmv_wave: the whole rows [r0, r0(next)) holding the nonzeros [p0, p0(next));
 // entry n_wb is a sentinel {nnz, nrows}
 constexpr int kWctrRegions = 3 + 8;
@@ -314,15 +323,23 @@ inline hipError_t dev_alloc(T **p, size_t bytes)
     return device_alloc(reinterpret_cast<void **>(p), bytes);
 }
 
-// launchers implemented in qbh_kernels.hip (all asynchronous on `s`)
+// qbh_spmv_csr.hip (launchers are asynchronous on `s`, here and below)
+using SpmvKernel = void (*)(SpmvArgs);         // address of one instance of a k_spmv_* kernel (the instance tables)
 int launch_spmv(const SpmvArgs &a, int kernel, int npb, int tpr, int grid, hipStream_t s);
 int spmv_grid(int kernel, int64_t n_blocks, int64_t nrows, int tpr);
 int rows_kernel_occupancy(int npb, int tpr, int un, int dict_mode);
+int vector_kernel_occupancy(int tpr, int un, bool dict);
+
+// qbh_spmv_wave.hip
 int launch_spmv_wave(const SpmvArgs &a, int tpr, int grid, hipStream_t s);
 int launch_spmv_wave2(const SpmvArgs &a, int tpr, int ops, int grid, hipStream_t s);   // pipelined; ops 0 plain store, 2 epilogue + far addend
 int wave2_kernel_occupancy(int tpr, int ops);
 int64_t wave2_chunk_slots(int64_t n_wb);
 int launch_reduce_chunks(const double *slots, int64_t n_slots, double *partials, int *nparts_out, hipStream_t s);
+int wave_kernel_occupancy(int tpr);
+int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, WaveDesc *d_wd, int64_t n_wb, hipStream_t s);
+
+// qbh_kron_prep.hip
 int launch_kron_tile(const d2 *x, d2 *xt, int64_t n, const KronTile &t, hipStream_t s, int xt_real = 0, int *flag = nullptr);
 int launch_kron_check(const int64_t *ia, const int32_t *ja, int64_t nrows, int64_t S, int *d_flag, hipStream_t s);
 int launch_kron_count(const int64_t *ia, const int32_t *ja, int64_t nrows, const KronTile &t, int32_t *cnt_near, int32_t *cnt_far, hipStream_t s);
@@ -337,18 +354,6 @@ int launch_kron_fill_codes(const int64_t *ia, const int32_t *ja, const uint8_t *
 int launch_kron_tile_re(const double *x, double *xt, int64_t n, const KronTile &t, hipStream_t s);
 int launch_kron_fill(const int64_t *ia, const int32_t *ja, const d2 *val, int64_t nrows, const KronTile &t, const int64_t *ia_n, int32_t *ja_n,
                      d2 *val_n, const int64_t *ia_f, int32_t *ja_f, d2 *val_f, hipStream_t s);
-int wave_kernel_occupancy(int tpr);
-int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, WaveDesc *d_wd, int64_t n_wb, hipStream_t s);
-int vector_kernel_occupancy(int tpr, int un, bool dict);
-int launch_build_rowblocks(const int64_t *d_ia, int64_t nrows, int64_t window, int32_t *d_rb,
-                           int64_t *d_bp, int64_t n_blocks, hipStream_t s);
-int launch_reduce_partials(const double *partials, int nparts, int ncomp, double *out, hipStream_t s);
-int launch_dotc(const d2 *x, const d2 *y, int64_t n, double *partials, hipStream_t s);
-int launch_axpy_norm(d2 alpha, const double *alpha_dev, const d2 *x, d2 *y, int64_t n, double *partials, double *yr, int *flag,
-                     hipStream_t s, const double *scale_dev = nullptr);
-// the same passes writing the TILED copy of the updated y as well (Kronecker split, band 8: the next SpMV's far-pass gather source)
-int launch_axpy_norm_tile(d2 alpha, const double *alpha_dev, const d2 *x, d2 *y, d2 *yt, int64_t n, const KronTile &t, double *partials,
-                          hipStream_t s, const double *scale_dev = nullptr, int yt_real = 0, int *flag = nullptr);
 // the tiled blocks of the ranks, as gathered (rank after rank; complex or packed real parts), moved into the tiled order of the
 // whole vector the far part of every shard indexes: elements [off[q], off[q] + len[q]) of rank q's block
 struct KronPlace {
@@ -386,6 +391,27 @@ int launch_kron_pack(const KronPack &a, hipStream_t s);
 // need[u] = 1 for every major index u of the WHOLE operator that a far (2-byte or int32 columns) or cross entry of this shard reads
 int launch_kron_need(const uint16_t *c16_f, const int32_t *ja_f, int64_t far_slots, const int32_t *ja_x, int64_t nnz_x, int64_t S, int64_t NUg, int B,
                      uint8_t *need, hipStream_t s);
+
+// qbh_csrprep.hip
+int launch_build_rowblocks(const int64_t *d_ia, int64_t nrows, int64_t window, int32_t *d_rb,
+                           int64_t *d_bp, int64_t n_blocks, hipStream_t s);
+int launch_max_rowlen(const int64_t *d_ia, int64_t nrows, int64_t *d_out, hipStream_t s);
+int build_value_dict(const d2 *d_val, int64_t nnz, int cap, uint8_t **d_code_out, d2 **d_dict_out, int *n_out, hipStream_t s);
+int exclusive_scan(const int32_t *d_cnt, int64_t n, int64_t *d_ia, hipStream_t s);
+int launch_split_count(const int64_t *ia, const int32_t *ja, int64_t nrows, int32_t lo, int32_t hi, int32_t *cnt0, hipStream_t s);
+int launch_split_fill(const int64_t *ia, const int32_t *ja, const d2 *val, const uint8_t *code, int64_t nrows, int32_t lo,
+                      int32_t hi, const int64_t *ia0, int32_t *ja0, d2 *val0, uint8_t *code0, int64_t *ia1, int32_t *ja1,
+                      d2 *val1, uint8_t *code1, int code_w, hipStream_t s);
+
+// qbh_blas1.hip
+int blas_grid(int64_t n);
+int launch_reduce_partials(const double *partials, int nparts, int ncomp, double *out, hipStream_t s);
+int launch_dotc(const d2 *x, const d2 *y, int64_t n, double *partials, hipStream_t s);
+int launch_axpy_norm(d2 alpha, const double *alpha_dev, const d2 *x, d2 *y, int64_t n, double *partials, double *yr, int *flag,
+                     hipStream_t s, const double *scale_dev = nullptr);
+// the same passes writing the TILED copy of the updated y as well (Kronecker split, band 8: the next SpMV's far-pass gather source)
+int launch_axpy_norm_tile(d2 alpha, const double *alpha_dev, const d2 *x, d2 *y, d2 *yt, int64_t n, const KronTile &t, double *partials,
+                          hipStream_t s, const double *scale_dev = nullptr, int yt_real = 0, int *flag = nullptr);
 // tail of a pipelined Lanczos step: |w'|^2 from the axpy's partial sums, a = sc_x * <u, w>, b = sqrt(|w'|^2), the next step's
 // coefficients into state[0..3], {<u,w>, |w'|^2, a, b} into log_slot (host-visible)
 int launch_lanczos_tail(const double *partials, int nparts, const double *dot, double *state, double *log_slot, double sc_x_host, int use_host,
@@ -406,8 +432,19 @@ int launch_cg_update(d2 alpha, const d2 *p, const d2 *pp, d2 *v, d2 *r, int64_t 
                      hipStream_t s, const double *delta_dev = nullptr, double accu2 = 0.0);                                               // v+=a p; r-=a pp; |r|^2
 int launch_randomize(d2 *x, double *xr, int64_t n, int64_t global_offset, uint32_t seed, double *partials, hipStream_t s, const int32_t *major_inv = nullptr, int64_t S = 0);
 int launch_fill_const(d2 *x, int64_t n, double re, hipStream_t s);
-int launch_max_rowlen(const int64_t *d_ia, int64_t nrows, int64_t *d_out, hipStream_t s);
-int blas_grid(int64_t n);
+int launch_pack_real(const d2 *x, double *out, int64_t n, int *flag, hipStream_t s);
+int launch_unpack_real(const double *in, d2 *out, int64_t n, hipStream_t s);
+int launch_imag_norm(const d2 *x, int64_t n, double *partials, hipStream_t s);
+struct Coef8 { double v[16]; };   // up to 8 complex coefficients passed by value
+int launch_multi_dot8(const d2 *V, int64_t ldv, const d2 *w, int64_t n, int nv, double *partials, hipStream_t s);
+int launch_multi_axpy8(const d2 *V, int64_t ldv, const Coef8 &c, int nv, d2 *w, int64_t n, double *partials, hipStream_t s);
+int launch_basis_rotate(d2 *V, int64_t ldv, int64_t n, int m, int keep, const double *d_S, hipStream_t s);
+
+// qbh_mf.hip (its own launchers are declared with their argument structs below)
+int device_cu_count();            // compute units of the current device, 256 if unknown; looked up once
+
+// qbh_hess.cpp
+int symmetric_eigen_jacobi(int m, double *a, double *w, double *z);
 
 // sliced form of the coded Kronecker split (qbh_kronc.hip): groups of 16 rows, entry k of row j at gia[g] + 16 k + j
 struct KroncSliced {
@@ -441,20 +478,6 @@ int launch_kronc_fill(const int64_t *ia, const int32_t *ja, const uint8_t *code,
 size_t kronc_near_lds_bytes(int64_t S);
 int launch_kronc(const KroncSliced &K, const d2 *dict, int n_dict, const double *xt, const double *x, double *y, double alpha, double beta,
                  double gamma, double *partials, unsigned int *ctr, bool static_near, int *nparts_out, hipStream_t s);
-int launch_pack_real(const d2 *x, double *out, int64_t n, int *flag, hipStream_t s);
-int launch_unpack_real(const double *in, d2 *out, int64_t n, hipStream_t s);
-int launch_imag_norm(const d2 *x, int64_t n, double *partials, hipStream_t s);
-int exclusive_scan(const int32_t *d_cnt, int64_t n, int64_t *d_ia, hipStream_t s);
-int launch_split_count(const int64_t *ia, const int32_t *ja, int64_t nrows, int32_t lo, int32_t hi, int32_t *cnt0, hipStream_t s);
-int launch_split_fill(const int64_t *ia, const int32_t *ja, const d2 *val, const uint8_t *code, int64_t nrows, int32_t lo,
-                      int32_t hi, const int64_t *ia0, int32_t *ja0, d2 *val0, uint8_t *code0, int64_t *ia1, int32_t *ja1,
-                      d2 *val1, uint8_t *code1, int code_w, hipStream_t s);
-struct Coef8 { double v[16]; };   // up to 8 complex coefficients passed by value
-int launch_multi_dot8(const d2 *V, int64_t ldv, const d2 *w, int64_t n, int nv, double *partials, hipStream_t s);
-int launch_multi_axpy8(const d2 *V, int64_t ldv, const Coef8 &c, int nv, d2 *w, int64_t n, double *partials, hipStream_t s);
-int launch_basis_rotate(d2 *V, int64_t ldv, int64_t n, int m, int keep, const double *d_S, hipStream_t s);
-int symmetric_eigen_jacobi(int m, double *a, double *w, double *z);
-int build_value_dict(const d2 *d_val, int64_t nnz, int cap, uint8_t **d_code_out, d2 **d_dict_out, int *n_out, hipStream_t s);
 
 // host CSR -> device row shard (qbh_build.hip)
 int host_threads();

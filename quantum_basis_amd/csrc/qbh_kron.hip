@@ -17,12 +17,11 @@
 #include <algorithm>
 
 #include "qbh_internal.hpp"
+#include "qbh_device.hpp"
 
 namespace qbh {
 
 namespace {
-
-__device__ __forceinline__ d2 cmul_h(d2 a, d2 b) { return d2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
 // structure check of a ONE-class operator: every entry of local row r (global major U0 + r / S, minor r % S) keeps the major or
 // the minor index
@@ -249,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void k_kron_cross_rows(const int64_t *ia_x,
     for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; i < ((n_xrows + 31) / 32) * 32; i += ((int64_t)gridDim.x * blockDim.x) >> 3) {
         d2 sum = {0.0, 0.0};
         if (i < n_xrows)
-            for (int64_t k = ia_x[i] + sub; k < ia_x[i + 1]; k += 8) sum += cmul_h(val_x[k], xt[ja_x[k]]);
+            for (int64_t k = ia_x[i] + sub; k < ia_x[i + 1]; k += 8) sum += cmul(val_x[k], xt[ja_x[k]]);
         for (int off = 4; off > 0; off >>= 1) {
             sum.x += __shfl_xor(sum.x, off, 64);
             sum.y += __shfl_xor(sum.y, off, 64);

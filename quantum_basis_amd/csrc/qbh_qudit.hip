@@ -473,13 +473,7 @@ int qudit_merge_terms(const char *who, int n_sites, int d, int n_pairs, const in
 
 int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out)
 {
-    static int ncu = 0;
-    if (ncu == 0) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                  ? prop.multiProcessorCount : 256;
-    }
+    const int ncu = device_cu_count();
     const bool tl = a.t.tables_lds != 0;
     const size_t lds = mf_qudit_lds_bytes(a.t, tl);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ((size_t)158 * 1024) / (lds + 1024)));

@@ -140,7 +140,7 @@ constexpr int kSecMaxHops = 128;
 // y <- alpha MF(x) + beta y + gamma x for every row.  One work item = 1024 rows of one down block; an XCD takes a
 // contiguous run of items, so the workgroups that share an L2 sweep the same block -- and, hop by hop, the same target
 // blocks -- at the same time.
-// ORD: the ordered walk of the wave kernels (qbh_kernels.hip, DynWalk) at workgroup granularity -- every XCD owns one contiguous
+// ORD: the ordered walk of the wave kernels (qbh_spmv_wave.hip; DynWalk in qbh_device.hpp) at workgroup granularity -- every XCD owns one contiguous
 // eighth of the items and its workgroups draw them one at a time from a counter, so they cannot drift apart over the ~1600 items
 // each of them processes (the static assignment keeps them on one block only while they stay in lock step).
 template <bool REALX, int kSecUnroll, bool ORD>

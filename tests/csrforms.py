@@ -5,7 +5,7 @@ Three parts, none of which needs a GPU:
 
 * row-length profiles -> full-storage CSR (sorted distinct columns per row) or Hermitian upper storage, with four kinds of
   values (random complex, real, <= 256 distinct, 257..65536 distinct);
-* a mirror of the launch geometry (qbh_api.cpp setup_geometry / setup_wave_geometry / build_geometry, qbh_kernels.hip spmv_grid
+* a mirror of the launch geometry (qbh_api.cpp setup_geometry / setup_wave_geometry / build_geometry, qbh_spmv_csr.hip spmv_grid
   and the walks BlockWalk / DynWalk) that names the kernel, the template instance and the coding an (operator, options) pair
   runs, which block paths it reaches, and a lower bound on the blocks each persistent workgroup walks;
 * a long-double reference of the epilogue and both reductions with per-row error bounds (see `epilogue`).
@@ -26,7 +26,7 @@ KERNEL_NAMES = {KERNEL_STREAM: "stream", KERNEL_VECTOR: "vector", KERNEL_ROWS: "
 K_BLOCK = 256
 K_DICT_LDS = 1024
 K_ROW_CAP = 1024
-K_DYN_CHUNK = 4          # qbh_kernels.hip QBH_DYN_CHUNK
+K_DYN_CHUNK = 4          # qbh_device.hpp QBH_DYN_CHUNK
 WAVE_TILE = 512          # k_spmv_wave: 64 lanes x U = 8
 MAX_WG_PER_CU = 8        # 32 wavefronts per CU, 4 per workgroup: no occupancy query can return more
 GRID_CAP = 4096          # largest grid spmv_grid() returns (256 * 4 * 4, 256 * 8 * 2); also >= 8 workgroups x 256 CUs
@@ -251,7 +251,7 @@ def block_starts(ia, window, n_blocks):
 
 
 def walk_counts(n_units, grid, swz, chunk_mult=1):
-    """Units (row blocks; groups of 4 wave blocks) each workgroup of a `grid` launch takes under BlockWalk (qbh_kernels.hip:66-94)."""
+    """Units (row blocks; groups of 4 wave blocks) each workgroup of a `grid` launch takes under BlockWalk (qbh_device.hpp)."""
     per_xcd = (n_units + 7) >> 3
     nslot = grid >> 3
     chunk = nslot * max(chunk_mult, 1)
@@ -312,7 +312,7 @@ def route(kernel_opt, value_dict, ia, val, npb_opt=0, xcd_swizzle=2, wave_walk=-
 
 
 def all_routes():
-    """Every template instance qbh_spmv_dev can launch on a complex CSR operator (qbh_kernels.hip launch_spmv, launch_spmv_wave)."""
+    """Every template instance qbh_spmv_dev can launch on a complex CSR operator (qbh_spmv_csr.hip launch_spmv, qbh_spmv_wave.hip launch_spmv_wave)."""
     keys = set()
     for npb in (1024, 2048, 4096):
         for t in (1, 2, 4, 8, 16):

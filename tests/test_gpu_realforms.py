@@ -149,7 +149,7 @@ LDS_CAP = 150 * 1024
 
 
 def _mf_kernel(Nd, wu):
-    """Mirror of mf_row_kernel_ok / launch_mf_hubbard (qbh_kernels.hip) for real vectors: which kernel applies the operator."""
+    """Mirror of mf_row_kernel_ok / launch_mf_hubbard (qbh_mf.hip) for real vectors: which kernel applies the operator."""
     if not (Nd >= 256 and Nd < (1 << 24) and wu <= 64):
         return "lane"
     return "row_windowed" if Nd * 8 > LDS_CAP else "row"
