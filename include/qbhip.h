@@ -827,6 +827,25 @@ int qbh_gen_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz,
                   const double *kz /* [n_sites] */, const double *kxy /* [n_sites] */,
                   int n_sbonds, const int32_t *sbond_sites /* [2*n_sbonds] */, const double *bz, const double *bxy,
                   int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
+/* The operator of qbh_gen_kondo applied without a stored matrix: terms, word packing, basis order (ascending
+ * u | d << n | s << 2n), fermion convention, argument meaning, error codes and the order of the checks are those of
+ * qbh_gen_kondo (every argument and term check runs before the device is looked for).  Each row is unranked from the two
+ * counting tables (7.7 KB) and its terms are walked in the order qbh_gen_kondo generates them; a hop's column is the row plus
+ * a rank difference over the particles between its two sites, a local-spin exchange re-ranks the s field alone, a Kondo flip
+ * re-ranks all three fields.  Rows, ranks and rank differences are 64-bit, nothing is staged per row and no column is stored,
+ * so the limits dim < 2^31 and 160 entries per row of qbh_gen_kondo do not apply (n_sites in [1, 21] remains).
+ * The handle behaves like that of qbh_mf_qudit: SpMV with its fused epilogue and reductions, qbh_multmv(2), every solver,
+ * qbh_csr_set_comm on row shards [row_begin, row_end); qbh_csr_download returns QBH_EUNSUPP.  qbh_csr_get_info reports
+ * kernel = QBH_KERNEL_MATRIX_FREE, nnz = the entries qbh_gen_kondo would store for these rows (counted on the device, the
+ * diagonal always, zero amplitudes dropped elsewhere) and bytes_matrix = the tables held.  The real fast path and the
+ * packed-real drivers apply when every merged hop amplitude has a zero imaginary part (kxy, bxy and the diagonal are real by
+ * construction); a complex operator (flux) runs on complex vectors only.  A row shard computes its rows bit for bit as the
+ * whole operator does: the summation order inside a row is the term order. */
+int qbh_mf_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz,
+                 int n_terms, const int32_t *term_sites /* [2*n_terms] */, const qbh_z *amp_up, const qbh_z *amp_dn, double U,
+                 const double *kz /* [n_sites] */, const double *kxy /* [n_sites] */,
+                 int n_sbonds, const int32_t *sbond_sites /* [2*n_sbonds] */, const double *bz, const double *bxy,
+                 int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
 /* Momentum sectors of qbh_gen_kondo: the same terms and checks; translations as in qbh_gen_heisenberg_repr (1 .. 64 of them,
  * more: QBH_EUNSUPP), acting on the sites of all three fields, with the fermion sign of the two electron fields as in
  * qbh_gen_hubbard_repr.  Every merged term must be carried onto an equal one by every translation, else QBH_EINVAL.

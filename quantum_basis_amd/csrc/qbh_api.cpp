@@ -726,6 +726,7 @@ extern "C" void qbh_csr_destroy(qbh_csr *A)
         for (void *q : {(void *)A->mfq.cum, (void *)A->mfq.pairs, (void *)A->mfq.nrow, (void *)A->mfq.slot, (void *)A->mfq.sdiag,
                         (void *)A->mfq.pdiag, (void *)A->mfq.eout, (void *)A->mfq.eval})
             (void)hipFree(q);
+    if (A->kind == 5) (void)hipFree(A->mfk.K);
     if (A->ev2) (void)hipEventDestroy(A->ev2);
     if (A->ev3) (void)hipEventDestroy(A->ev3);
     for (auto &o : A->ev_old)
@@ -953,7 +954,7 @@ static int adopt_mf_rows(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t ro
     return QBH_OK;
 }
 
-// In the three below the handle owns the tables once the call succeeds; on failure the caller still does.
+// In the four below the handle owns the tables once the call succeeds; on failure the caller still does.
 int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                           int64_t nnz_equiv, const qbh_opts *opts)
 {
@@ -981,6 +982,15 @@ int qbh::adopt_mf_qudit(qbh_csr **out, const qbh::MfQudit &t, bool values_real, 
     return QBH_OK;
 }
 
+int qbh::adopt_mf_kondo(qbh_csr **out, const qbh::MfKondo &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
+                        int64_t nnz_equiv, const qbh_opts *opts)
+{
+    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
+    (*out)->kind = 5;
+    (*out)->mfk = t;
+    return QBH_OK;
+}
+
 extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
 {
     if (!A || !info) return QBH_EINVAL;
@@ -999,6 +1009,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
         info->bytes_matrix = ((int64_t)(A->mfh.n_sites + 1) * (A->mfh.n_dn + 1) + (int64_t)A->mfh.n_chunks * (A->mfh.n_dn + 1) * 64 +
                               3 * (int64_t)A->mfh.n_bonds) * 8;
     if (A->kind == 4) info->bytes_matrix = A->mfq.bytes;
+    if (A->kind == 5) info->bytes_matrix = A->mfk.bytes;
     if (A->kind == 3 && A->mfsec) {
         const qbh::MfSec &m = *A->mfsec;
         info->bytes_matrix = m.n_blocks * (int64_t)sizeof(qbh::MfSecBlock) + m.n_items * 8 + m.n_rrows * 12 + m.rnnz * 20 +

@@ -678,6 +678,26 @@ struct MfQuditArgs {
 int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out);
 int adopt_mf_qudit(qbh_csr **out, const MfQudit &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
                    int64_t nnz_equiv, const qbh_opts *opts);
+// matrix-free Kondo lattice operator, basis and terms of qbh_gen_kondo (qbh_kondo.hip): the row is unranked from the A / binom
+// tables of KondoDev (qbh_kondo.hpp) and its terms walked by kd_row_terms; the one table is the device copy of KondoDev.
+struct KondoDev;
+struct MfKondo {
+    KondoDev *K = nullptr;         // device copy: shape, ranking tables, merged terms
+    int64_t   bytes = 0;           // of that table
+};
+struct MfKondoArgs {
+    MfKondo t;
+    int64_t row_begin, nrows;
+    const d2 *xg, *xl;
+    const double *xr;
+    d2 *y;
+    double alpha, beta, gamma;
+    double *partials;
+    double *y_re;
+};
+int launch_mf_kondo(const MfKondoArgs &a, hipStream_t s, int *nparts_out);
+int adopt_mf_kondo(qbh_csr **out, const MfKondo &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
+                   int64_t nnz_equiv, const qbh_opts *opts);
 // adopt a matrix-free operator (tables already in HBM) behind a qbh_csr handle (qbh_api.cpp)
 int adopt_mf_hubbard(qbh_csr **out, const MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                      int64_t nnz_equiv, const qbh_opts *opts);
@@ -824,12 +844,13 @@ struct qbh_csr {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     // matrix-free operator (kind 1) instead of CSR arrays (kind 0)
-    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites
+    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites | 5 matrix-free Kondo lattice
     qbh::MfSec *mfsec = nullptr;    // kind 3: block tables + compact remainder (host copy of the descriptor, device arrays)
     qbh::MfSec *d_mfsec = nullptr;   // its device copy (kernel argument)
     qbh::MfHubbard mf;
     qbh::MfHeis    mfh;
     qbh::MfQudit   mfq;
+    qbh::MfKondo   mfk;
 
     // split shard: the arrays above hold the locally-owned columns, `rem` the remote ones
     bool     has_rem = false;

@@ -1,6 +1,7 @@
 // qbh_kondo.hip -- device assembly of the Kondo lattice model (conduction electrons plus a localized spin-1/2 on every
-// site; the reference's add_orbital("electron") + add_orbital("spin-1/2") examples): qbh_gen_kondo, and the term checks
-// the momentum-sector generator in qbh_sector.hip shares.  Basis, ranking and the row terms: qbh_kondo.hpp.
+// site; the reference's add_orbital("electron") + add_orbital("spin-1/2") examples): qbh_gen_kondo, the same operator applied
+// without a stored matrix (qbh_mf_kondo, k_mf_kondo), and the term checks the momentum-sector generator in qbh_sector.hip
+// shares.  Basis, ranking and the row terms: qbh_kondo.hpp.
 //
 // Count -> scan -> fill.  The fill kernel follows k_qudit_fill: one row per lane, its entries insertion-sorted by column in
 // the lane's own LDS column as (column, entry code), the values decoded from the codes on the way out.  No private array,
@@ -87,12 +88,159 @@ __global__ __launch_bounds__(kKondoFillBlock) void k_kondo_fill(const KondoDev *
     }
 }
 
+// ------------------------------------------------------------------------------------ matrix-free apply (kind 5) --
+// y <- alpha H x + beta y + gamma x without a stored matrix.  One lane per row, grid-stride over a resident grid; A and binom
+// in LDS, the merged terms read through the kernel's KondoDev pointer (uniform over the lanes).  The row is unranked once
+// and its terms walked by kd_row_terms; the hook gathers x[column] and accumulates in the order the terms arrive, so a row's
+// sum depends on nothing but the row.  Columns:
+//   hop           one species moves inside the block of s: row + (rank' - rank) of that species, times C(n, n_up) for the
+//                 down species; the difference runs over the particles between the two sites only
+//   spin exchange popcount(s) stays: kd_srank(s') + the row's rank inside its block (rd C(n, n_up) + ru)
+//   Kondo flip    the block changes: kd_rank of all three fields
+constexpr int kMfKondoBlock = 256;
+constexpr int kMfKondoPerCu = 7;         // workgroups per CU of the resident grid: 66 VGPRs admit 7 waves per SIMD
+
+// rank(to) - rank(from) (mod 2^64) of two patterns with the same popcount that stand above k0 set bits
+__device__ __forceinline__ uint64_t kd_rank_delta(const uint64_t *binom, uint64_t from, uint64_t to, int k0)
+{
+    uint64_t r = 0;
+    for (int k = k0 + 1; to; ++k) {
+        const int p2 = __ffsll((long long)to) - 1, p1 = __ffsll((long long)from) - 1;
+        to &= to - 1;
+        from &= from - 1;
+        r += binom[p2 * kKondoTab + k] - binom[p1 * kKondoTab + k];
+    }
+    return r;
+}
+
+__device__ __forceinline__ double kd_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <bool REALX>
+__global__ __launch_bounds__(kMfKondoBlock) void k_mf_kondo(MfKondoArgs a)
+{
+    __shared__ uint64_t lds[kKondoTabWords];
+    __shared__ double red[3 * (kMfKondoBlock / 64)];
+    const KondoDev &K = *a.t.K;
+    kd_stage_tables(lds, K, kMfKondoBlock);
+    const uint64_t *A = lds, *binom = lds + kKondoTab * kKondoTab;
+    const int tid = threadIdx.x;
+    double acc[3] = {0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kMfKondoBlock;
+    for (int64_t lrow = (int64_t)blockIdx.x * kMfKondoBlock + tid; lrow < a.nrows; lrow += stride) {
+        const uint64_t grow = (uint64_t)(a.row_begin + lrow);
+        uint64_t u, d, s, ru, rd;
+        kd_unrank(K, A, binom, grow, &u, &d, &s, &ru, &rd);
+        const uint64_t cu = binom[K.n_sites * kKondoTab + K.nu0 + __popcll(s)];
+        const uint64_t in_block = rd * cu + ru;
+        d2 sum = {0.0, 0.0};
+        const d2 dg = kd_row_terms(K, u, d, s, [&](uint64_t u2, uint64_t d2w, uint64_t s2, int code) {
+            const int kind = code >> 12;
+            uint64_t col;
+            if (kind >= 2) {
+                const uint64_t o = kind == 2 ? u : d, o2 = kind == 2 ? u2 : d2w;
+                const uint64_t ends = o ^ o2;                              // the two sites of the hop
+                const int lo = __ffsll((long long)ends) - 1, hi = 63 - __clzll((long long)ends);
+                const uint64_t span = (2ULL << hi) - (1ULL << lo);         // sites lo .. hi
+                const uint64_t dr = kd_rank_delta(binom, o & span, o2 & span, __popcll(o & ((1ULL << lo) - 1ULL)));
+                col = grow + (kind == 2 ? dr : dr * cu);
+            } else if (kind == 1) {
+                col = kd_srank(A, s2) + in_block;
+            } else {
+                col = kd_rank(K, A, binom, u2, d2w, s2);
+            }
+            const d2 v = kd_value(K, code);
+            if (REALX) {
+                sum.x += v.x * a.xr[col];
+            } else {
+                const d2 xv = a.xg[col];
+                sum.x += v.x * xv.x - v.y * xv.y;
+                sum.y += v.x * xv.y + v.y * xv.x;
+            }
+        });
+        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
+        if (a.y_re != nullptr) {
+            if (a.beta != 0.0) yo.x = a.y_re[lrow];
+            xi.x = a.xr[grow];
+        } else {
+            if (a.beta != 0.0) yo = a.y[lrow];
+            if (REALX) xi.x = a.xr[grow];
+            else       xi = a.xg[grow];
+        }
+        sum += dg.x * xi;                                                  // the diagonal is real by construction
+        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
+        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
+        else                   a.y[lrow] = yn;
+        acc[0] += xi.x * yn.x + xi.y * yn.y;
+        acc[1] += xi.x * yn.y - xi.y * yn.x;
+        acc[2] += yn.x * yn.x + yn.y * yn.y;
+    }
+    if (a.partials != nullptr) {
+        const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = kd_wave_sum(acc[c]);
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) red[c * (kMfKondoBlock / 64) + wave] = acc[c];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int c = 0; c < 3; ++c) {
+                double v = 0.0;
+                for (int w2 = 0; w2 < kMfKondoBlock / 64; ++w2) v += red[c * (kMfKondoBlock / 64) + w2];
+                a.partials[(size_t)blockIdx.x * 3 + c] = v;
+            }
+        }
+    }
+}
+
+// entries qbh_gen_kondo would store for rows [row_begin, row_end) (the diagonal always, zero amplitudes dropped elsewhere):
+// what k_kondo_count counts, as one sum per workgroup
+__global__ __launch_bounds__(256) void k_mf_kondo_count(const KondoDev *Kp, int64_t row_begin, int64_t row_end, unsigned long long *part)
+{
+    __shared__ uint64_t lds[kKondoTabWords];
+    __shared__ unsigned long long red[256];
+    const KondoDev &K = *Kp;
+    kd_stage_tables(lds, K, 256);
+    const uint64_t *A = lds, *binom = lds + kKondoTab * kKondoTab;
+    unsigned long long c = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t row = row_begin + (int64_t)blockIdx.x * 256 + threadIdx.x; row < row_end; row += stride) {
+        uint64_t u, d, s, ru, rd;
+        kd_unrank(K, A, binom, (uint64_t)row, &u, &d, &s, &ru, &rd);
+        c += 1;
+        kd_row_terms(K, u, d, s, [&](uint64_t, uint64_t, uint64_t, int) { ++c; });
+    }
+    red[threadIdx.x] = c;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
 struct HipFree {
     std::vector<void *> p;
     ~HipFree() { for (void *q : p) (void)hipFree(q); }
 };
 
 }  // namespace
+
+int launch_mf_kondo(const MfKondoArgs &a, hipStream_t s, int *nparts_out)
+{
+    const int64_t nblk = (a.nrows + kMfKondoBlock - 1) / kMfKondoBlock;
+    const int g = (int)std::min<int64_t>(nblk, std::min<int64_t>((int64_t)device_cu_count() * kMfKondoPerCu, kMaxRedBlocks));
+    if (a.xr != nullptr) hipLaunchKernelGGL(k_mf_kondo<true>, dim3(g), dim3(kMfKondoBlock), 0, s, a);
+    else                 hipLaunchKernelGGL(k_mf_kondo<false>, dim3(g), dim3(kMfKondoBlock), 0, s, a);
+    QBH_HIP(hipGetLastError());
+    if (nparts_out) *nparts_out = g;
+    return QBH_OK;
+}
 
 int kondo_shape(const char *who, int n_sites, int n_elec, int two_sz, KondoDev &K)
 {
@@ -144,7 +292,7 @@ int kondo_shape(const char *who, int n_sites, int n_elec, int two_sz, KondoDev &
 
 int kondo_setup(const char *who, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites, const qbh_z *amp_up,
                 const qbh_z *amp_dn, double U, const double *kz, const double *kxy, int n_sbonds, const int32_t *sbond_sites,
-                const double *bz, const double *bxy, KondoDev &K)
+                const double *bz, const double *bxy, KondoDev &K, bool any_row_length)
 {
     const int shape = kondo_shape(who, n_sites, n_elec, two_sz, K);
     if (shape != QBH_OK && shape != QBH_EUNSUPP) return shape;             // an empty sector is reported after the term checks
@@ -192,7 +340,7 @@ int kondo_setup(const char *who, int n_sites, int n_elec, int two_sz, int n_term
     int max_row = 1 + 2 * (int)pairs.size();
     for (int i = 0; i < n_sites; ++i) max_row += kxy[i] != 0.0 ? 1 : 0;
     for (const auto &kv : bmap) max_row += kv.second[1] != 0.0 ? 1 : 0;
-    if (max_row > kKondoMaxRow || (int)tmap.size() > kKondoMaxTerms || (int)bmap.size() > kKondoMaxSbonds) {
+    if ((max_row > kKondoMaxRow && !any_row_length) || (int)tmap.size() > kKondoMaxTerms || (int)bmap.size() > kKondoMaxSbonds) {
         set_error("%s: a row may hold %d entries; at most %d are supported", who, max_row, kKondoMaxRow);
         return QBH_EUNSUPP;
     }
@@ -350,4 +498,61 @@ extern "C" int qbh_gen_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz,
     qbh_opts og;
     opts_generated(opts, &og);
     return qbh_csr_create_device(out, nrows, dim, row_begin, nnz, d_ia, d_ja, reinterpret_cast<qbh_z *>(d_val), 1, &og);
+}
+
+extern "C" int qbh_mf_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites,
+                            const qbh_z *amp_up, const qbh_z *amp_dn, double U, const double *kz, const double *kxy, int n_sbonds,
+                            const int32_t *sbond_sites, const double *bz, const double *bxy, int64_t row_begin, int64_t row_end,
+                            int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    static const char *who = "qbh_mf_kondo";
+    if (!out) {
+        set_error("%s: out is NULL", who);
+        return QBH_EINVAL;
+    }
+    std::vector<KondoDev> kk(1);
+    KondoDev &K = kk[0];
+    const int max_row = kondo_setup(who, n_sites, n_elec, two_sz, n_terms, term_sites, amp_up, amp_dn, U, kz, kxy, n_sbonds,
+                                    sbond_sites, bz, bxy, K, true);       // no row is staged: any row length
+    if (max_row <= 0) return max_row;
+    if (dim_out) *dim_out = (int64_t)K.total;                 // < 2^63: rows, ranks and rank differences are 64-bit
+    const int64_t dim = (int64_t)K.total;
+    if (row_end < 0) row_end = dim;
+    if (row_begin < 0 || row_begin >= row_end || row_end > dim) {
+        set_error("%s: bad row range [%lld, %lld) of %lld", who, (long long)row_begin, (long long)row_end, (long long)dim);
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_KHIP(who, hipSetDevice(opts->device));
+
+    bool values_real = true;                                  // kxy, bxy and the diagonal are real by construction
+    for (int t = 0; t < K.n_terms; ++t)
+        if (K.aup[t][1] != 0.0 || K.adn[t][1] != 0.0) values_real = false;
+    HipFree pool;
+    MfKondo t;
+    QBH_KHIP(who, qbh::dev_alloc(&t.K, sizeof(KondoDev)));
+    pool.p.push_back(t.K);
+    QBH_KHIP(who, hipMemcpy(t.K, &K, sizeof(KondoDev), hipMemcpyHostToDevice));
+    t.bytes = (int64_t)sizeof(KondoDev);
+
+    const int64_t nrows = row_end - row_begin;
+    const int cgrid = blas_grid(nrows);
+    unsigned long long *d_part = nullptr;
+    QBH_KHIP(who, qbh::dev_alloc(&d_part, (size_t)cgrid * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_mf_kondo_count, dim3(cgrid), dim3(256), 0, 0, t.K, row_begin, row_end, d_part);
+    std::vector<unsigned long long> part((size_t)cgrid);
+    hipError_t ce = hipGetLastError();
+    if (ce == hipSuccess) ce = hipMemcpy(part.data(), d_part, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_part);
+    QBH_KHIP(who, ce);
+    int64_t nnz = 0;
+    for (unsigned long long v : part) nnz += (int64_t)v;
+
+    const int rc = adopt_mf_kondo(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    if (rc == QBH_OK) pool.p.clear();                         // the handle owns the tables now
+    return rc;
 }

@@ -1,5 +1,5 @@
 // qbh_kondo.hpp -- what the Kondo-lattice generators share: the word packing, the ranking and the terms of one row, used by
-// qbh_kondo.hip (the full sector, qbh_gen_kondo) and by the momentum sectors in qbh_sector.hpp / qbh_sector.hip (qbh_gen_kondo_repr).
+// qbh_kondo.hip (the full sector, qbh_gen_kondo and qbh_mf_kondo) and by the momentum sectors in qbh_sector.hpp / qbh_sector.hip (qbh_gen_kondo_repr).
 //
 // A site carries a conduction-electron orbital and a localized spin-1/2.  A word is three n-bit fields
 //     w = u | d << n | s << 2n      u, d: sites occupied by an up / down electron;  s: sites whose local spin is DOWN
@@ -41,10 +41,11 @@ struct KondoDev {
 // merged terms need (> 0), or a code (< 0): n_sites outside
 // [1, 21], n_elec outside [0, 2 n_sites], a parity of (n_elec, two_sz, n_sites) that admits no block, a term outside the
 // lattice: QBH_EINVAL; merged hops not Hermitian: QBH_ENOTHERM; no block inside the range of n_up, n_dn (K.total = 0) or a
-// row that may hold more than kKondoMaxRow entries: QBH_EUNSUPP.  Needs no device.
+// row that may hold more than kKondoMaxRow entries: QBH_EUNSUPP.  Needs no device.  any_row_length: a row above kKondoMaxRow
+// is not refused (the matrix-free form stages no row); every other check is unchanged.
 int kondo_setup(const char *who, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites, const qbh_z *amp_up,
                 const qbh_z *amp_dn, double U, const double *kz, const double *kxy, int n_sbonds, const int32_t *sbond_sites,
-                const double *bz, const double *bxy, KondoDev &K);
+                const double *bz, const double *bxy, KondoDev &K, bool any_row_length = false);
 // the shape part of kondo_setup alone (tables filled, no terms): for operators that only need the basis
 int kondo_shape(const char *who, int n_sites, int n_elec, int two_sz, KondoDev &K);
 // every merged term must be carried onto an equal one by every translation (QBH_EINVAL otherwise)

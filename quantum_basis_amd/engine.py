@@ -376,8 +376,11 @@ class csr_mat:
         return keep, (len(hops), _p(sites), _p(aup), _p(adn)), (_p(kz), _p(kxy), len(sb), _p(ss), _p(bz), _p(bxy))
 
     @classmethod
-    def kondo(cls, n_sites, n_elec, two_sz, bonds, t=1.0, J_K=1.1, J_RKKY=0.0, U=0.0, rows=None, opts=None, terms=None):
-        """Kondo lattice model assembled on the device (qbh_gen_kondo; the reference's chain_Kondo.cc): n_elec conduction
+    def kondo(cls, n_sites, n_elec, two_sz, bonds, t=1.0, J_K=1.1, J_RKKY=0.0, U=0.0, rows=None, opts=None, terms=None,
+              matrix_free=False):
+        """Kondo lattice model assembled on the device (qbh_gen_kondo; the reference's chain_Kondo.cc) or applied without a
+        stored matrix (matrix_free=True: qbh_mf_kondo, same basis, no limit of 2^31 states or of 160 entries per row;
+        kondo.unrank / kondo.rank translate between an index and its word there): n_elec conduction
         electrons and a localized spin-1/2 on every site in the sector 2 S^z_total = two_sz.  Hops -t both ways on every
         bond, J_K S_i . s_i on every site, J_RKKY S_i . S_j between local spins on every bond, U n_up n_dn.  terms =
         kondo.Terms(hops, kz, kxy, sbonds) replaces all three lists (anisotropic couplings, complex hops, observables).
@@ -393,8 +396,9 @@ class csr_mat:
         r0, r1 = (0, -1) if rows is None else rows
         h = C.c_void_p()
         dim = C.c_int64(0)
-        check(lib().qbh_gen_kondo(C.byref(h), n_sites, n_elec, two_sz, *hop, float(U), *rest, C.c_int64(r0), C.c_int64(r1),
-                                  C.byref(dim), C.byref(opts)), "qbh_gen_kondo")
+        fn = lib().qbh_mf_kondo if matrix_free else lib().qbh_gen_kondo
+        check(fn(C.byref(h), n_sites, n_elec, two_sz, *hop, float(U), *rest, C.c_int64(r0), C.c_int64(r1),
+                 C.byref(dim), C.byref(opts)), "qbh_mf_kondo" if matrix_free else "qbh_gen_kondo")
         return cls(0, None, None, None, opts=opts, _handle=h)
 
     @classmethod

@@ -1,4 +1,4 @@
-"""Basis and term lists of the Kondo lattice model (qbh_gen_kondo, qbh_gen_kondo_repr).  Pure numpy, no device.
+"""Basis and term lists of the Kondo lattice model (qbh_gen_kondo, qbh_mf_kondo, qbh_gen_kondo_repr).  Pure numpy, no device.
 
 Every site carries a conduction-electron orbital and a localized spin-1/2.  A basis word is three n-bit fields
 
@@ -15,6 +15,7 @@ The operator (include/qbhip.h, qbh_gen_kondo) is given by a Terms tuple:
 and U sum_i n_up n_dn, passed separately.
 """
 from collections import namedtuple
+from functools import lru_cache
 from math import comb
 
 import numpy as np
@@ -67,6 +68,72 @@ def words(n_sites, n_elec, two_sz):
         ud = (pat[n_dn][:, None] << n) | pat[n_up][None, :]
         out.append(ud.reshape(-1) | (np.uint64(s) << (n + n)))
     return np.concatenate(out) if out else np.zeros(0, dtype=np.uint64)
+
+
+@lru_cache(maxsize=16)
+def _rank_table(n_sites, n_elec, two_sz):
+    """(blocks, A): blocks[m] = (n_up, n_dn) and A[p][c] = sum_j C(p, j) w(c + j) with w(m) = C(n, n_up(m)) C(n, n_dn(m))
+    (0 where the sector has no block m): the words whose s field agrees with a given one above bit p, holds 0 at p and has c
+    ones above p (the table of the device's ranking, qbh_kondo.hpp)."""
+    assert 1 <= n_sites <= MAX_SITES
+    blocks = {m: (n_up, n_dn) for (n_up, n_dn, m) in sector_blocks(n_sites, n_elec, two_sz)}
+    w = [comb(n_sites, blocks[m][0]) * comb(n_sites, blocks[m][1]) if m in blocks else 0 for m in range(n_sites + 1)]
+    A = [[sum(comb(p, j) * w[c + j] for j in range(p + 1) if c + j <= n_sites) for c in range(n_sites + 1)] for p in range(n_sites + 1)]
+    return blocks, A
+
+
+def _colex_rank(bits):
+    r, k = 0, 0
+    p = 0
+    while bits:
+        if bits & 1:
+            k += 1
+            r += comb(p, k)
+        bits >>= 1
+        p += 1
+    return r
+
+
+def _colex_unrank(n_sites, k, r):
+    bits, p = 0, n_sites - 1
+    while k >= 1:
+        while comb(p, k) > r:
+            p -= 1
+        bits |= 1 << p
+        r -= comb(p, k)
+        p -= 1
+        k -= 1
+    return bits
+
+
+def unrank(n_sites, n_elec, two_sz, r):
+    """(u, d, s) of the word with index r in the sector, without enumerating it: words(...)[r] == u | d << n | s << 2n."""
+    blocks, A = _rank_table(n_sites, n_elec, two_sz)
+    r = int(r)
+    assert 0 <= r < sector_dim(n_sites, n_elec, two_sz)
+    s, c = 0, 0
+    for p in range(n_sites - 1, -1, -1):
+        if r >= A[p][c]:
+            s |= 1 << p
+            r -= A[p][c]
+            c += 1
+    n_up, n_dn = blocks[c]
+    cu = comb(n_sites, n_up)
+    return _colex_unrank(n_sites, n_up, r % cu), _colex_unrank(n_sites, n_dn, r // cu), s
+
+
+def rank(n_sites, n_elec, two_sz, u, d, s):
+    """Index in the sector of the word u | d << n | s << 2n (which must belong to it): the inverse of unrank."""
+    blocks, A = _rank_table(n_sites, n_elec, two_sz)
+    u, d, s = int(u), int(d), int(s)
+    m = bin(s).count("1")
+    assert m in blocks and (bin(u).count("1"), bin(d).count("1")) == blocks[m] and max(u, d, s) < 1 << n_sites
+    r, c = 0, 0
+    for p in range(n_sites - 1, -1, -1):
+        if (s >> p) & 1:
+            r += A[p][c]
+            c += 1
+    return r + _colex_rank(d) * comb(n_sites, blocks[m][0]) + _colex_rank(u)
 
 
 def fields(w, n_sites):
