@@ -298,7 +298,8 @@ typedef struct qbh_csr_info {
     int     basis_detected;                  /* 1: basis_internal was found by the library itself (qbh_opts.basis_detect)               */
     int     basis_n_sites, basis_n_up, basis_n_dn;   /* the basis named by the caller or found (0 when basis_internal == 0)          */
     double  basis_detect_ms;                 /* wall ms the search took (inside create_ms for host arrays), whatever it found          */
-    int     kron_table_kernel;               /* 1: the coded split was recognised as T (x) 1 + 1 (x) T' + D and the all-real SpMV runs the table kernel */
+    int     kron_table_kernel;               /* 1: the coded split was recognised as T (x) 1 + 1 (x) T' + D and the all-real SpMV runs the table kernel;
+                                                for a handle of qbh_mf_qudit_repr: 1 = its translation and counting tables are staged in LDS, 0 = read from global memory */
     int     wire_element_bytes;              /* communicator attached: bytes per element of x the LAST gather put on the links -- 16 (complex128) or 8
                                                 (real parts only: qbh_opts.real_wire on split shards, the real fast path on plain ones); 0 before the first */
     int     major_partition;                 /* > 1: the major indices are in the partition order of qbh_opts.major_partition (that many parts) */
@@ -793,6 +794,34 @@ int qbh_gen_qudit_repr_cuts(qbh_csr **out, int n_sites, int d, int total,
                             int n_single, const int32_t *single_sites, const double *single_diag,
                             int n_trans, const int32_t *perms, const double *chars, double fake_pos,
                             int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts);
+/* The sector operator of qbh_gen_qudit_repr applied from its basis, without a stored matrix: terms, basis, character
+ * convention, row formula, zero-norm rows (the fake diagonal fake_pos + i/dim) and dropped zero-norm targets are those of
+ * qbh_gen_qudit_repr, and every argument, term, invariance and symmetry check runs with its codes and in its order, all of
+ * them before the device is looked for.  What is held is the representative list (8 B per row), one info byte per row, the
+ * directory of the enumeration (8 B per 4096 words of the sector) and the tables; each row walks the merged terms, every
+ * target word is canonicalised with the translation tables and its representative found through the directory.  Nothing is
+ * staged per row, so the limit of 160 entries per row of qbh_gen_qudit_repr does not apply (long-range and dense couplings
+ * are accepted); the limits on d, on 64-bit words, on 1024 site pairs, on 64 translations, on 2^40 words and on 2^31
+ * representatives remain.  Rows [row_begin, row_end) of the sector as in qbh_mf_qudit (row_end = -1: to the end); a range
+ * that cannot lie in the sector is QBH_EINVAL, before the device is looked for where the number of words already excludes it,
+ * else after the enumeration, with *dim_out (may be NULL) set to the sector dimension.  At d = 2 with level 1 = down the
+ * operator is that of qbh_gen_heisenberg_repr.
+ * The handle behaves like that of qbh_mf_qudit: SpMV with its fused epilogue and reductions, qbh_multmv(2), every solver,
+ * qbh_csr_set_comm on row shards; qbh_csr_download returns QBH_EUNSUPP.  qbh_csr_get_info reports kernel =
+ * QBH_KERNEL_MATRIX_FREE, bytes_matrix = tables + representatives + info bytes + directory, kron_table_kernel = 1 when the
+ * translation tables and the counting table are staged in LDS (0: they exceed the LDS budget and are read from global
+ * memory) and nnz = the number of contributions the kernel applies for these rows: one diagonal per row plus every
+ * off-diagonal term entry whose target has nonzero norm, counted BEFORE duplicates merge.  That is an upper bound on what
+ * qbh_gen_qudit_repr stores for the same rows (two entries of a row that reach the same representative are two
+ * contributions here and one stored entry there); counting merged entries would need the row array this form exists to
+ * avoid.  The real fast path and the packed-real drivers apply when every merged pair matrix is real and every character is
+ * real (k = 0 and k = pi among them; an imaginary part below 1e-13 is the rounding of sin(pi t) and is dropped).  A row shard
+ * computes its rows bit for bit as the whole operator does: the summation order inside a row is the term order. */
+int qbh_mf_qudit_repr(qbh_csr **out, int n_sites, int d, int total,
+                      int n_pairs, const int32_t *pair_sites, const qbh_z *pair_mat,
+                      int n_single, const int32_t *single_sites, const double *single_diag,
+                      int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                      int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
 /* moprXvec_repr (src/model.cc:1715-1846) for O_q = sum_s coef[s] O_s between momentum sectors of qbh_gen_qudit_repr: local as
  * in qbh_mopr_qudit_dev (nonzero only where l' = l + dq, else QBH_EINVAL).  coef must transform with a character,
  * coef[g(s)] = eta(g) coef[s] for every translation (else QBH_EINVAL); the operator maps the sector (total_old, chars_old)

@@ -108,7 +108,7 @@ EXPORTS = [
     "qbh_ckpt_cg_update", "qbh_ckpt_cg_init", "qbh_ckpt_cg_clean", "qbh_eigenvec_cg_ckpt",
     "qbh_csr_set_comm", "qbh_rccl_unique_id", "qbh_comm_create_rccl", "qbh_comm_destroy", "qbh_get_stats", "qbh_sync", "qbh_csr_set_option", "qbh_csr_major_order",
     "qbh_gen_hubbard", "qbh_mf_hubbard", "qbh_gen_heisenberg", "qbh_mf_heisenberg", "qbh_gen_heisenberg_repr", "qbh_gen_hubbard_repr", "qbh_gen_heisenberg_repr_cuts", "qbh_gen_hubbard_repr_cuts", "qbh_mf_hubbard_repr", "qbh_mopr_diag_hubrepr_dev", "qbh_mopr_c_hubrepr_dev", "qbh_csr_download", "qbh_csr_reference_order", "qbh_csr_set_basis",
-    "qbh_gen_qudit", "qbh_mf_qudit", "qbh_mopr_qudit_dev", "qbh_gen_qudit_repr", "qbh_gen_qudit_repr_cuts", "qbh_mopr_qudit_repr_dev",
+    "qbh_gen_qudit", "qbh_mf_qudit", "qbh_mopr_qudit_dev", "qbh_gen_qudit_repr", "qbh_gen_qudit_repr_cuts", "qbh_mf_qudit_repr", "qbh_mopr_qudit_repr_dev",
     "qbh_gen_kondo", "qbh_mf_kondo", "qbh_gen_kondo_repr", "qbh_gen_kondo_repr_cuts", "qbh_mopr_diag_kondo_repr_dev",
 ]
 
@@ -233,6 +233,8 @@ def lib():
                                      dbl, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Opts)]
     L.qbh_gen_qudit_repr_cuts.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp,
                                           vp, dbl, C.c_int, C.c_int, vp, C.POINTER(i64), C.POINTER(Opts)]
+    L.qbh_mf_qudit_repr.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp,
+                                    dbl, i64, i64, C.POINTER(i64), C.POINTER(Opts)]
     L.qbh_mopr_qudit_repr_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
                                           C.POINTER(i64), vp]
     kterms = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, dbl, vp, vp, C.c_int, vp, vp, vp]

@@ -727,6 +727,8 @@ extern "C" void qbh_csr_destroy(qbh_csr *A)
                         (void *)A->mfq.pdiag, (void *)A->mfq.eout, (void *)A->mfq.eval})
             (void)hipFree(q);
     if (A->kind == 5) (void)hipFree(A->mfk.K);
+    if (A->kind == 6)
+        for (int k = 0; k < A->mfqr.n_own; ++k) (void)hipFree(A->mfqr.own[k]);
     if (A->ev2) (void)hipEventDestroy(A->ev2);
     if (A->ev3) (void)hipEventDestroy(A->ev3);
     for (auto &o : A->ev_old)
@@ -954,7 +956,7 @@ static int adopt_mf_rows(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t ro
     return QBH_OK;
 }
 
-// In the four below the handle owns the tables once the call succeeds; on failure the caller still does.
+// In the five below the handle owns the tables once the call succeeds; on failure the caller still does.
 int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                           int64_t nnz_equiv, const qbh_opts *opts)
 {
@@ -991,6 +993,15 @@ int qbh::adopt_mf_kondo(qbh_csr **out, const qbh::MfKondo &t, bool values_real, 
     return QBH_OK;
 }
 
+int qbh::adopt_mf_qudit_repr(qbh_csr **out, const qbh::MfQuditRepr &t, bool values_real, int64_t nrows, int64_t ncols,
+                             int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts)
+{
+    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
+    (*out)->kind = 6;
+    (*out)->mfqr = t;
+    return QBH_OK;
+}
+
 extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
 {
     if (!A || !info) return QBH_EINVAL;
@@ -1010,6 +1021,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
                               3 * (int64_t)A->mfh.n_bonds) * 8;
     if (A->kind == 4) info->bytes_matrix = A->mfq.bytes;
     if (A->kind == 5) info->bytes_matrix = A->mfk.bytes;
+    if (A->kind == 6) info->bytes_matrix = A->mfqr.bytes;
     if (A->kind == 3 && A->mfsec) {
         const qbh::MfSec &m = *A->mfsec;
         info->bytes_matrix = m.n_blocks * (int64_t)sizeof(qbh::MfSecBlock) + m.n_items * 8 + m.n_rrows * 12 + m.rnnz * 20 +
@@ -1056,6 +1068,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
     info->basis_n_dn = A->basis.kind ? A->basis.n_dn : 0;
     info->basis_detect_ms = A->detect_ms;
     info->kron_table_kernel = (A->kronc.active && A->kronc.table_route) ? 1 : 0;
+    if (A->kind == 6) info->kron_table_kernel = A->mfqr.tables_lds;      // the sector's tables in LDS (1) or in global memory (0)
     if (A->kronc.active) {                       // the coded form of the split (row kernel, packed-double vectors)
         info->kron_minor = A->kronc.t.S;
         info->kron_far_nnz = A->kronc.sl.active ? A->kronc.sl.slots_f : A->kronc.far_p.nnz;      // sliced: stored far entries (padding included)

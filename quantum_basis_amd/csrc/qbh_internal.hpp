@@ -698,6 +698,36 @@ struct MfKondoArgs {
 int launch_mf_kondo(const MfKondoArgs &a, hipStream_t s, int *nparts_out);
 int adopt_mf_kondo(qbh_csr **out, const MfKondo &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
                    int64_t nnz_equiv, const qbh_opts *opts);
+// matrix-free momentum sector of the d-level sites, basis and rows of qbh_gen_qudit_repr (qbh_sector_mf_qudit.hip): the row's
+// representative and info byte are read, its terms walked as qrepr_row walks them (qbh_sector.hpp), every target word
+// canonicalised with the translation tables and found through the directory of the enumeration.
+struct MfQuditRepr {
+    const void     *R = nullptr;         // device copy of QuditReprDev: shape, characters, term tables
+    const uint64_t *tab = nullptr;       // [n_tab] byte-sliced translation tables (sector_symmetry)
+    const uint64_t *cum = nullptr;       // [n_cum] counting table of qd_rank
+    const uint64_t *reps = nullptr;      // [dim] representatives, ascending
+    const uint8_t  *info = nullptr;      // [dim] |S| | zero-norm << 7
+    const int64_t  *chunk_pos = nullptr; // [nchunks + 1] directory: first representative of every 4096 ranks
+    int64_t   dim = 0;
+    int       n_tab = 0, n_cum = 0;
+    int       tables_lds = 0;            // 1: tab and cum are staged in LDS; 0: they are read from global memory
+    int       n_own = 0;
+    void     *own[16] = {};              // every device array above and behind R: freed with the handle
+    int64_t   bytes = 0;                 // tables + representatives + info bytes + directory
+};
+struct MfQuditReprArgs {
+    MfQuditRepr t;
+    int64_t row_begin, nrows;
+    const d2 *xg, *xl;
+    const double *xr;
+    d2 *y;
+    double alpha, beta, gamma;
+    double *partials;
+    double *y_re;
+};
+int launch_mf_qudit_repr(const MfQuditReprArgs &a, hipStream_t s, int *nparts_out);
+int adopt_mf_qudit_repr(qbh_csr **out, const MfQuditRepr &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
+                        int64_t nnz_equiv, const qbh_opts *opts);
 // adopt a matrix-free operator (tables already in HBM) behind a qbh_csr handle (qbh_api.cpp)
 int adopt_mf_hubbard(qbh_csr **out, const MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                      int64_t nnz_equiv, const qbh_opts *opts);
@@ -844,13 +874,14 @@ struct qbh_csr {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     // matrix-free operator (kind 1) instead of CSR arrays (kind 0)
-    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites | 5 matrix-free Kondo lattice
+    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites | 5 matrix-free Kondo lattice | 6 matrix-free d-level momentum sector
     qbh::MfSec *mfsec = nullptr;    // kind 3: block tables + compact remainder (host copy of the descriptor, device arrays)
     qbh::MfSec *d_mfsec = nullptr;   // its device copy (kernel argument)
     qbh::MfHubbard mf;
     qbh::MfHeis    mfh;
     qbh::MfQudit   mfq;
     qbh::MfKondo   mfk;
+    qbh::MfQuditRepr mfqr;
 
     // split shard: the arrays above hold the locally-owned columns, `rem` the remote ones
     bool     has_rem = false;

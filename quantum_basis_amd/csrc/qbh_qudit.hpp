@@ -1,5 +1,6 @@
 // qbh_qudit.hpp -- what the d-level generators share: the word packing and ranking of qbh_qudit.hip (the full sector,
-// qbh_gen_qudit) and of the momentum sectors in qbh_sector.hpp / qbh_sector.hip (qbh_gen_qudit_repr), and the term merging both run.
+// qbh_gen_qudit) and of the momentum sectors in qbh_sector.hpp / qbh_sector.hip / qbh_sector_mf_qudit.hip (qbh_gen_qudit_repr,
+// qbh_mf_qudit_repr), and the term merging all of them run.
 //
 // Site s holds a level l_s in [0, d) in bits [s b, (s+1) b), b = bits_per_level(d); words of one charge are ranked in
 // ascending order of sum_s l_s d^s, which is the order of the packed words as integers.  The counting table cum[s][q] is
@@ -58,6 +59,21 @@ __device__ __forceinline__ uint64_t qd_unrank(const uint64_t *cum, int n_sites, 
         w |= (uint64_t)l << (s * bits);
     }
     return w;
+}
+
+// the rank of word w among the words of its charge, the inverse of qd_unrank: site s adds the words that agree with w above
+// s and hold a smaller level at s, cum[s][Q_s] - cum[s][Q_s - l_s] with Q_s the charge of sites 0..s
+__device__ __forceinline__ uint64_t qd_rank(const uint64_t *cum, int n_sites, int bits, int tw, uint64_t w)
+{
+    uint64_t r = 0;
+    int Q = 0;
+    for (int s = 0; s < n_sites; ++s) {
+        const int l = qd_level(w, bits, s);
+        Q += l;
+        const uint64_t *c = cum + s * tw;
+        r += c[Q] - c[Q - l];
+    }
+    return r;
 }
 
 // the next word of the same charge: the lowest site s that can take one more level while the sites below it give one up

@@ -1,7 +1,7 @@
 // qbh_sector.hpp -- the momentum-sector toolkit: the symmetry tables, the enumeration of orbit representatives, the row
 // helpers and the four families (spin-1/2, Hubbard / t-J, d-level sites, Kondo lattice) with their row functions.  Used by
 // the stored sector generators (qbh_sector.hip), the operators between sectors (qbh_sector_mopr.hip) and the matrix-free
-// Hubbard sector (qbh_sector_mf.hip).  Internal linkage: each translation unit instantiates the kernels it uses.
+// sectors (Hubbard: qbh_sector_mf.hip, d-level sites: qbh_sector_mf_qudit.hip).  Internal linkage: each translation unit instantiates the kernels it uses.
 #pragma once
 #include "qbh_gen_util.hpp"
 #include "qbh_dict.hpp"
@@ -487,6 +487,22 @@ __device__ __forceinline__ uint64_t sector_seek(const QuditReprDev &R, uint64_t 
 }
 __device__ __forceinline__ void sector_step(const QuditReprDev &R, uint64_t &cur) { cur = qd_next(cur, R.n_sites, R.d, R.bits); }
 
+// the word a with the levels of sites si and sj replaced by those of the term entry o = l'_i | l'_j << 8
+__device__ __forceinline__ uint64_t qrepr_target(uint64_t a, int bits, uint64_t field, int si, int sj, int o)
+{
+    return (a & ~((field << (si * bits)) | (field << (sj * bits)))) | ((uint64_t)(o & 0xff) << (si * bits)) |
+           ((uint64_t)(o >> 8) << (sj * bits));
+}
+
+// the entry h = <a|M|c> of a row with |S_a| = sa whose target is carried to a representative with info byte cj by g:
+// h * conj(chi(g)) * sqrt(|S_b|/|S_a|)
+__device__ __forceinline__ d2 qrepr_value(const QuditReprDev &R, d2 h, int g, uint8_t cj, double sa)
+{
+    const double f = sqrt((double)(cj & 0x7f) / sa);
+    const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];
+    return d2{h.x * cr - h.y * cim, h.x * cim + h.y * cr};
+}
+
 // one row of the sector operator into (cols, vals), columns ascending, duplicates merged; returns its length
 __device__ int qrepr_row(const QuditReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
                          int32_t *cols, d2 *vals)
@@ -509,18 +525,13 @@ __device__ int qrepr_row(const QuditReprDev &R, const uint64_t *tab, const uint6
         const int e1 = R.eoff[p * d2n + in + 1];
         for (int e = R.eoff[p * d2n + in]; e < e1; ++e) {
             const int o = R.eout[e];
-            const uint64_t c = (a & ~((field << (si * R.bits)) | (field << (sj * R.bits)))) | ((uint64_t)(o & 0xff) << (si * R.bits)) |
-                               ((uint64_t)(o >> 8) << (sj * R.bits));
+            const uint64_t c = qrepr_target(a, R.bits, field, si, sj, o);
             int g = 0;
             const uint64_t b = sector_canonical(R, tab, c, &g);
             const int64_t lo = sector_find(reps, dim, b);
             const uint8_t cj = info[lo];
             if (cj & 0x80) continue;      // zero-norm target: dropped
-            const double f = sqrt((double)(cj & 0x7f) / sa);
-            const d2 h = R.eval[e];
-            const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];        // conj(chi(g*)) * sqrt(|S_b|/|S_a|)
-            const d2 v = {h.x * cr - h.y * cim, h.x * cim + h.y * cr};
-            row_add(cols, vals, n, kQuditReprMaxRow, i, lo, v, dg);
+            row_add(cols, vals, n, kQuditReprMaxRow, i, lo, qrepr_value(R, R.eval[e], g, cj, sa), dg);
         }
     }
     return row_finish(cols, vals, n, dg);
@@ -810,9 +821,12 @@ struct SectorDev {
     int64_t dim = 0;
 };
 
-// enumerates the sector described by R (its term pointers already set, or unused); everything in S joins `pool`
+// enumerates the sector described by R (its term pointers already set, or unused); everything in S joins `pool`.  With
+// chunk_pos_out the directory of the enumeration is kept in the pool as well: chunk_pos[c] = the position of the first
+// representative among the words of ranks [c * kSectorChunk, (c + 1) * kSectorChunk), nchunks + 1 entries, the last one dim.
 template <class Dev>
-int sector_enumerate(const Dev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, SectorDev<Dev> &S, const char *who)
+int sector_enumerate(const Dev &R, const std::vector<uint64_t> &tab, std::vector<void *> &pool, SectorDev<Dev> &S, const char *who,
+                     int64_t **chunk_pos_out = nullptr, int64_t *nchunks_out = nullptr)
 {
     int64_t nstates = 0;
     std::vector<uint64_t> ctab;
@@ -829,7 +843,14 @@ int sector_enumerate(const Dev &R, const std::vector<uint64_t> &tab, std::vector
     int64_t *d_pos = nullptr;
     QBH_HIP_WHO(who, tmp.alloc(&d_code, (size_t)nstates));
     QBH_HIP_WHO(who, tmp.alloc(&d_cnt, (size_t)nchunks * sizeof(int32_t)));
-    QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
+    if (chunk_pos_out) {
+        QBH_HIP_WHO(who, qbh::dev_alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
+        pool.push_back(d_pos);
+        *chunk_pos_out = d_pos;
+        if (nchunks_out) *nchunks_out = nchunks;
+    } else {
+        QBH_HIP_WHO(who, tmp.alloc(&d_pos, (size_t)(nchunks + 1) * sizeof(int64_t)));
+    }
     hipLaunchKernelGGL(k_sector_flag<Dev>, dim3(egrid), dim3(256), 0, 0, S.R, S.tab, nstates, d_code, d_cnt, nchunks);
     QBH_HIP_WHO(who, hipGetLastError());
     QBH_TRY(exclusive_scan(d_cnt, nchunks, d_pos, 0));
