@@ -368,6 +368,26 @@ def test_iram_device_resident_with_a_large_basis():
             assert np.linalg.norm(O.multmv(Z[j]) - w[j] * Z[j]) < 1e-7
 
 
+def test_iram_device_resident_past_one_trip_of_the_basis_kernels():
+    """dim 705,432 > 524,288: threads of k_multi_dot<8>, k_multi_axpy and k_basis_rotate take a second trip (the other IRAM
+    tests stop at dim 34,650); complex basis (real_fast_path=0)"""
+    g = helpers.probe()["chain22_sz0"]
+    A = q.csr_mat.heisenberg(22, 11, lattices.chain(22), opts=q.make_opts(real_fast_path=0))
+    n = A.dim
+    assert n == g["dim"] and n > 524288
+    nconv, w, z = q.iram(n, A, None, 2, 10, 3000, "sr", method="device")
+    assert nconv == 2
+    assert abs(w[0] - g["E0"]) <= E0_RTOL * abs(g["E0"])
+    Z = z.reshape(2, n)
+    assert np.allclose(Z.conj() @ Z.T, np.eye(2), atol=1e-10)
+    hz = np.empty(n, dtype=np.complex128)
+    for j in range(2):
+        zj = np.ascontiguousarray(Z[j])
+        A.MultMv(zj, hz)
+        assert np.linalg.norm(hz - w[j] * zj) < 1e-8
+    A.destroy()
+
+
 def test_iram_main_test_tj_chain_degenerate_pair():
     """src/main_test.cc:113-211: locate_E0_iram(full, 4, 8) on the t-J chain, E0 = E1 = -9.762087307."""
     k = helpers.known()["tJ_chain12"]
