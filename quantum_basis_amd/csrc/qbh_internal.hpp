@@ -38,6 +38,7 @@ struct DebugSw {
     int mf_row = -1, mf_chunk = 0, mf_window = 0;                         // matrix-free Hubbard kernel
     int kronc_abl = 0, kronc_far_chunk = 0, kronc_far_ng = 0, kronc_far_nt = 0;
     int no_far_align = 0;     // in-place split: the far part directly behind the near part (unaligned)
+    int far_cols8 = -1;       // 0: the sliced far pass keeps reading its 2-byte columns slot by slot (no grouped copy, KronSplit::c8_f; A/B only)
     int no_defer = 0;         // Lanczos: read <u, w> back every step instead of keeping it on the device
     int host_delay_us = 0;    // Lanczos: the host spins this long after every read-back of a step's scalars (models a slow / descheduled host)
     int pipe_nospec = 0;      // pipelined Lanczos loop: 1 = never enqueue a step before the one before it has been read back (debugging)
@@ -132,6 +133,9 @@ struct SpmvArgs {
     // block's descriptor names (WaveDesc::pad) -- near part: column - pad * kS (pad = major index of the block's first row);
     // sliced far part: target major index + (band - (pad >> 1)) * kNU, the x element is (pad >> 1) * 8 kNU + 8 * that + lane % 8
     const uint16_t *ja16;
+    // sliced far part whose 8 slots of a line all name the same major index (T (x) 1): that value once per 8 slots, entry i >> 3 for
+    // slot i (k_spmv_wave2<.., G8 = true>: one column load per lane and block instead of eight); nullptr: ja16 is read
+    const uint16_t *ja8;
     // k_spmv_wave2 under the dynamic walk, passes with the fused epilogue: one slot of three sums per chunk of blocks
     // (wave2_chunk_slots(n_wb) slots; never nullptr for those launches), added up in a fixed order by launch_reduce_chunks
     double *chunk_red;
@@ -306,6 +310,7 @@ int launch_kron_desc_c16(WaveDesc *wd, int64_t n_wb, int64_t div, bool far, bool
 // raised when a value does not fit 16 bits (or a far column is not what the sliced layout promises)
 int launch_kron_c16_near(const WaveDesc *wd, int64_t n_wb, const int32_t *ja, int64_t S, int64_t col0, uint16_t *out, int *flag, hipStream_t s);
 int launch_kron_c16_far(const WaveDesc *wd, const int32_t *ja, int64_t slots, int64_t NU, uint16_t *out, int *flag, hipStream_t s);
+int launch_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *flag, hipStream_t s);
 int launch_kron_check2(const int64_t *ia, const int32_t *ja, int64_t nrows, int64_t S, int64_t U0, int *d_flag, hipStream_t s);
 // qbh_opts.basis_kind (qbh_reorder.hip): re-express the plain CSR of A in the library's internal order, keep the vector map
 int basis_to_internal(qbh_csr *A, int kind, int n_sites, int n_up, int n_dn, bool *applied);
@@ -827,6 +832,7 @@ struct qbh_csr {
         int64_t *ia_n = nullptr, *ia_f = nullptr;
         int32_t *ja_n = nullptr, *ja_f = nullptr;
         uint16_t *c16_n = nullptr, *c16_f = nullptr;    // 2-byte columns (qbh_opts.kron_cols16): allocations of their own; the int32 form of that part is gone
+        uint16_t *c8_f = nullptr;       // c16_f once per 8 slots, where the 8 are equal throughout: what the far pass reads (derived; lives and dies with c16_f)
         qbh::d2 *val_n = nullptr, *val_f = nullptr;
         qbh::WaveDesc *wd_n = nullptr, *wd_f = nullptr;
         int64_t  nwb_n = 0, nwb_f = 0;

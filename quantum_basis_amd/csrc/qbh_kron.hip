@@ -308,6 +308,19 @@ __global__ __launch_bounds__(kBlock) void k_kron_c16_far(const WaveDesc *wd, con
     if (bad) *flag = 1;
 }
 
+// the far columns once per 8 slots (slots is a multiple of 8): line l = slots 8 l .. 8 l + 7 = one entry of the 8 rows of a group.
+// For T (x) 1 the hop does not depend on the minor index and the 8 values are equal; one line that is not raises the flag.
+__global__ __launch_bounds__(kBlock) void k_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *flag)
+{
+    bool bad = false;
+    for (int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; l < (slots >> 3); l += (int64_t)gridDim.x * blockDim.x) {
+        const uint16_t c = c16[l << 3];
+        for (int j = 1; j < 8; ++j) bad = bad || c16[(l << 3) + j] != c;
+        out[l] = c;
+    }
+    if (bad) *flag = 1;
+}
+
 }  // namespace
 
 int launch_kron_desc_c16(WaveDesc *wd, int64_t n_wb, int64_t div, bool far, bool undo, hipStream_t s)
@@ -327,6 +340,13 @@ int launch_kron_c16_near(const WaveDesc *wd, int64_t n_wb, const int32_t *ja, in
 int launch_kron_c16_far(const WaveDesc *wd, const int32_t *ja, int64_t slots, int64_t NU, uint16_t *out, int *flag, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kron_c16_far, dim3(4096), dim3(kBlock), 0, s, wd, ja, slots, NU, out, flag);
+    QBH_HIP(hipGetLastError());
+    return QBH_OK;
+}
+
+int launch_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *flag, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kron_c8_far, dim3(4096), dim3(kBlock), 0, s, c16, slots, out, flag);
     QBH_HIP(hipGetLastError());
     return QBH_OK;
 }

@@ -24,7 +24,7 @@ void kron_free_aux(qbh_csr *A)
 {
     qbh_csr::KronSplit &K = A->kron;
     for (void *q : {(void *)K.ia_n, (void *)K.ia_f, (void *)K.wd_n, (void *)K.wd_f, (void *)K.d_xt, (void *)K.d_far, (void *)K.ia_x, (void *)K.xrow,
-                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
+                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
         if (q) (void)hipFree(q);
     if (K.own_far) {
         if (K.ja_f) (void)hipFree(K.ja_f);
@@ -177,6 +177,34 @@ int kron_short_cols(qbh_csr *A)
     // order (k_kron_place), the columns never change
     if (K.sliced && !K.own_far && K.t.B == 8 && 2 * K.NUg <= 65536 && K.far_slots > 0)
         QBH_TRY(convert(true, &K.c16_f));
+    // T (x) 1: the 8 slots of a line of the far stream name the same major index -- the hop does not depend on the minor index, and
+    // padding carries the row's own.  Then the far pass reads the value once per line from a copy 1/8 the size (k_spmv_wave2's G8;
+    // blocks start at multiples of 512 slots, checked by k_kron_c16_far).  A derived stream only: c16_f stays what everything else
+    // reads, and its values are relative to the same descriptor bases.  One line that is not uniform, no room, or any error: the pass
+    // keeps the per-slot stream.  QBH_DEBUG=far_cols8=0 skips it (A/B of the two streams from one build).
+    if (K.c16_f && K.far_slots % 8 == 0 && qbh::debug_sw().far_cols8 != 0) {
+        const int64_t cnt = K.far_slots / 8;
+        uint16_t *c = nullptr;
+        if (hipMalloc(&c, (size_t)(cnt + 64) * sizeof(uint16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            c = nullptr;
+        }
+        if (c) {
+            int bad = 0;
+            hipError_t he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+            if (he == hipSuccess) he = hipMemsetAsync(c + cnt, 0, 64 * sizeof(uint16_t), s);
+            const int rc = he == hipSuccess ? qbh::launch_kron_c8_far(K.c16_f, K.far_slots, c, A->d_flag, s) : QBH_OK;
+            if (rc == QBH_OK && he == hipSuccess) he = hipMemcpyAsync(&bad, A->d_flag, sizeof(int), hipMemcpyDeviceToHost, s);
+            if (rc == QBH_OK && he == hipSuccess) he = hipStreamSynchronize(s);
+            if (rc == QBH_OK && he == hipSuccess) he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+            if (rc != QBH_OK || he != hipSuccess || bad) {
+                (void)hipGetLastError();
+                (void)hipFree(c);
+            } else {
+                K.c8_f = c;
+            }
+        }
+    }
     if (K.c16_n && K.c16_f && A->own_arrays && (K.nnz_x == 0 || K.own_x)) {      // nothing is left in the int32 array
         (void)hipFree(A->d_ja);
         A->d_ja = nullptr;

@@ -259,11 +259,16 @@ int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, Wa
 #endif
 // C16: the part's columns are 2 bytes each (a.ja16), relative to a base named by the block's descriptor (SpmvArgs::ja16): 8 lines
 // of column stream per block instead of 16 -- the passes are bound by line requests, not bytes (DESIGN-history 5.0b)
-template <int TPR, int OPS, bool DYN, bool C16 = false>
+// G8 (sliced far pass with 2-byte columns only): the 8 slots of every line of the stream name the same major index (T (x) 1, verified
+// at conversion) and a.ja8 holds that value once per line -- ONE column load per lane and block (1 line of the 512-slot block's ~140
+// instead of 8), and one register instead of eight carried across the pipeline stage; the per-slot values are formed by cross-lane
+// moves where the gathers are issued.  Gather addresses, and everything behind them, are those of the per-slot stream.
+template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES, (OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES))) void k_spmv_wave2(SpmvArgs a)
 {
     spmv_args_resolve(a);
     static_assert(!C16 || OPS == 1 || OPS == 2 || OPS == 3, "2-byte columns: the one-class near passes and the sliced far pass");
+    static_assert(!G8 || (C16 && OPS == 3), "grouped columns: the sliced far pass with 2-byte columns");
     constexpr int NW = 512, RP = 64 / TPR;
     constexpr bool EPI = OPS == 1 || OPS == 2 || OPS == 4, FAR = OPS == 2 || OPS == 4;      // OPS 1: the fused epilogue WITHOUT a far addend
     // The fused reductions under the ordered dynamic walk: which wavefront takes which chunk depends on the run, so per-wavefront
@@ -372,11 +377,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
         const int nm1 = nn - 1;
         // p0 of the sentinel is nnz: clamp the base so that even an empty block loads inside the arrays
         const int64_t base = b.n > 0 ? b.p0 : 0;
+        if constexpr (G8) {
+            // line l of the block = slots 8 l .. 8 l + 7 (blocks start at multiples of 512 slots and hold a multiple of 8); lane l keeps
+            // line l's value, a line past the block's end reads the last one (what the clamped per-slot loads name there)
+            const int lm = nm1 >> 3;
+            c[0] = ntload(a.ja8 + (base >> 3) + (lane < lm ? lane : lm));
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = lane + u * 64;
-            if constexpr (C16) c[u] = ntload(a.ja16 + base + (i < nn ? i : nm1));
-            else               c[u] = ntload(a.ja + base + (i < nn ? i : nm1)) & a.colmask;
+            for (int u = 1; u < 8; ++u) c[u] = 0;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = lane + u * 64;
+                if constexpr (C16) c[u] = ntload(a.ja16 + base + (i < nn ? i : nm1));
+                else               c[u] = ntload(a.ja + base + (i < nn ? i : nm1)) & a.colmask;
+            }
         }
         // The up to 7 entries in front of the block's first one are the tail of the block BEFORE: their 2-byte columns are relative
         // to THAT block's base, and decoded with this block's they can point up to two major indices ahead -- past the end of x
@@ -559,8 +573,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
         if constexpr (C16) {
             // sliced far part: slot i of a block belongs to far row 8 g + i % 8 (groups and blocks start at multiples of 8 slots)
             const d2 *xq = a.xg + b0.xb + (OPS == 3 ? (lane & 7) : 0);
+            if constexpr (G8) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) xv[u] = xq[OPS == 3 ? (cA[u] << 3) : cA[u]];
+                for (int u = 0; u < 8; ++u) xv[u] = xq[__shfl(cA[0], (lane >> 3) + 8 * u, 64) << 3];      // slot lane + 64 u sits in line lane / 8 + 8 u
+            } else {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) xv[u] = xq[OPS == 3 ? (cA[u] << 3) : cA[u]];
+            }
         } else {
 #pragma unroll
             for (int u = 0; u < 8; ++u) xv[u] = a.xg[cA[u]];
@@ -724,19 +743,20 @@ int64_t wave2_chunk_slots(int64_t n_wb)
 }
 
 // instance table of k_spmv_wave2: every tpr other than 2 and 4 takes the 8 form, every pass form other than 0, 1, 3 and 4 is 2;
-// 2-byte columns (c16) exist for the one-class near passes and the sliced far pass only
-template <int OPS, bool C16>
+// 2-byte columns (c16) exist for the one-class near passes and the sliced far pass only, grouped ones (g8) for the latter only
+template <int OPS, bool C16, bool G8 = false>
 static SpmvKernel wave2_kernel_tpr(int tpr, bool dyn)
 {
     switch (tpr) {
-    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16> : k_spmv_wave2<2, OPS, false, C16>;
-    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16> : k_spmv_wave2<4, OPS, false, C16>;
-    default: return dyn ? k_spmv_wave2<8, OPS, true, C16> : k_spmv_wave2<8, OPS, false, C16>;
+    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8> : k_spmv_wave2<2, OPS, false, C16, G8>;
+    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8> : k_spmv_wave2<4, OPS, false, C16, G8>;
+    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8> : k_spmv_wave2<8, OPS, false, C16, G8>;
     }
 }
 
-static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16)
+static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8)
 {
+    if (g8) return (c16 && ops == 3) ? wave2_kernel_tpr<3, true, true>(tpr, dyn) : nullptr;
     if (c16) {
         switch (ops) {
         case 1:  return wave2_kernel_tpr<1, true>(tpr, dyn);
@@ -762,9 +782,9 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
         set_error("launch_spmv_wave2: the dynamic walk of an epilogue pass needs its chunk-partial slots");
         return QBH_EINVAL;
     }
-    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr);
+    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr);
     if (k == nullptr) {
-        set_error("launch_spmv_wave2: 2-byte columns with pass form %d", ops);
+        set_error("launch_spmv_wave2: 2-byte%s columns with pass form %d", a.ja8 ? " grouped" : "", ops);
         return QBH_EINVAL;
     }
     return launch_kernel(k, grid, kBlock, s, a);
@@ -773,7 +793,7 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
 // asks about the ordered dynamic walk with int32 columns (DYN = true, C16 = false) whatever the launch will use: kept as found
 int wave2_kernel_occupancy(int tpr, int ops)
 {
-    return kernel_occupancy(wave2_kernel(tpr, ops, true, false));
+    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false));
 }
 
 }  // namespace qbh
