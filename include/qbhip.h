@@ -896,6 +896,28 @@ int qbh_gen_kondo_repr_cuts(qbh_csr **out, int n_sites, int n_elec, int two_sz,
                             int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy,
                             int n_trans, const int32_t *perms, const double *chars, double fake_pos,
                             int shard, int n_shards, const int64_t *row_cuts, int64_t *dim_out, const qbh_opts *opts);
+/* The sector operator of qbh_gen_kondo_repr applied from its basis without a stored matrix: arguments, terms, basis (all
+ * orbit representatives ascending, zero-norm representatives kept as decoupled fake rows), entry formula, error codes and
+ * the order of the checks are those of qbh_gen_kondo_repr, and all of them run before the device is looked for.  The one
+ * difference: no row is staged, so the refusal of more than 160 entries in the worst row does not apply.  What is held is 9 B
+ * per representative, the directory of the enumeration (8 B per 4096 words) and the tables; below 2^31 representatives
+ * remain.  Rows [row_begin, row_end) of the sector (row_end = -1: to the end); a range that cannot lie in the sector is
+ * QBH_EINVAL, before the device is looked for where the number of words already excludes it, else after the enumeration, with
+ * *dim_out (may be NULL) set to the sector dimension.
+ * The handle behaves like that of qbh_mf_qudit_repr: SpMV with its fused epilogue and reductions, qbh_multmv(2), every
+ * solver, qbh_csr_set_comm on row shards; qbh_csr_download returns QBH_EUNSUPP.  qbh_csr_get_info reports kernel =
+ * QBH_KERNEL_MATRIX_FREE, bytes_matrix = tables + representatives + info bytes + directory, and nnz = the number of
+ * contributions the kernel applies for these rows: one diagonal per row plus every off-diagonal term entry whose target has
+ * nonzero norm, counted BEFORE duplicates merge (an upper bound on what qbh_gen_kondo_repr stores for the same rows).  The
+ * real fast path and the packed-real drivers apply when every merged hop amplitude has a zero imaginary part and every
+ * character is real (k = 0 and k = pi among them; an imaginary part below 1e-13 is the rounding of sin(pi t) and is dropped).
+ * A row shard computes its rows bit for bit as the whole operator does: the summation order inside a row is the term order. */
+int qbh_mf_kondo_repr(qbh_csr **out, int n_sites, int n_elec, int two_sz,
+                      int n_terms, const int32_t *term_sites, const qbh_z *amp_up, const qbh_z *amp_dn, double U,
+                      const double *kz, const double *kxy,
+                      int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy,
+                      int n_trans, const int32_t *perms, const double *chars, double fake_pos,
+                      int64_t row_begin, int64_t row_end, int64_t *dim_out, const qbh_opts *opts);
 /* moprXvec_repr (src/model.cc:1715-1846, diagonal branch) between two momentum sectors of qbh_gen_kondo_repr with the same
  * (n_elec, two_sz) for O = sum_s ( coef_up[s] n_{s,up} + coef_dn[s] n_{s,dn} + coef_spin[s] S^z_s ): the density N_q and the
  * S^z_q of the electrons and of the local spins.  Contract of qbh_mopr_diag_hubrepr_dev: the three coefficient sets transform

@@ -729,6 +729,8 @@ extern "C" void qbh_csr_destroy(qbh_csr *A)
     if (A->kind == 5) (void)hipFree(A->mfk.K);
     if (A->kind == 6)
         for (int k = 0; k < A->mfqr.n_own; ++k) (void)hipFree(A->mfqr.own[k]);
+    if (A->kind == 7)
+        for (int k = 0; k < A->mfkr.n_own; ++k) (void)hipFree(A->mfkr.own[k]);
     if (A->ev2) (void)hipEventDestroy(A->ev2);
     if (A->ev3) (void)hipEventDestroy(A->ev3);
     for (auto &o : A->ev_old)
@@ -956,7 +958,7 @@ static int adopt_mf_rows(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t ro
     return QBH_OK;
 }
 
-// In the five below the handle owns the tables once the call succeeds; on failure the caller still does.
+// In the six below the handle owns the tables once the call succeeds; on failure the caller still does.
 int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                           int64_t nnz_equiv, const qbh_opts *opts)
 {
@@ -1002,6 +1004,15 @@ int qbh::adopt_mf_qudit_repr(qbh_csr **out, const qbh::MfQuditRepr &t, bool valu
     return QBH_OK;
 }
 
+int qbh::adopt_mf_kondo_repr(qbh_csr **out, const qbh::MfKondoRepr &t, bool values_real, int64_t nrows, int64_t ncols,
+                             int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts)
+{
+    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
+    (*out)->kind = 7;
+    (*out)->mfkr = t;
+    return QBH_OK;
+}
+
 extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
 {
     if (!A || !info) return QBH_EINVAL;
@@ -1022,6 +1033,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
     if (A->kind == 4) info->bytes_matrix = A->mfq.bytes;
     if (A->kind == 5) info->bytes_matrix = A->mfk.bytes;
     if (A->kind == 6) info->bytes_matrix = A->mfqr.bytes;
+    if (A->kind == 7) info->bytes_matrix = A->mfkr.bytes;
     if (A->kind == 3 && A->mfsec) {
         const qbh::MfSec &m = *A->mfsec;
         info->bytes_matrix = m.n_blocks * (int64_t)sizeof(qbh::MfSecBlock) + m.n_items * 8 + m.n_rrows * 12 + m.rnnz * 20 +

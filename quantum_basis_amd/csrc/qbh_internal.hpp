@@ -733,6 +733,34 @@ struct MfQuditReprArgs {
 int launch_mf_qudit_repr(const MfQuditReprArgs &a, hipStream_t s, int *nparts_out);
 int adopt_mf_qudit_repr(qbh_csr **out, const MfQuditRepr &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
                         int64_t nnz_equiv, const qbh_opts *opts);
+// matrix-free momentum sector of the Kondo lattice, basis and rows of qbh_gen_kondo_repr (qbh_sector_mf_kondo.hip): the row's
+// representative and info byte are read, its terms walked by kd_row_terms as kondo_row walks them (qbh_sector.hpp), every
+// target word canonicalised with the translation tables and found through the directory of the enumeration (kd_rank).
+struct MfKondoRepr {
+    const void     *R = nullptr;         // device copy of KondoReprDev: shape, counting tables, terms, characters, permutations
+    const uint64_t *tab = nullptr;       // [n_tab] byte-sliced translation tables (sector_symmetry)
+    const uint64_t *reps = nullptr;      // [dim] representatives, ascending
+    const uint8_t  *info = nullptr;      // [dim] |S| | zero-norm << 7
+    const int64_t  *chunk_pos = nullptr; // [nchunks + 1] directory: first representative of every 4096 ranks
+    int64_t   dim = 0;
+    int       n_tab = 0;
+    int       n_own = 0;
+    void     *own[8] = {};               // every device array above: freed with the handle
+    int64_t   bytes = 0;                 // tables + representatives + info bytes + directory
+};
+struct MfKondoReprArgs {
+    MfKondoRepr t;
+    int64_t row_begin, nrows;
+    const d2 *xg, *xl;
+    const double *xr;
+    d2 *y;
+    double alpha, beta, gamma;
+    double *partials;
+    double *y_re;
+};
+int launch_mf_kondo_repr(const MfKondoReprArgs &a, hipStream_t s, int *nparts_out);
+int adopt_mf_kondo_repr(qbh_csr **out, const MfKondoRepr &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
+                        int64_t nnz_equiv, const qbh_opts *opts);
 // adopt a matrix-free operator (tables already in HBM) behind a qbh_csr handle (qbh_api.cpp)
 int adopt_mf_hubbard(qbh_csr **out, const MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
                      int64_t nnz_equiv, const qbh_opts *opts);
@@ -880,7 +908,7 @@ struct qbh_csr {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     // matrix-free operator (kind 1) instead of CSR arrays (kind 0)
-    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites | 5 matrix-free Kondo lattice | 6 matrix-free d-level momentum sector
+    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites | 5 matrix-free Kondo lattice | 6 matrix-free d-level momentum sector | 7 matrix-free Kondo momentum sector
     qbh::MfSec *mfsec = nullptr;    // kind 3: block tables + compact remainder (host copy of the descriptor, device arrays)
     qbh::MfSec *d_mfsec = nullptr;   // its device copy (kernel argument)
     qbh::MfHubbard mf;
@@ -888,6 +916,7 @@ struct qbh_csr {
     qbh::MfQudit   mfq;
     qbh::MfKondo   mfk;
     qbh::MfQuditRepr mfqr;
+    qbh::MfKondoRepr mfkr;
 
     // split shard: the arrays above hold the locally-owned columns, `rem` the remote ones
     bool     has_rem = false;

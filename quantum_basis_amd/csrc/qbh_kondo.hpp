@@ -1,5 +1,6 @@
 // qbh_kondo.hpp -- what the Kondo-lattice generators share: the word packing, the ranking and the terms of one row, used by
-// qbh_kondo.hip (the full sector, qbh_gen_kondo and qbh_mf_kondo) and by the momentum sectors in qbh_sector.hpp / qbh_sector.hip (qbh_gen_kondo_repr).
+// qbh_kondo.hip (the full sector, qbh_gen_kondo and qbh_mf_kondo) and by the momentum sectors in qbh_sector.hpp / qbh_sector.hip
+// (qbh_gen_kondo_repr) and qbh_sector_mf_kondo.hip (qbh_mf_kondo_repr, which also finds a word's place in the basis from kd_rank).
 //
 // A site carries a conduction-electron orbital and a localized spin-1/2.  A word is three n-bit fields
 //     w = u | d << n | s << 2n      u, d: sites occupied by an up / down electron;  s: sites whose local spin is DOWN

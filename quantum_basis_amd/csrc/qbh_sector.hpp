@@ -1,7 +1,7 @@
 // qbh_sector.hpp -- the momentum-sector toolkit: the symmetry tables, the enumeration of orbit representatives, the row
 // helpers and the four families (spin-1/2, Hubbard / t-J, d-level sites, Kondo lattice) with their row functions.  Used by
 // the stored sector generators (qbh_sector.hip), the operators between sectors (qbh_sector_mopr.hip) and the matrix-free
-// sectors (Hubbard: qbh_sector_mf.hip, d-level sites: qbh_sector_mf_qudit.hip).  Internal linkage: each translation unit instantiates the kernels it uses.
+// sectors (Hubbard: qbh_sector_mf.hip, d-level sites: qbh_sector_mf_qudit.hip, Kondo lattice: qbh_sector_mf_kondo.hip).  Internal linkage: each translation unit instantiates the kernels it uses.
 #pragma once
 #include "qbh_gen_util.hpp"
 #include "qbh_dict.hpp"
@@ -615,6 +615,17 @@ __device__ __forceinline__ int sector_parity(const KondoReprDev &R, int g, uint6
     return kondo_parity(R, g, w & m) ^ kondo_parity(R, g, (w >> R.k.n_sites) & m);
 }
 
+// the entry of a row with |S_a| = sa from the code of kd_row_terms, when translation g with sign parity pt carries the target
+// to a representative with info byte cj: <a|H|c> sigma(g*) conj(chi(g*)) sqrt(|S_b|/|S_a|).  The one expression of the stored
+// rows (kondo_row) and of the matrix-free apply (qbh_sector_mf_kondo.hip).
+__device__ __forceinline__ d2 kondo_repr_value(const KondoReprDev &R, int code, int g, int pt, uint8_t cj, double sa)
+{
+    const double f = (pt ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
+    const d2 h = kd_value(R.k, code);
+    const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];
+    return d2{h.x * cr - h.y * cim, h.x * cim + h.y * cr};
+}
+
 // one row of the sector operator into (cols, vals), columns ascending, duplicates merged; returns its length
 __device__ int kondo_row(const KondoReprDev &R, const uint64_t *tab, const uint64_t *reps, const uint8_t *info, int64_t dim, int64_t i,
                          int32_t *cols, d2 *vals)
@@ -636,11 +647,7 @@ __device__ int kondo_row(const KondoReprDev &R, const uint64_t *tab, const uint6
         const int64_t lo = sector_find(reps, dim, b);
         const uint8_t cj = info[lo];
         if (cj & 0x80) return;            // zero-norm target: dropped
-        const double f = (pt ? -1.0 : 1.0) * sqrt((double)(cj & 0x7f) / sa);
-        const d2 h = kd_value(R.k, code);
-        const double cr = f * R.chr[2 * g], cim = -f * R.chr[2 * g + 1];          // sigma(g*) conj(chi(g*)) sqrt(|S_b|/|S_a|)
-        const d2 v = {h.x * cr - h.y * cim, h.x * cim + h.y * cr};
-        row_add(cols, vals, n, kKondoMaxRow, i, lo, v, off);
+        row_add(cols, vals, n, kKondoMaxRow, i, lo, kondo_repr_value(R, code, g, pt, cj, sa), off);
     });
     return row_finish(cols, vals, n, dg0 + off);
 }

@@ -1,0 +1,341 @@
+// qbh_sector_mf_kondo.hip -- qbh_mf_kondo_repr (toolkit and the Kondo family: qbh_sector.hpp; words, ranking, terms: qbh_kondo.hpp)
+//
+// The sector operator of qbh_gen_kondo_repr applied from its basis, without a stored matrix (MfKondoRepr in qbh_internal.hpp).
+// What stays in HBM is the representative list (8 B per row), one info byte per row, the directory of the enumeration (8 B per
+// 4096 words) and the tables: no row pointers, no columns, no values.  One lane handles one representative row and follows
+// kondo_row up to the point where that would call row_add: it splits the word into (u, d, s), walks kd_row_terms in its own
+// order, and for each emitted (u', d', s', code) forms the word c, canonicalises it with the byte-sliced translation tables
+// (sector_canonical: n_trans x 3 fields x n_chunks table reads), takes the fermion sign of the translation only when it is
+// not the identity, finds the position of the representative b and accumulates kondo_repr_value x[b] as the entries arrive.
+// An entry that returns to the row's own orbit simply adds to x[i].  Nothing is staged per row, so the limit of 160 entries
+// per row of the stored form does not apply, and the order of the sums of a row does not depend on which rows the launch
+// covers: a row shard is bit-identical to the same rows of the whole operator.
+//
+// The position of b is not looked up in the whole list: kd_rank(b) >> 12 (the inverse of the enumeration's kd_unrank;
+// ascending words are ascending ranks) names the chunk of 4096 words that holds b, the directory gives the positions of that
+// chunk's first and last representatives, and a bisection of at most 12 steps inside those (at most 32 KB, contiguous) ends at
+// what sector_find returns from 31 steps over the whole list.
+//
+// The translation tables and the two counting tables A and binom of KondoDev are always staged in LDS: with at most 21 sites
+// (4 six-bit chunks per field) and 64 translations they take at most 138,816 B.  The term arrays, the characters and the
+// permutations are read through the device copy of KondoReprDev (uniform over the lanes, cached).
+#include "qbh_sector.hpp"
+
+namespace qbh {
+namespace {
+
+static_assert(kSectorChunk == 1 << 12, "krepr_find shifts a rank by 12 bits to its chunk");
+constexpr int kKondoTabEntries = kKondoTab * kKondoTab;
+constexpr size_t kMfKreprLdsCap = (size_t)150 * 1024;         // the budget of launch_mf_heis
+constexpr size_t kMfKreprLdsMax =
+    ((size_t)kReprMaxTrans * ((kKondoMaxSites + 5) / 6) * 64 + 2 * (size_t)kKondoTabEntries) * sizeof(uint64_t);
+static_assert(kMfKreprLdsMax == 138816 && kMfKreprLdsMax <= kMfKreprLdsCap,
+              "the translation tables, A and binom of every admissible sector fit LDS: there is no global-memory path");
+
+// Two workgroup shapes for one kernel body.  The compiler reports 85 VGPRs for every instance of the apply kernel (88
+// allocated: 5 waves per SIMD, 20 per CU) and 0 bytes of scratch, so a CU holds at most five workgroups of 256 lanes or one
+// of 1024, and the LDS the tables take (160 KB per CU) decides between them:
+//   four or more workgroups of 256 lanes fit:  256 lanes, min(5, 160 KB / footprint) per CU: 16 or 20 waves per CU
+//   fewer fit (footprint above 40 KB):         1024 lanes, one workgroup per CU: 16 waves per CU instead of 4 to 12
+constexpr int kMfKreprBlockS = 256, kMfKreprBlockL = 1024;
+constexpr int kMfKreprPerCuS = 5;                             // VGPR-limited workgroups of 256 lanes per CU
+constexpr size_t kMfKreprLdsCu = (size_t)160 * 1024;
+constexpr size_t kMfKreprLdsStatic = 1024;                    // the reduction scratch of a workgroup and allocation granules
+
+inline size_t mf_krepr_lds_bytes(const MfKondoRepr &t) { return ((size_t)t.n_tab + 2 * (size_t)kKondoTabEntries) * sizeof(uint64_t); }
+inline int mf_krepr_fit(const MfKondoRepr &t) { return (int)(kMfKreprLdsCu / (mf_krepr_lds_bytes(t) + kMfKreprLdsStatic)); }
+inline bool mf_krepr_large(const MfKondoRepr &t) { return mf_krepr_fit(t) < 4; }
+
+// the resident grid of both kernels
+inline int mf_krepr_grid(const MfKondoRepr &t, int64_t nrows)
+{
+    const bool large = mf_krepr_large(t);
+    const int block = large ? kMfKreprBlockL : kMfKreprBlockS;
+    const int per_cu = large ? 1 : std::min(kMfKreprPerCuS, mf_krepr_fit(t));
+    const int64_t nblk = (nrows + block - 1) / block;
+    return (int)std::min<int64_t>(nblk, std::min<int64_t>((int64_t)device_cu_count() * per_cu, kMaxRedBlocks));
+}
+
+// tab | A | binom into LDS and the pointers the row walk reads them through
+__device__ __forceinline__ void krepr_stage(const MfKondoRepr &t, const KondoReprDev &R, uint64_t *lds, int nthreads, const uint64_t *&tab,
+                                            const uint64_t *&A, const uint64_t *&binom)
+{
+    for (int k = threadIdx.x; k < t.n_tab; k += nthreads) lds[k] = t.tab[k];
+    for (int k = threadIdx.x; k < kKondoTabEntries; k += nthreads) {
+        lds[t.n_tab + k] = R.k.A[k];
+        lds[t.n_tab + kKondoTabEntries + k] = R.k.binom[k];
+    }
+    __syncthreads();
+    tab = lds;
+    A = lds + t.n_tab;
+    binom = A + kKondoTabEntries;
+}
+
+// position of representative b = (u, d, s) in reps[0, dim): the directory entry of its chunk of ranks, then a bisection
+// among that chunk's representatives.  b is a representative, so this is sector_find(reps, dim, b); the result stays below
+// dim for any word.
+__device__ __forceinline__ int64_t krepr_find(const KondoDev &K, const uint64_t *A, const uint64_t *binom, const uint64_t *reps,
+                                              const int64_t *chunk_pos, int64_t dim, uint64_t b)
+{
+    const int nb = K.n_sites;
+    const uint64_t mlow = (1ULL << nb) - 1ULL;
+    const uint64_t c = kd_rank(K, A, binom, b & mlow, (b >> nb) & mlow, b >> (2 * nb)) >> 12;
+    int64_t lo = chunk_pos[c], hi = chunk_pos[c + 1];
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (reps[mid] < b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < dim ? lo : dim - 1;
+}
+
+// the terms of the row of representative a (|S_a| = sa, nonzero norm) in the order of kondo_row: sink(position of b, value)
+// for every off-diagonal term entry whose target has nonzero norm; returns the diagonal of the row's own word
+template <class Sink>
+__device__ __forceinline__ d2 krepr_walk(const KondoReprDev &R, const uint64_t *tab, const uint64_t *A, const uint64_t *binom,
+                                         const uint64_t *reps, const uint8_t *info, const int64_t *chunk_pos, int64_t dim, uint64_t a,
+                                         double sa, Sink sink)
+{
+    const int nb = R.k.n_sites;
+    const uint64_t mlow = (1ULL << nb) - 1ULL;
+    return kd_row_terms(R.k, a & mlow, (a >> nb) & mlow, a >> (2 * nb), [&](uint64_t u2, uint64_t d2w, uint64_t s2, int code) {
+        const uint64_t c = u2 | (d2w << nb) | (s2 << (2 * nb));
+        int g = 0;
+        const uint64_t b = sector_canonical(R, tab, c, &g);
+        const int pt = g ? sector_parity(R, g, c) : 0;
+        const int64_t lo = krepr_find(R.k, A, binom, reps, chunk_pos, dim, b);
+        const uint8_t cj = info[lo];
+        if (cj & 0x80) return;            // zero-norm target: dropped
+        sink(lo, kondo_repr_value(R, code, g, pt, cj, sa));
+    });
+}
+
+__device__ __forceinline__ double krepr_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// y <- alpha H x + beta y + gamma x on rows [row_begin, row_begin + nrows) of the sector: one lane per row, grid-stride over
+// a resident grid, every row gathers (no atomics).  Epilogue and partial sums as k_mf_qudit_repr.
+template <bool REALX, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr(MfKondoReprArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t kr_lds[];
+    __shared__ double red[3 * (BLOCK / 64)];
+    const MfKondoRepr &t = a.t;
+    const KondoReprDev &R = *static_cast<const KondoReprDev *>(t.R);
+    const int tid = threadIdx.x;
+    const uint64_t *tab, *A, *binom;
+    krepr_stage(t, R, kr_lds, BLOCK, tab, A, binom);
+    double acc[3] = {0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t lrow = (int64_t)blockIdx.x * BLOCK + tid; lrow < a.nrows; lrow += stride) {
+        const int64_t grow = a.row_begin + lrow;
+        const uint8_t ci = t.info[grow];
+        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
+        if (a.y_re != nullptr) {
+            if (a.beta != 0.0) yo.x = a.y_re[lrow];
+            xi.x = a.xr[grow];
+        } else {
+            if (a.beta != 0.0) yo = a.y[lrow];
+            if (REALX) xi.x = a.xr[grow];
+            else       xi = a.xg[grow];
+        }
+        d2 sum = {0.0, 0.0};
+        d2 dg;
+        if (ci & 0x80) {                  // zero norm at this momentum: the decoupled row of row_zero_norm
+            dg = d2{R.fake_pos + (double)grow / (double)t.dim, 0.0};
+        } else {
+            dg = krepr_walk(R, tab, A, binom, t.reps, t.info, t.chunk_pos, t.dim, t.reps[grow], (double)(ci & 0x7f), [&](int64_t lo, d2 v) {
+                if (REALX) {
+                    sum.x += v.x * a.xr[lo];
+                } else {
+                    const d2 x = a.xg[lo];
+                    sum.x += v.x * x.x - v.y * x.y;
+                    sum.y += v.x * x.y + v.y * x.x;
+                }
+            });
+        }
+        sum += dg.x * xi;                 // the diagonal of a word is real by construction (kondo_setup drops Im of a number term)
+        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
+        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
+        else                   a.y[lrow] = yn;
+        acc[0] += xi.x * yn.x + xi.y * yn.y;
+        acc[1] += xi.x * yn.y - xi.y * yn.x;
+        acc[2] += yn.x * yn.x + yn.y * yn.y;
+    }
+    if (a.partials != nullptr) {
+        const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = krepr_wave_sum(acc[c]);
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) red[c * (BLOCK / 64) + wave] = acc[c];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int c = 0; c < 3; ++c) {
+                double v = 0.0;
+                for (int w2 = 0; w2 < BLOCK / 64; ++w2) v += red[c * (BLOCK / 64) + w2];
+                a.partials[(size_t)blockIdx.x * 3 + c] = v;
+            }
+        }
+    }
+}
+
+// the contributions the apply kernel makes for rows [row_begin, row_end): one diagonal per row and every off-diagonal term
+// entry whose target has nonzero norm, before duplicates merge.  One sum per workgroup.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr_count(MfKondoRepr t, int64_t row_begin, int64_t row_end, unsigned long long *part)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t kr_lds[];
+    __shared__ unsigned long long red[BLOCK / 64];
+    const KondoReprDev &R = *static_cast<const KondoReprDev *>(t.R);
+    const uint64_t *tab, *A, *binom;
+    krepr_stage(t, R, kr_lds, BLOCK, tab, A, binom);
+    unsigned long long c = 0;
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t row = row_begin + (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < row_end; row += stride) {
+        const uint8_t ci = t.info[row];
+        c += 1;
+        if (!(ci & 0x80))
+            (void)krepr_walk(R, tab, A, binom, t.reps, t.info, t.chunk_pos, t.dim, t.reps[row], (double)(ci & 0x7f),
+                             [&](int64_t, d2) { c += 1; });
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long v = 0;
+        for (int w = 0; w < BLOCK / 64; ++w) v += red[w];
+        part[blockIdx.x] = v;
+    }
+}
+
+template <class Kernel, class... Args>
+hipError_t krepr_launch(Kernel k, int grid, int block, size_t lds, hipStream_t s, Args... args)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, args...);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+int launch_mf_kondo_repr(const MfKondoReprArgs &a, hipStream_t s, int *nparts_out)
+{
+    const size_t lds = mf_krepr_lds_bytes(a.t);
+    const int g = mf_krepr_grid(a.t, a.nrows);
+    const bool rx = a.xr != nullptr;
+    if (mf_krepr_large(a.t)) {
+        if (rx) QBH_HIP(krepr_launch(k_mf_kondo_repr<true, kMfKreprBlockL>, g, kMfKreprBlockL, lds, s, a));
+        else    QBH_HIP(krepr_launch(k_mf_kondo_repr<false, kMfKreprBlockL>, g, kMfKreprBlockL, lds, s, a));
+    } else {
+        if (rx) QBH_HIP(krepr_launch(k_mf_kondo_repr<true, kMfKreprBlockS>, g, kMfKreprBlockS, lds, s, a));
+        else    QBH_HIP(krepr_launch(k_mf_kondo_repr<false, kMfKreprBlockS>, g, kMfKreprBlockS, lds, s, a));
+    }
+    if (nparts_out) *nparts_out = g;
+    return QBH_OK;
+}
+
+}  // namespace qbh
+
+extern "C" int qbh_mf_kondo_repr(qbh_csr **out, int n_sites, int n_elec, int two_sz, int n_terms, const int32_t *term_sites,
+                                 const qbh_z *amp_up, const qbh_z *amp_dn, double U, const double *kz, const double *kxy,
+                                 int n_sbonds, const int32_t *sbond_sites, const double *bz, const double *bxy, int n_trans,
+                                 const int32_t *perms, const double *chars, double fake_pos, int64_t row_begin, int64_t row_end,
+                                 int64_t *dim_out, const qbh_opts *opts)
+{
+    using namespace qbh;
+    const char *who = "qbh_mf_kondo_repr";
+    if (!out) {
+        set_error("%s: out is NULL", who);
+        return QBH_EINVAL;
+    }
+    std::vector<KondoReprDev> rr(1);
+    KondoReprDev &R = rr[0];
+    memset(&R, 0, sizeof(R));
+    const int max_row = kondo_setup(who, n_sites, n_elec, two_sz, n_terms, term_sites, amp_up, amp_dn, U, kz, kxy, n_sbonds,
+                                    sbond_sites, bz, bxy, R.k, true);     // no row is staged: any row length
+    if (max_row <= 0) return max_row;
+    std::vector<uint64_t> tab;
+    QBH_TRY(kondo_symmetry(R, tab, n_trans, perms, chars, who));
+    QBH_TRY(kondo_invariant(who, R.k, n_trans, perms));
+    int64_t nstates = 0;
+    std::vector<uint64_t> ctab;
+    QBH_TRY(sector_words(R, ctab, &nstates, who));
+    // what can be said about the row range before the sector is enumerated: the dimension is at most the number of words
+    if (row_begin < 0 || row_end < -1 || (row_end >= 0 && row_begin >= row_end) || row_begin >= nstates || row_end > nstates) {
+        set_error("%s: bad row range [%lld, %lld) of a sector of %lld words", who, (long long)row_begin, (long long)row_end,
+                  (long long)nstates);
+        return QBH_EINVAL;
+    }
+    if (qbh_device_count() <= 0) {        // every refusal above comes before the device is looked for
+        set_error("no HIP device visible");
+        return QBH_ENODEVICE;
+    }
+    if (opts && opts->device >= 0) QBH_HIP_WHO(who, hipSetDevice(opts->device));
+
+    // real values: every merged hop amplitude real and every character real (kxy, bxy and the diagonal are real by
+    // construction).  A character computed as exp(-i k.t) at k = pi carries sin(pi t), which rounds to at most
+    // 64 pi 2^-53 = 2.2e-14 for the 64 translations allowed: an imaginary part below 1e-13 is that rounding and is dropped,
+    // so that the real and the complex kernel apply the same numbers.
+    bool values_real = true;
+    for (int t = 0; t < R.k.n_terms; ++t)
+        if (R.k.aup[t][1] != 0.0 || R.k.adn[t][1] != 0.0) values_real = false;
+    for (int g = 0; g < n_trans; ++g)
+        if (std::fabs(R.chr[2 * g + 1]) > 1e-13) values_real = false;
+    if (values_real)
+        for (int g = 0; g < n_trans; ++g) R.chr[2 * g + 1] = 0.0;
+
+    R.fake_pos = fake_pos;
+    DevBufs bufs;
+    SectorDev<KondoReprDev> S;
+    int64_t *d_pos = nullptr, nchunks = 0;
+    QBH_TRY(sector_enumerate(R, tab, bufs.pool, S, who, &d_pos, &nchunks));
+    const int64_t dim = S.dim;
+    if (dim_out) *dim_out = dim;
+    if (row_end < 0) row_end = dim;
+    if (row_begin >= row_end || row_end > dim) {
+        set_error("%s: bad row range [%lld, %lld) of %lld", who, (long long)row_begin, (long long)row_end, (long long)dim);
+        return QBH_EINVAL;
+    }
+
+    MfKondoRepr t;
+    t.R = S.R;
+    t.tab = S.tab;
+    t.reps = S.reps;
+    t.info = S.info;
+    t.chunk_pos = d_pos;
+    t.dim = dim;
+    t.n_tab = (int)tab.size();
+    if (mf_krepr_lds_bytes(t) > kMfKreprLdsMax || bufs.pool.size() > sizeof(t.own) / sizeof(t.own[0])) {
+        set_error("%s: internal: %d table words, %d device arrays to hand over", who, t.n_tab, (int)bufs.pool.size());
+        return QBH_EHIP;
+    }
+    for (void *p : bufs.pool) t.own[t.n_own++] = p;
+    t.bytes = (int64_t)(sizeof(KondoReprDev) + tab.size() * 8) + dim * 9 + (nchunks + 1) * 8;
+
+    const int64_t nrows = row_end - row_begin;
+    const int cgrid = mf_krepr_grid(t, nrows);
+    const size_t lds = mf_krepr_lds_bytes(t);
+    unsigned long long *d_part = nullptr;
+    QBH_HIP_WHO(who, qbh::dev_alloc(&d_part, (size_t)cgrid * sizeof(unsigned long long)));
+    hipError_t ce = mf_krepr_large(t)
+                        ? krepr_launch(k_mf_kondo_repr_count<kMfKreprBlockL>, cgrid, kMfKreprBlockL, lds, (hipStream_t)0, t, row_begin, row_end, d_part)
+                        : krepr_launch(k_mf_kondo_repr_count<kMfKreprBlockS>, cgrid, kMfKreprBlockS, lds, (hipStream_t)0, t, row_begin, row_end, d_part);
+    std::vector<unsigned long long> part((size_t)cgrid);
+    if (ce == hipSuccess) ce = hipMemcpy(part.data(), d_part, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_part);
+    QBH_HIP_WHO(who, ce);
+    int64_t nnz = 0;
+    for (unsigned long long v : part) nnz += (int64_t)v;
+
+    const int rc = adopt_mf_kondo_repr(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    if (rc == QBH_OK) bufs.release();     // the handle owns the tables, the representatives and the directory now
+    return rc;
+}

@@ -708,6 +708,21 @@ int spmv_run(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double g
             h.gamma = gamma;
             h.partials = m.partials;
             QBH_TRY(qbh::launch_mf_qudit_repr(h, A->stream, &mf_parts));
+        } else if (A->kind == 7) {
+            qbh::MfKondoReprArgs h{};
+            h.t = A->mfkr;
+            h.row_begin = m.row_begin;
+            h.nrows = m.nrows;
+            h.xg = m.xg;
+            h.xl = m.xl;
+            h.xr = m.xr;
+            h.y = m.y;
+            h.y_re = m.y_re;
+            h.alpha = alpha;
+            h.beta = beta;
+            h.gamma = gamma;
+            h.partials = m.partials;
+            QBH_TRY(qbh::launch_mf_kondo_repr(h, A->stream, &mf_parts));
         } else {
             QBH_TRY(qbh::launch_mf_hubbard(m, A->grid, A->stream, &mf_parts));
         }

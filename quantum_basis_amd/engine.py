@@ -415,10 +415,16 @@ class csr_mat:
 
     @classmethod
     def kondo_repr(cls, n_sites, n_elec, two_sz, bonds, perms, chars, t=1.0, J_K=1.1, J_RKKY=0.0, U=0.0, fake_pos=100.0,
-                   shard=(0, 1), opts=None, row_cuts=None, terms=None):
+                   shard=(0, 1), opts=None, row_cuts=None, terms=None, matrix_free=False, rows=None):
         """The operator of kondo in a momentum sector (qbh_gen_kondo_repr; the reference's
         examples/trans_symmetric/latt_chain/chain_Kondo.cc): perms / chars / fake_pos / shard / row_cuts as in
-        heisenberg_repr.  The terms must be invariant under every translation."""
+        heisenberg_repr.  The terms must be invariant under every translation.
+        matrix_free=True: the same operator applied from its basis without a stored matrix (qbh_mf_kondo_repr; no limit on the
+        entries of a row); rows=(r0, r1) then selects a row block, shard / row_cuts belong to the stored form."""
+        if matrix_free and (tuple(shard) != (0, 1) or row_cuts is not None):
+            raise ValueError("kondo_repr(matrix_free=True) takes rows=(r0, r1), not shard / row_cuts")
+        if rows is not None and not matrix_free:
+            raise ValueError("kondo_repr: rows=(r0, r1) needs matrix_free=True; the stored form takes shard / row_cuts")
         _lib.require_gpu()
         opts = opts if opts is not None else make_opts()
         keep, hop, rest = cls._kondo_args(n_sites, bonds, t, J_K, J_RKKY, terms)
@@ -429,6 +435,12 @@ class csr_mat:
         assert cuts is None or cuts.size == int(shard[1]) + 1
         h = C.c_void_p()
         dim = C.c_int64(0)
+        if matrix_free:
+            r0, r1 = (0, -1) if rows is None else rows
+            check(lib().qbh_mf_kondo_repr(C.byref(h), n_sites, n_elec, two_sz, *hop, float(U), *rest, len(c), _p(p), _p(c),
+                                          fake_pos, C.c_int64(r0), C.c_int64(r1), C.byref(dim), C.byref(opts)),
+                  "qbh_mf_kondo_repr")
+            return cls(0, None, None, None, opts=opts, _handle=h)
         check(lib().qbh_gen_kondo_repr_cuts(C.byref(h), n_sites, n_elec, two_sz, *hop, float(U), *rest, len(c), _p(p), _p(c),
                                             fake_pos, int(shard[0]), int(shard[1]), _p(cuts) if cuts is not None else None,
                                             C.byref(dim), C.byref(opts)), "qbh_gen_kondo_repr")
