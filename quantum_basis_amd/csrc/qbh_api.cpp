@@ -697,40 +697,9 @@ extern "C" void qbh_csr_destroy(qbh_csr *A)
     if (A->basis.d_map) (void)hipFree(A->basis.d_map);
     if (A->basis.d_stage) (void)hipFree(A->basis.d_stage);
     if (A->d_xr) (void)hipFree(A->d_xr);
-    if (A->kind == 1) {
-        (void)hipFree(A->mf.cfg_u);
-        (void)hipFree(A->mf.cfg_d);
-        (void)hipFree(A->mf.tgt_u);
-        (void)hipFree(A->mf.tgt_d);
-        (void)hipFree(A->mf.val_u);
-        (void)hipFree(A->mf.val_d);
-        if (A->mf.pk_d) (void)hipFree(A->mf.pk_d);
-    }
-    if (A->mfsec) {
-        for (void *q : {(void *)A->mfsec->blk, (void *)A->mfsec->hop, (void *)A->mfsec->item, (void *)A->mfsec->ucfg,
-                        (void *)A->mfsec->upell, (void *)A->mfsec->prank, (void *)A->mfsec->oid, (void *)A->mfsec->oek, (void *)A->mfsec->tpar,
-                        (void *)A->mfsec->usgn, (void *)A->mfsec->utab, (void *)A->mfsec->uext, (void *)A->mfsec->rrow, (void *)A->mfsec->ria,
-                        (void *)A->mfsec->rja, (void *)A->mfsec->rval, (void *)A->d_mfsec})
-            if (q) (void)hipFree(q);
-        delete A->mfsec;
-        A->mfsec = nullptr;
-    }
-    if (A->kind == 2) {
-        (void)hipFree(A->mfh.binom);
-        (void)hipFree(A->mfh.chunk);
-        (void)hipFree(A->mfh.mask);
-        (void)hipFree(A->mfh.offd);
-        (void)hipFree(A->mfh.diag);
-    }
-    if (A->kind == 4)
-        for (void *q : {(void *)A->mfq.cum, (void *)A->mfq.pairs, (void *)A->mfq.nrow, (void *)A->mfq.slot, (void *)A->mfq.sdiag,
-                        (void *)A->mfq.pdiag, (void *)A->mfq.eout, (void *)A->mfq.eval})
-            (void)hipFree(q);
-    if (A->kind == 5) (void)hipFree(A->mfk.K);
-    if (A->kind == 6)
-        for (int k = 0; k < A->mfqr.n_own; ++k) (void)hipFree(A->mfqr.own[k]);
-    if (A->kind == 7)
-        for (int k = 0; k < A->mfkr.n_own; ++k) (void)hipFree(A->mfkr.own[k]);
+    for (int k = 0; k < A->n_mf_own; ++k) (void)hipFree(A->mf_own[k]);       // the tables of a matrix-free operator, whatever its kind
+    delete A->mfsec;
+    A->mfsec = nullptr;
     if (A->ev2) (void)hipEventDestroy(A->ev2);
     if (A->ev3) (void)hipEventDestroy(A->ev3);
     for (auto &o : A->ev_old)
@@ -892,44 +861,14 @@ int qbh::adopt_coded_csr(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t ro
     return QBH_OK;
 }
 
-int qbh::adopt_mf_sector(qbh_csr **out, qbh::MfSec *host_tables, qbh::MfSec *dev_tables, int64_t dim, int64_t nnz_equiv,
-                         const qbh_opts *opts)
+int qbh::adopt_mf_handle(qbh_csr **out, int kind, const std::vector<void *> &own, int64_t bytes, bool values_real, int64_t nrows,
+                         int64_t ncols, int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts)
 {
     qbh_csr *A = nullptr;
-    QBH_TRY(new_handle(&A, opts));
-    A->nrows = A->ncols = dim;
-    A->row_offset = 0;
-    A->nnz = A->nnz_total = nnz_equiv;
-    A->kernel = QBH_KERNEL_ROWS;
-    A->values_real = host_tables->all_real;
-    A->n_blocks = (dim + qbh::kBlock - 1) / qbh::kBlock;
-    A->grid = (int)std::min<int64_t>(A->n_blocks, 256 * 8);
-    auto fail = [&](int code) {
-        qbh_csr_destroy(A);
-        return code;
-    };
-    if (qbh::dev_alloc(&A->d_scal, 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
-    if (hipHostMalloc(&A->h_scal, 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
-    if (qbh::dev_alloc(&A->d_flag, sizeof(int)) != hipSuccess) return fail(QBH_ENOMEM);
-    if (hipMemsetAsync(A->d_flag, 0, sizeof(int), A->stream) != hipSuccess) return fail(QBH_EHIP);      // on the handle's stream: the null stream is not ordered with it
-    if (hipEventCreate(&A->ev0) != hipSuccess || hipEventCreate(&A->ev1) != hipSuccess ||
-        hipEventCreate(&A->ev2) != hipSuccess || hipEventCreate(&A->ev3) != hipSuccess)
-        return fail(QBH_EHIP);
-    if (qbh::dev_alloc(&A->d_partials, (size_t)qbh::kMaxRedBlocks * 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
-    A->stats = qbh_stats{};
-    A->stats.ms_spmv_min = std::numeric_limits<double>::infinity();
-    A->kind = 3;                // from here on the handle owns the tables (on any failure above the caller still does)
-    A->mfsec = host_tables;
-    A->d_mfsec = dev_tables;
-    *out = A;
-    return QBH_OK;
-}
-
-// what the row-parallel matrix-free forms share: a handle with workspace and no arrays (the caller sets kind and its tables)
-static int adopt_mf_rows(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t row_offset, int64_t nnz_equiv, bool values_real,
-                         const qbh_opts *opts)
-{
-    qbh_csr *A = nullptr;
+    if (own.size() > sizeof(A->mf_own) / sizeof(A->mf_own[0])) {
+        qbh::set_error("internal: %d device arrays to hand over to a matrix-free operator", (int)own.size());
+        return QBH_EHIP;
+    }
     QBH_TRY(new_handle(&A, opts));
     A->nrows = nrows;
     A->ncols = ncols;
@@ -954,62 +893,27 @@ static int adopt_mf_rows(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t ro
     if (qbh::dev_alloc(&A->d_partials, nparts * 16 * sizeof(double)) != hipSuccess) return fail(QBH_ENOMEM);
     A->stats = qbh_stats{};
     A->stats.ms_spmv_min = std::numeric_limits<double>::infinity();
+    A->kind = kind;             // from here on the handle owns the tables (on any failure above the caller still does)
+    for (void *q : own) A->mf_own[A->n_mf_own++] = q;
+    A->mf_bytes = bytes;
     *out = A;
     return QBH_OK;
 }
 
-// In the six below the handle owns the tables once the call succeeds; on failure the caller still does.
-int qbh::adopt_mf_hubbard(qbh_csr **out, const qbh::MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
-                          int64_t nnz_equiv, const qbh_opts *opts)
+// kind 3: the host copy of the descriptor names the device arrays; it is deleted with the handle
+int qbh::adopt_mf_sector(qbh_csr **out, qbh::MfSec *host_tables, qbh::MfSec *dev_tables, int64_t dim, int64_t nnz_equiv,
+                         const qbh_opts *opts)
 {
-    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, true, opts));      // t and U are real
-    (*out)->kind = 1;
-    (*out)->mf = t;
-    return QBH_OK;
-}
-
-int qbh::adopt_mf_heis(qbh_csr **out, const qbh::MfHeis &t, int64_t nrows, int64_t ncols, int64_t row_offset,
-                          int64_t nnz_equiv, const qbh_opts *opts)
-{
-    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, true, opts));      // J is real
-    (*out)->kind = 2;
-    (*out)->mfh = t;
-    return QBH_OK;
-}
-
-int qbh::adopt_mf_qudit(qbh_csr **out, const qbh::MfQudit &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
-                        int64_t nnz_equiv, const qbh_opts *opts)
-{
-    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
-    (*out)->kind = 4;
-    (*out)->mfq = t;
-    return QBH_OK;
-}
-
-int qbh::adopt_mf_kondo(qbh_csr **out, const qbh::MfKondo &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
-                        int64_t nnz_equiv, const qbh_opts *opts)
-{
-    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
-    (*out)->kind = 5;
-    (*out)->mfk = t;
-    return QBH_OK;
-}
-
-int qbh::adopt_mf_qudit_repr(qbh_csr **out, const qbh::MfQuditRepr &t, bool values_real, int64_t nrows, int64_t ncols,
-                             int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts)
-{
-    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
-    (*out)->kind = 6;
-    (*out)->mfqr = t;
-    return QBH_OK;
-}
-
-int qbh::adopt_mf_kondo_repr(qbh_csr **out, const qbh::MfKondoRepr &t, bool values_real, int64_t nrows, int64_t ncols,
-                             int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts)
-{
-    QBH_TRY(adopt_mf_rows(out, nrows, ncols, row_offset, nnz_equiv, values_real, opts));
-    (*out)->kind = 7;
-    (*out)->mfkr = t;
+    const qbh::MfSec &m = *host_tables;
+    std::vector<void *> own;
+    for (void *q : {(void *)m.blk, (void *)m.hop, (void *)m.item, (void *)m.ucfg, (void *)m.upell, (void *)m.prank, (void *)m.oid, (void *)m.oek,
+                    (void *)m.tpar, (void *)m.usgn, (void *)m.utab, (void *)m.uext, (void *)m.rrow, (void *)m.ria, (void *)m.rja, (void *)m.rval,
+                    (void *)dev_tables})
+        if (q) own.push_back(q);
+    const int64_t bytes = m.n_blocks * (int64_t)sizeof(qbh::MfSecBlock) + m.n_items * 8 + m.n_rrows * 12 + m.rnnz * 20 +
+                          (m.orbit ? m.cu * 26 + m.n_orb * m.w_orb * 6 : m.cu * 4 * (1 + m.w_up + m.n_trans));
+    QBH_TRY(adopt_mf(out, 3, &qbh_csr::mfsec, host_tables, own, bytes, m.all_real, dim, dim, 0, nnz_equiv, opts));
+    (*out)->d_mfsec = dev_tables;
     return QBH_OK;
 }
 
@@ -1025,20 +929,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
     info->bytes_matrix = (A->nrows + 1) * 8 * (A->has_rem ? 2 : 1) + nnz * 4 + (A->d_code ? nnz + 256 * 16 : nnz * 16) +
                          (nb + 2) * 12;
     info->bytes_algorithmic = nnz * 20 + (A->nrows + 1) * 8 + A->nrows * 32;
-    if (A->kind == 1)
-        info->bytes_matrix = (A->mf.Nu * A->mf.wu + A->mf.Nd * A->mf.wd) * 5 + A->mf.Nd * A->mf.wd * 4 + (A->mf.Nu + A->mf.Nd) * 4;
-    if (A->kind == 2)
-        info->bytes_matrix = ((int64_t)(A->mfh.n_sites + 1) * (A->mfh.n_dn + 1) + (int64_t)A->mfh.n_chunks * (A->mfh.n_dn + 1) * 64 +
-                              3 * (int64_t)A->mfh.n_bonds) * 8;
-    if (A->kind == 4) info->bytes_matrix = A->mfq.bytes;
-    if (A->kind == 5) info->bytes_matrix = A->mfk.bytes;
-    if (A->kind == 6) info->bytes_matrix = A->mfqr.bytes;
-    if (A->kind == 7) info->bytes_matrix = A->mfkr.bytes;
-    if (A->kind == 3 && A->mfsec) {
-        const qbh::MfSec &m = *A->mfsec;
-        info->bytes_matrix = m.n_blocks * (int64_t)sizeof(qbh::MfSecBlock) + m.n_items * 8 + m.n_rrows * 12 + m.rnnz * 20 +
-                             (m.orbit ? m.cu * 26 + m.n_orb * m.w_orb * 6 : m.cu * 4 * (1 + m.w_up + m.n_trans));
-    }
+    if (A->kind != 0) info->bytes_matrix = A->mf_bytes;
     info->kernel = A->kind != 0 ? QBH_KERNEL_MATRIX_FREE : A->use_wave ? QBH_KERNEL_WAVE : A->kernel;
     info->value_dict = A->d_code ? A->n_dict : 0;
     info->device = A->device;

@@ -447,9 +447,11 @@ extern "C" int qbh_mf_hubbard(qbh_csr **out, int n_sites, int n_up, int n_dn, in
     m.Nu = Nu;
     m.Nd = Nd;
     m.U = U;
-    auto free_tables = [&]() {
+    auto tables = [&]() {                    // the device arrays placed so far
+        std::vector<void *> own;
         for (void *q : {(void *)m.cfg_u, (void *)m.cfg_d, (void *)m.tgt_u, (void *)m.tgt_d, (void *)m.val_u, (void *)m.val_d, (void *)m.pk_d})
-            if (q) (void)hipFree(q);
+            if (q) own.push_back(q);
+        return own;
     };
     auto build = [&]() -> int {
     QBH_HIP(qbh::dev_alloc(&m.cfg_u, (size_t)Nu * sizeof(uint32_t)));
@@ -479,8 +481,11 @@ extern "C" int qbh_mf_hubbard(qbh_csr **out, int n_sites, int n_up, int n_dn, in
     return QBH_OK;
     };
     int rc = build();
-    if (rc == QBH_OK) rc = adopt_mf_hubbard(out, m, row_end - row_begin, dim, row_begin, rowptr(row_end) - rowptr(row_begin), opts);
-    if (rc != QBH_OK) free_tables();         // the handle takes the tables only when adoption succeeds
+    if (rc == QBH_OK)                        // t and U are real
+        rc = adopt_mf(out, 1, &qbh_csr::mf, m, tables(), (m.Nu * m.wu + m.Nd * m.wd) * 5 + m.Nd * m.wd * 4 + (m.Nu + m.Nd) * 4, true,
+                      row_end - row_begin, dim, row_begin, rowptr(row_end) - rowptr(row_begin), opts);
+    if (rc != QBH_OK)                        // the handle takes the tables only when adoption succeeds
+        for (void *q : tables()) (void)hipFree(q);
     return rc;
 }
 
@@ -689,7 +694,8 @@ extern "C" int qbh_mf_heisenberg(qbh_csr **out, int n_sites, int n_dn, int n_bon
     }
     const int64_t nrows = row_end - row_begin;
     const int64_t nnz_equiv = (int64_t)((double)nnz_full * ((double)nrows / (double)dim));
-    rc = adopt_mf_heis(out, t, nrows, dim, row_begin, nnz_equiv, opts);
+    const int64_t bytes = ((int64_t)(t.n_sites + 1) * (t.n_dn + 1) + (int64_t)t.n_chunks * (t.n_dn + 1) * 64 + 3 * (int64_t)t.n_bonds) * 8;
+    rc = adopt_mf(out, 2, &qbh_csr::mfh, t, pool, bytes, true, nrows, dim, row_begin, nnz_equiv, opts);      // J is real
     if (rc != QBH_OK) free_pool(pool);
     return rc;
 }

@@ -581,6 +581,18 @@ struct MfSec {
     int32_t    *rja = nullptr;
     d2         *rval = nullptr;
 };
+// The vectors and coefficients of one matrix-free y <- alpha H x + beta y + gamma x on rows [row_begin, row_begin + nrows):
+// every matrix-free kernel takes its own tables plus this block (filled once per SpMV, spmv_run).  The order of the fields is
+// the kernel-argument layout k_mf_hubbard_row<true> was tuned with (22 spilled SGPRs; 32 with y_re in front of alpha).
+struct MfVec {
+    int64_t row_begin, nrows;
+    const d2 *xg, *xl;           // gather source (full-length x), shard-local x
+    const double *xr;            // packed real parts of the gather source (nullptr = complex gather)
+    d2 *y;
+    double alpha, beta, gamma;
+    double *partials;            // [workgroups * 3] or nullptr
+    double *y_re;                // all-real operation: y stored as doubles (x_local = xr)
+};
 struct MfSecArgs {
     const MfSec *t;              // device copy
     int64_t n_items, dim, n_rrows;
@@ -588,12 +600,8 @@ struct MfSecArgs {
     const int64_t *ria;
     const int32_t *rja;
     const d2 *rval;
-    const d2 *xg, *xl;
-    const double *xr, *xl_re;
-    d2 *y;
-    double *y_re;
-    double alpha, beta, gamma;
-    double *partials;            // [nparts * 3] or nullptr
+    MfVec v;                     // row_begin = 0, nrows = dim
+    const double *xl_re;         // all-real operation: x as doubles
     unsigned int *ctr;           // ordered walk: 8 zeroed counters, 128 bytes apart (nullptr: static assignment)
     int orbit;                   // the tables are in orbit order (MfSec::orbit): k_mf_sector_orb
     // the orbit-order tables once more as kernel arguments: pointers read out of *t are generic (flat loads), these are global
@@ -605,17 +613,10 @@ struct MfSecArgs {
 };
 // y <- alpha H x + beta y + gamma x in three launches (block tables, remainder rows, reductions); *nparts_out = partial sums
 int launch_mf_sector(const MfSecArgs &a, hipStream_t s, int *nparts_out);
-int adopt_mf_sector(qbh_csr **out, MfSec *host_tables, MfSec *dev_tables, int64_t dim, int64_t nnz_equiv, const qbh_opts *opts);
 
 struct MfArgs {
     MfHubbard t;
-    int64_t row_begin, nrows;
-    const d2 *xg, *xl;
-    const double *xr;
-    d2 *y;
-    double alpha, beta, gamma;
-    double *partials;
-    double *y_re;                // all-real operation: y stored as doubles (x_local = xr)
+    MfVec v;
     // the diagonal as one value code per row + the real parts of the value dictionary (an operator RECOGNISED as T (x) 1 + 1 (x) T' + D,
     // qbh_split.cpp kronc_table_route) instead of U * double occupancy from the two configuration lists (t.cfg_u / t.cfg_d unused then)
     const uint8_t *dcode = nullptr;
@@ -637,19 +638,7 @@ struct MfHeis {
     int       uniform = 0;         // 1: every bond has the same weight (offd0, diag0): no per-bond amplitude reads
     double    offd0 = 0.0, diag0 = 0.0;
 };
-struct MfHeisArgs {
-    MfHeis t;
-    int64_t row_begin, nrows;
-    const d2 *xg, *xl;
-    const double *xr;
-    d2 *y;
-    double alpha, beta, gamma;
-    double *partials;
-    double *y_re;
-};
-int launch_mf_heis(const MfHeisArgs &a, hipStream_t s, int *nparts_out);
-int adopt_mf_heis(qbh_csr **out, const MfHeis &t, int64_t nrows, int64_t ncols, int64_t row_offset, int64_t nnz_equiv,
-                  const qbh_opts *opts);
+int launch_mf_heis(const MfHeis &t, const MfVec &v, hipStream_t s, int *nparts_out);
 // matrix-free operator on sites with d levels and one conserved charge, basis and terms of qbh_gen_qudit (qbh_qudit.hip):
 // unrank the row from cum[s][q], take every pair's levels from the packed word, column = row + qd_move_delta.  The merged
 // pair matrices are kept once per DISTINCT matrix (class); a pair with at most m off-diagonal entries in a row of its class
@@ -668,41 +657,15 @@ struct MfQudit {
     double   *pdiag = nullptr;     // [n_cls * d^2]
     int32_t  *eout = nullptr;      // [n_ent] the column's level at site j
     d2       *eval = nullptr;      // [n_ent] <in|M|out>, entry base + in
-    int64_t   bytes = 0;           // of the tables above
 };
-struct MfQuditArgs {
-    MfQudit t;
-    int64_t row_begin, nrows;
-    const d2 *xg, *xl;
-    const double *xr;
-    d2 *y;
-    double alpha, beta, gamma;
-    double *partials;
-    double *y_re;
-};
-int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out);
-int adopt_mf_qudit(qbh_csr **out, const MfQudit &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
-                   int64_t nnz_equiv, const qbh_opts *opts);
+int launch_mf_qudit(const MfQudit &t, const MfVec &v, hipStream_t s, int *nparts_out);
 // matrix-free Kondo lattice operator, basis and terms of qbh_gen_kondo (qbh_kondo.hip): the row is unranked from the A / binom
 // tables of KondoDev (qbh_kondo.hpp) and its terms walked by kd_row_terms; the one table is the device copy of KondoDev.
 struct KondoDev;
 struct MfKondo {
     KondoDev *K = nullptr;         // device copy: shape, ranking tables, merged terms
-    int64_t   bytes = 0;           // of that table
 };
-struct MfKondoArgs {
-    MfKondo t;
-    int64_t row_begin, nrows;
-    const d2 *xg, *xl;
-    const double *xr;
-    d2 *y;
-    double alpha, beta, gamma;
-    double *partials;
-    double *y_re;
-};
-int launch_mf_kondo(const MfKondoArgs &a, hipStream_t s, int *nparts_out);
-int adopt_mf_kondo(qbh_csr **out, const MfKondo &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
-                   int64_t nnz_equiv, const qbh_opts *opts);
+int launch_mf_kondo(const MfKondo &t, const MfVec &v, hipStream_t s, int *nparts_out);
 // matrix-free momentum sector of the d-level sites, basis and rows of qbh_gen_qudit_repr (qbh_sector_mf_qudit.hip): the row's
 // representative and info byte are read, its terms walked as qrepr_row walks them (qbh_sector.hpp), every target word
 // canonicalised with the translation tables and found through the directory of the enumeration.
@@ -716,23 +679,8 @@ struct MfQuditRepr {
     int64_t   dim = 0;
     int       n_tab = 0, n_cum = 0;
     int       tables_lds = 0;            // 1: tab and cum are staged in LDS; 0: they are read from global memory
-    int       n_own = 0;
-    void     *own[16] = {};              // every device array above and behind R: freed with the handle
-    int64_t   bytes = 0;                 // tables + representatives + info bytes + directory
 };
-struct MfQuditReprArgs {
-    MfQuditRepr t;
-    int64_t row_begin, nrows;
-    const d2 *xg, *xl;
-    const double *xr;
-    d2 *y;
-    double alpha, beta, gamma;
-    double *partials;
-    double *y_re;
-};
-int launch_mf_qudit_repr(const MfQuditReprArgs &a, hipStream_t s, int *nparts_out);
-int adopt_mf_qudit_repr(qbh_csr **out, const MfQuditRepr &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
-                        int64_t nnz_equiv, const qbh_opts *opts);
+int launch_mf_qudit_repr(const MfQuditRepr &t, const MfVec &v, hipStream_t s, int *nparts_out);
 // matrix-free momentum sector of the Kondo lattice, basis and rows of qbh_gen_kondo_repr (qbh_sector_mf_kondo.hip): the row's
 // representative and info byte are read, its terms walked by kd_row_terms as kondo_row walks them (qbh_sector.hpp), every
 // target word canonicalised with the translation tables and found through the directory of the enumeration (kd_rank).
@@ -744,26 +692,8 @@ struct MfKondoRepr {
     const int64_t  *chunk_pos = nullptr; // [nchunks + 1] directory: first representative of every 4096 ranks
     int64_t   dim = 0;
     int       n_tab = 0;
-    int       n_own = 0;
-    void     *own[8] = {};               // every device array above: freed with the handle
-    int64_t   bytes = 0;                 // tables + representatives + info bytes + directory
 };
-struct MfKondoReprArgs {
-    MfKondoRepr t;
-    int64_t row_begin, nrows;
-    const d2 *xg, *xl;
-    const double *xr;
-    d2 *y;
-    double alpha, beta, gamma;
-    double *partials;
-    double *y_re;
-};
-int launch_mf_kondo_repr(const MfKondoReprArgs &a, hipStream_t s, int *nparts_out);
-int adopt_mf_kondo_repr(qbh_csr **out, const MfKondoRepr &t, bool values_real, int64_t nrows, int64_t ncols, int64_t row_offset,
-                        int64_t nnz_equiv, const qbh_opts *opts);
-// adopt a matrix-free operator (tables already in HBM) behind a qbh_csr handle (qbh_api.cpp)
-int adopt_mf_hubbard(qbh_csr **out, const MfHubbard &t, int64_t nrows, int64_t ncols, int64_t row_offset,
-                     int64_t nnz_equiv, const qbh_opts *opts);
+int launch_mf_kondo_repr(const MfKondoRepr &t, const MfVec &v, hipStream_t s, int *nparts_out);
 // adopt a CSR whose value stream was generated directly in dictionary-coded form (the handle owns every array;
 // d_code holds nnz + 16 bytes, d_dict 256 entries)
 int adopt_coded_csr(qbh_csr **out, int64_t nrows, int64_t ncols, int64_t row_offset, int64_t nnz, int64_t *d_ia,
@@ -907,16 +837,19 @@ struct qbh_csr {
     qbh::d2 *d_stage_x = nullptr, *d_stage_y = nullptr;   // host-vector seam staging
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
-    // matrix-free operator (kind 1) instead of CSR arrays (kind 0)
-    int      kind = 0;               // 0 stored CSR | 1 matrix-free Hubbard | 2 matrix-free Heisenberg | 3 matrix-free Hubbard momentum sector | 4 matrix-free d-level sites | 5 matrix-free Kondo lattice | 6 matrix-free d-level momentum sector | 7 matrix-free Kondo momentum sector
-    qbh::MfSec *mfsec = nullptr;    // kind 3: block tables + compact remainder (host copy of the descriptor, device arrays)
-    qbh::MfSec *d_mfsec = nullptr;   // its device copy (kernel argument)
-    qbh::MfHubbard mf;
-    qbh::MfHeis    mfh;
-    qbh::MfQudit   mfq;
-    qbh::MfKondo   mfk;
-    qbh::MfQuditRepr mfqr;
-    qbh::MfKondoRepr mfkr;
+    // matrix-free operator (kind != 0) instead of CSR arrays (kind 0): the tables of its kind, filled by adopt_mf
+    int      kind = 0;               // 0 stored CSR, else the matrix-free form named beside its tables below
+    qbh::MfHubbard mf;               // 1 Hubbard
+    qbh::MfHeis    mfh;              // 2 Heisenberg
+    qbh::MfSec *mfsec = nullptr;     // 3 Hubbard momentum sector: block tables + compact remainder (host copy of the descriptor, device arrays)
+    qbh::MfSec *d_mfsec = nullptr;   //   its device copy (kernel argument)
+    qbh::MfQudit   mfq;              // 4 d-level sites
+    qbh::MfKondo   mfk;              // 5 Kondo lattice
+    qbh::MfQuditRepr mfqr;           // 6 d-level momentum sector
+    qbh::MfKondoRepr mfkr;           // 7 Kondo momentum sector
+    void    *mf_own[24] = {};        // every device array behind those tables: freed with the handle
+    int      n_mf_own = 0;
+    int64_t  mf_bytes = 0;           // what they hold (qbh_csr_info.bytes_matrix)
 
     // split shard: the arrays above hold the locally-owned columns, `rem` the remote ones
     bool     has_rem = false;
@@ -992,3 +925,21 @@ struct qbh_csr {
     bool  ev_drop = false;           // the current set times a discarded speculative SpMV: not counted
 };
 constexpr int kLzRing = 8;
+
+namespace qbh {
+// Adopt a matrix-free operator of `kind` (tables already in HBM) behind a qbh_csr handle with workspace and no arrays
+// (qbh_api.cpp).  own = the device arrays behind the tables, bytes = what they hold.  The handle owns them once the call has
+// succeeded; on failure the caller still does.
+int adopt_mf_handle(qbh_csr **out, int kind, const std::vector<void *> &own, int64_t bytes, bool values_real, int64_t nrows,
+                    int64_t ncols, int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts);
+// ... and its tables into their place in the handle
+template <class T>
+int adopt_mf(qbh_csr **out, int kind, T qbh_csr::*tables, const T &t, const std::vector<void *> &own, int64_t bytes, bool values_real,
+             int64_t nrows, int64_t ncols, int64_t row_offset, int64_t nnz_equiv, const qbh_opts *opts)
+{
+    QBH_TRY(adopt_mf_handle(out, kind, own, bytes, values_real, nrows, ncols, row_offset, nnz_equiv, opts));
+    (*out)->*tables = t;
+    return QBH_OK;
+}
+int adopt_mf_sector(qbh_csr **out, MfSec *host_tables, MfSec *dev_tables, int64_t dim, int64_t nnz_equiv, const qbh_opts *opts);
+}  // namespace qbh

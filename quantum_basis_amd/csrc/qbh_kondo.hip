@@ -16,6 +16,7 @@
 
 #include "qbh_internal.hpp"
 #include "qbh_kondo.hpp"
+#include "qbh_mf_row.hpp"
 
 namespace qbh {
 namespace {
@@ -113,19 +114,12 @@ __device__ __forceinline__ uint64_t kd_rank_delta(const uint64_t *binom, uint64_
     return r;
 }
 
-__device__ __forceinline__ double kd_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <bool REALX>
-__global__ __launch_bounds__(kMfKondoBlock) void k_mf_kondo(MfKondoArgs a)
+__global__ __launch_bounds__(kMfKondoBlock) void k_mf_kondo(MfKondo t, MfVec a)
 {
     __shared__ uint64_t lds[kKondoTabWords];
     __shared__ double red[3 * (kMfKondoBlock / 64)];
-    const KondoDev &K = *a.t.K;
+    const KondoDev &K = *t.K;
     kd_stage_tables(lds, K, kMfKondoBlock);
     const uint64_t *A = lds, *binom = lds + kKondoTab * kKondoTab;
     const int tid = threadIdx.x;
@@ -153,49 +147,13 @@ __global__ __launch_bounds__(kMfKondoBlock) void k_mf_kondo(MfKondoArgs a)
             } else {
                 col = kd_rank(K, A, binom, u2, d2w, s2);
             }
-            const d2 v = kd_value(K, code);
-            if (REALX) {
-                sum.x += v.x * a.xr[col];
-            } else {
-                const d2 xv = a.xg[col];
-                sum.x += v.x * xv.x - v.y * xv.y;
-                sum.y += v.x * xv.y + v.y * xv.x;
-            }
+            mf_gather_add<REALX>(a, sum, kd_value(K, code), (int64_t)col);
         });
-        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-        if (a.y_re != nullptr) {
-            if (a.beta != 0.0) yo.x = a.y_re[lrow];
-            xi.x = a.xr[grow];
-        } else {
-            if (a.beta != 0.0) yo = a.y[lrow];
-            if (REALX) xi.x = a.xr[grow];
-            else       xi = a.xg[grow];
-        }
-        sum += dg.x * xi;                                                  // the diagonal is real by construction
-        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-        else                   a.y[lrow] = yn;
-        acc[0] += xi.x * yn.x + xi.y * yn.y;
-        acc[1] += xi.x * yn.y - xi.y * yn.x;
-        acc[2] += yn.x * yn.x + yn.y * yn.y;
+        d2 yo, xi;
+        mf_row_load<REALX>(a, lrow, grow, yo, xi);
+        mf_row_finish(a, lrow, sum, dg.x, xi, yo, acc);                    // the diagonal is real by construction
     }
-    if (a.partials != nullptr) {
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = kd_wave_sum(acc[c]);
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c * (kMfKondoBlock / 64) + wave] = acc[c];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < 3; ++c) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < kMfKondoBlock / 64; ++w2) v += red[c * (kMfKondoBlock / 64) + w2];
-                a.partials[(size_t)blockIdx.x * 3 + c] = v;
-            }
-        }
-    }
+    mf_block_partials<kMfKondoBlock>(acc, red, a.partials);
 }
 
 // entries qbh_gen_kondo would store for rows [row_begin, row_end) (the diagonal always, zero amplitudes dropped elsewhere):
@@ -231,12 +189,12 @@ struct HipFree {
 
 }  // namespace
 
-int launch_mf_kondo(const MfKondoArgs &a, hipStream_t s, int *nparts_out)
+int launch_mf_kondo(const MfKondo &t, const MfVec &a, hipStream_t s, int *nparts_out)
 {
     const int64_t nblk = (a.nrows + kMfKondoBlock - 1) / kMfKondoBlock;
     const int g = (int)std::min<int64_t>(nblk, std::min<int64_t>((int64_t)device_cu_count() * kMfKondoPerCu, kMaxRedBlocks));
-    if (a.xr != nullptr) hipLaunchKernelGGL(k_mf_kondo<true>, dim3(g), dim3(kMfKondoBlock), 0, s, a);
-    else                 hipLaunchKernelGGL(k_mf_kondo<false>, dim3(g), dim3(kMfKondoBlock), 0, s, a);
+    if (a.xr != nullptr) hipLaunchKernelGGL(k_mf_kondo<true>, dim3(g), dim3(kMfKondoBlock), 0, s, t, a);
+    else                 hipLaunchKernelGGL(k_mf_kondo<false>, dim3(g), dim3(kMfKondoBlock), 0, s, t, a);
     QBH_HIP(hipGetLastError());
     if (nparts_out) *nparts_out = g;
     return QBH_OK;
@@ -537,7 +495,6 @@ extern "C" int qbh_mf_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz, 
     QBH_KHIP(who, qbh::dev_alloc(&t.K, sizeof(KondoDev)));
     pool.p.push_back(t.K);
     QBH_KHIP(who, hipMemcpy(t.K, &K, sizeof(KondoDev), hipMemcpyHostToDevice));
-    t.bytes = (int64_t)sizeof(KondoDev);
 
     const int64_t nrows = row_end - row_begin;
     const int cgrid = blas_grid(nrows);
@@ -552,7 +509,7 @@ extern "C" int qbh_mf_kondo(qbh_csr **out, int n_sites, int n_elec, int two_sz, 
     int64_t nnz = 0;
     for (unsigned long long v : part) nnz += (int64_t)v;
 
-    const int rc = adopt_mf_kondo(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    const int rc = adopt_mf(out, 5, &qbh_csr::mfk, t, pool.p, (int64_t)sizeof(KondoDev), values_real, nrows, dim, row_begin, nnz, opts);
     if (rc == QBH_OK) pool.p.clear();                         // the handle owns the tables now
     return rc;
 }

@@ -2,7 +2,7 @@
 #include <algorithm>
 
 #include "qbh_internal.hpp"
-#include "qbh_device.hpp"
+#include "qbh_mf_row.hpp"
 
 namespace qbh {
 
@@ -20,18 +20,18 @@ __global__ __launch_bounds__(kBlock) void k_mf_hubbard(MfArgs a)
     const MfHubbard &t = a.t;
     if (threadIdx.x < 16) amp_s[threadIdx.x] = t.amp[threadIdx.x];
     __syncthreads();
-    const int64_t n_chunks = (a.nrows + kBlock - 1) / kBlock;
-    const bool need_x = a.gamma != 0.0 || a.partials != nullptr;
+    const int64_t n_chunks = (a.v.nrows + kBlock - 1) / kBlock;
+    const bool need_x = a.v.gamma != 0.0 || a.v.partials != nullptr;
     for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const int64_t lrow = chunk * kBlock + threadIdx.x;
-        if (lrow < a.nrows) {
-            const int64_t grow = a.row_begin + lrow;
+        if (lrow < a.v.nrows) {
+            const int64_t grow = a.v.row_begin + lrow;
             const int64_t u = grow / t.Nd, d = grow - u * t.Nd;
             d2 sum = {0.0, 0.0};
             // diagonal: U * number of doubly occupied sites
             const double diag = t.U * (double)__popc(t.cfg_u[u] & t.cfg_d[d]);
-            if (REALX) sum.x = diag * a.xr[grow];
-            else       sum = diag * a.xg[grow];
+            if (REALX) sum.x = diag * a.v.xr[grow];
+            else       sum = diag * a.v.xg[grow];
             // The tables are padded to a multiple of 8 hops with (target = the configuration itself, amplitude 0),
             // so each group of 8 table reads and 8 gathers is issued without a branch (8 loads in flight per lane).
             // up-species hops: x[u' * Nd + d], consecutive lanes -> consecutive addresses
@@ -46,13 +46,13 @@ __global__ __launch_bounds__(kBlock) void k_mf_hubbard(MfArgs a)
                 if (REALX) {
                     double xr[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) xr[j] = a.xr[c[j]];
+                    for (int j = 0; j < 8; ++j) xr[j] = a.v.xr[c[j]];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) sum.x += v[j] * xr[j];
                 } else {
                     d2 xv[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) xv[j] = a.xg[c[j]];
+                    for (int j = 0; j < 8; ++j) xv[j] = a.v.xg[c[j]];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) sum += v[j] * xv[j];
                 }
@@ -70,39 +70,39 @@ __global__ __launch_bounds__(kBlock) void k_mf_hubbard(MfArgs a)
                 if (REALX) {
                     double xr[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) xr[j] = a.xr[c[j]];
+                    for (int j = 0; j < 8; ++j) xr[j] = a.v.xr[c[j]];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) sum.x += v[j] * xr[j];
                 } else {
                     d2 xv[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) xv[j] = a.xg[c[j]];
+                    for (int j = 0; j < 8; ++j) xv[j] = a.v.xg[c[j]];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) sum += v[j] * xv[j];
                 }
             }
             d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-            if (a.y_re != nullptr) {                  // all-real operation (REALX): y and x_local as doubles
-                if (a.beta != 0.0) yo.x = a.y_re[lrow];
-                if (need_x) xi.x = a.xr[grow];
+            if (a.v.y_re != nullptr) {                  // all-real operation (REALX): y and x_local as doubles
+                if (a.v.beta != 0.0) yo.x = a.v.y_re[lrow];
+                if (need_x) xi.x = a.v.xr[grow];
             } else {
-                if (a.beta != 0.0) yo = a.y[lrow];
-                if (need_x) xi = a.xl[lrow];
+                if (a.v.beta != 0.0) yo = a.v.y[lrow];
+                if (need_x) xi = a.v.xl[lrow];
             }
-            const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-            if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-            else                   a.y[lrow] = yn;
+            const d2 yn = a.v.alpha * sum + a.v.beta * yo + a.v.gamma * xi;
+            if (a.v.y_re != nullptr) a.v.y_re[lrow] = yn.x;
+            else                     a.v.y[lrow] = yn;
             acc[0] += xi.x * yn.x + xi.y * yn.y;
             acc[1] += xi.x * yn.y - xi.y * yn.x;
             acc[2] += yn.x * yn.x + yn.y * yn.y;
         }
     }
-    if (a.partials != nullptr) {
+    if (a.v.partials != nullptr) {
         block_sum<3>(acc, red);
         if (threadIdx.x == 0) {
-            a.partials[(size_t)blockIdx.x * 3 + 0] = acc[0];
-            a.partials[(size_t)blockIdx.x * 3 + 1] = acc[1];
-            a.partials[(size_t)blockIdx.x * 3 + 2] = acc[2];
+            a.v.partials[(size_t)blockIdx.x * 3 + 0] = acc[0];
+            a.v.partials[(size_t)blockIdx.x * 3 + 1] = acc[1];
+            a.v.partials[(size_t)blockIdx.x * 3 + 2] = acc[2];
         }
     }
 }
@@ -138,8 +138,8 @@ __global__ __launch_bounds__(kMfRowBlock) void k_mf_hubbard_row(MfArgs a, int ch
     double acc[3] = {0.0, 0.0, 0.0};
     if (tid < 16) amp_s[tid] = t.amp[tid];
     if (a.dcode != nullptr && tid < 256) dd_s[tid] = a.ddict[tid];
-    const int64_t u_first = a.row_begin / Nd, u_last = (a.row_begin + a.nrows - 1) / Nd;
-    const bool need_y = a.beta != 0.0;
+    const int64_t u_first = a.v.row_begin / Nd, u_last = (a.v.row_begin + a.v.nrows - 1) / Nd;
+    const bool need_y = a.v.beta != 0.0;
     const uint4 *pk = reinterpret_cast<const uint4 *>(t.pk_d);
     const int nk4 = t.wd / 4;
     const int64_t n_chunks = WINDOWED ? (Nd + chunk - 1) / chunk : 1;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kMfRowBlock) void k_mf_hubbard_row(MfArgs a, int ch
                 w_lo = w_hi - wcap > 0 ? w_hi - wcap : 0;
             }
         }
-        const double *xrow = a.xr + u * Nd;
+        const double *xrow = a.v.xr + u * Nd;
         for (int64_t d = w_lo + tid; d < w_hi; d += kMfRowBlock) xs[d - w_lo] = xrow[d];
         if (tid < 64) {
             // the up-neighbours of u with a non-zero amplitude, compacted by one wavefront and padded to a group of 8
@@ -182,8 +182,8 @@ __global__ __launch_bounds__(kMfRowBlock) void k_mf_hubbard_row(MfArgs a, int ch
             if (tid == 0) up_n = npad;
         }
         __syncthreads();
-        int64_t d_lo = a.row_begin > u * Nd ? a.row_begin - u * Nd : 0;
-        int64_t d_hi = (a.row_begin + a.nrows - u * Nd) < Nd ? (a.row_begin + a.nrows - u * Nd) : Nd;
+        int64_t d_lo = a.v.row_begin > u * Nd ? a.v.row_begin - u * Nd : 0;
+        int64_t d_hi = (a.v.row_begin + a.v.nrows - u * Nd) < Nd ? (a.v.row_begin + a.v.nrows - u * Nd) : Nd;
         if (d_lo < c_lo) d_lo = c_lo;
         if (d_hi > c_hi) d_hi = c_hi;
         const uint32_t cu = a.dcode != nullptr ? 0u : t.cfg_u[u];
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kMfRowBlock) void k_mf_hubbard_row(MfArgs a, int ch
             for (int j0 = 0; j0 < nu; j0 += 8) {
                 double xv[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) xv[j] = a.xr[up_off[j0 + j] + d];
+                for (int j = 0; j < 8; ++j) xv[j] = a.v.xr[up_off[j0 + j] + d];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) sum += up_amp[j0 + j] * xv[j];
             }
@@ -226,40 +226,24 @@ __global__ __launch_bounds__(kMfRowBlock) void k_mf_hubbard_row(MfArgs a, int ch
 #pragma unroll
                 for (int j = 0; j < 8; ++j) sum += amp_s[w[j] >> 24] * xv[j];
             }
-            const int64_t lrow = u * Nd + d - a.row_begin;
+            const int64_t lrow = u * Nd + d - a.v.row_begin;
             d2 yo = {0.0, 0.0};
             if (need_y) {
-                if (a.y_re != nullptr) yo.x = a.y_re[lrow];
-                else                   yo = a.y[lrow];
+                if (a.v.y_re != nullptr) yo.x = a.v.y_re[lrow];
+                else                     yo = a.v.y[lrow];
             }
             d2 yn;
-            yn.x = a.alpha * sum + a.beta * yo.x + a.gamma * xd;
-            yn.y = a.beta * yo.y;
-            if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-            else                   a.y[lrow] = yn;
+            yn.x = a.v.alpha * sum + a.v.beta * yo.x + a.v.gamma * xd;
+            yn.y = a.v.beta * yo.y;
+            if (a.v.y_re != nullptr) a.v.y_re[lrow] = yn.x;
+            else                     a.v.y[lrow] = yn;
             acc[0] += xd * yn.x;
             acc[1] += xd * yn.y;
             acc[2] += yn.x * yn.x + yn.y * yn.y;
         }
         __syncthreads();                           // the row and the neighbour list are rewritten next
     }
-    if (a.partials != nullptr) {
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = wave_sum(acc[c]);
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c * (kMfRowBlock / 64) + wave] = acc[c];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < 3; ++c) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < kMfRowBlock / 64; ++w2) v += red[c * (kMfRowBlock / 64) + w2];
-                a.partials[(size_t)blockIdx.x * 3 + c] = v;
-            }
-        }
-    }
+    mf_block_partials<kMfRowBlock>(acc, red, a.v.partials);
 }
 
 // -------------------------------------------- matrix-free Heisenberg operator --
@@ -269,11 +253,10 @@ constexpr int kMfHeisBlock = 512;
 
 // NCH > 0: the number of chunks as a compile-time constant (re-ranking loop fully unrolled, 32-bit index arithmetic)
 template <bool REALX, int NCH>
-__global__ __launch_bounds__(kMfHeisBlock) void k_mf_heis(MfHeisArgs a)
+__global__ __launch_bounds__(kMfHeisBlock) void k_mf_heis(MfHeis t, MfVec a)
 {
     extern __shared__ unsigned long long lds_u64[];
     __shared__ double red[3 * (kMfHeisBlock / 64)];
-    const MfHeis &t = a.t;
     const int nk = t.n_dn + 1;
     unsigned long long *binom = lds_u64;                                  // [(n_sites+1) * nk]
     unsigned long long *chunk = binom + (size_t)(t.n_sites + 1) * nk;     // [n_chunks * nk * 64]
@@ -362,41 +345,12 @@ __global__ __launch_bounds__(kMfHeisBlock) void k_mf_heis(MfHeisArgs a)
                 for (int j = 0; j < 8; ++j) sum += amp[j] * xv[j];
             }
         }
-        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-        if (a.y_re != nullptr) {
-            if (a.beta != 0.0) yo.x = a.y_re[lrow];
-            xi.x = a.xr[grow];
-        } else {
-            if (a.beta != 0.0) yo = a.y[lrow];
-            if (REALX) xi.x = a.xr[grow];
-            else       xi = a.xg[grow];
-        }
+        d2 yo, xi;
+        mf_row_load<REALX>(a, lrow, grow, yo, xi);
         if (uniform) dg = diag0 * (double)(t.n_real - 2 * ndiff);
-        sum += dg * xi;                                // diagonal: sum_b +-J_b/4
-        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-        else                   a.y[lrow] = yn;
-        acc[0] += xi.x * yn.x + xi.y * yn.y;
-        acc[1] += xi.x * yn.y - xi.y * yn.x;
-        acc[2] += yn.x * yn.x + yn.y * yn.y;
+        mf_row_finish(a, lrow, sum, dg, xi, yo, acc);      // diagonal: sum_b +-J_b/4
     }
-    if (a.partials != nullptr) {
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = wave_sum(acc[c]);
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c * (kMfHeisBlock / 64) + wave] = acc[c];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < 3; ++c) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < kMfHeisBlock / 64; ++w2) v += red[c * (kMfHeisBlock / 64) + w2];
-                a.partials[(size_t)blockIdx.x * 3 + c] = v;
-            }
-        }
-    }
+    mf_block_partials<kMfHeisBlock>(acc, red, a.partials);
 }
 
 int device_cu_count()
@@ -411,10 +365,9 @@ int device_cu_count()
     return ncu;
 }
 
-int launch_mf_heis(const MfHeisArgs &a, hipStream_t s, int *nparts_out)
+int launch_mf_heis(const MfHeis &t, const MfVec &a, hipStream_t s, int *nparts_out)
 {
     const int ncu = device_cu_count();
-    const MfHeis &t = a.t;
     const size_t nk = (size_t)t.n_dn + 1;
     const size_t lds = ((size_t)(t.n_sites + 1) * nk + (size_t)t.n_chunks * nk * 64 + (size_t)t.n_bonds) * 8 + (size_t)t.n_bonds * 16;
     if (lds > (size_t)150 * 1024) {
@@ -428,7 +381,7 @@ int launch_mf_heis(const MfHeisArgs &a, hipStream_t s, int *nparts_out)
     do {                                                                                                                          \
         QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_heis<RX, NC>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                     (int)lds));                                                                                   \
-        hipLaunchKernelGGL((k_mf_heis<RX, NC>), dim3(g), dim3(kMfHeisBlock), lds, s, a);                                           \
+        hipLaunchKernelGGL((k_mf_heis<RX, NC>), dim3(g), dim3(kMfHeisBlock), lds, s, t, a);                                        \
     } while (0)
     const bool rx = a.xr != nullptr;
     switch (t.n_chunks) {                                   // 24..36 sites get the unrolled forms
@@ -446,7 +399,7 @@ int launch_mf_heis(const MfHeisArgs &a, hipStream_t s, int *nparts_out)
 // true when a row-staged kernel applies: real vectors, the neighbour list fits one wavefront
 bool mf_row_kernel_ok(const MfArgs &a)
 {
-    if (a.xr == nullptr || a.t.pk_d == nullptr) return false;
+    if (a.v.xr == nullptr || a.t.pk_d == nullptr) return false;
     if (debug_sw().mf_row == 0) return false;
     return a.t.Nd >= 256 && a.t.Nd < (1 << 24) && a.t.wu <= kMfMaxUp && (a.t.wd % 8) == 0;
 }
@@ -458,7 +411,7 @@ int launch_mf_hubbard(const MfArgs &a, int grid, hipStream_t s, int *nparts_out)
         const int ncu = device_cu_count();
         const size_t lds_cap = (size_t)150 * 1024;
         const bool windowed = (size_t)a.t.Nd * sizeof(double) > lds_cap;
-        const int64_t n_u = (a.row_begin + a.nrows - 1) / a.t.Nd - a.row_begin / a.t.Nd + 1;
+        const int64_t n_u = (a.v.row_begin + a.v.nrows - 1) / a.t.Nd - a.v.row_begin / a.t.Nd + 1;
         if (!windowed) {
             const size_t lds = (size_t)a.t.Nd * sizeof(double);
             QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_hubbard_row<false>),
@@ -485,8 +438,8 @@ int launch_mf_hubbard(const MfArgs &a, int grid, hipStream_t s, int *nparts_out)
         if (nparts_out) *nparts_out = g;
         return QBH_OK;
     }
-    if (a.xr != nullptr) hipLaunchKernelGGL((k_mf_hubbard<true>), dim3(grid), dim3(kBlock), 0, s, a);
-    else                 hipLaunchKernelGGL((k_mf_hubbard<false>), dim3(grid), dim3(kBlock), 0, s, a);
+    if (a.v.xr != nullptr) hipLaunchKernelGGL((k_mf_hubbard<true>), dim3(grid), dim3(kBlock), 0, s, a);
+    else                   hipLaunchKernelGGL((k_mf_hubbard<false>), dim3(grid), dim3(kBlock), 0, s, a);
     QBH_HIP(hipGetLastError());
     if (nparts_out) *nparts_out = grid;
     return QBH_OK;

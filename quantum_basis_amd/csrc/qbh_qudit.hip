@@ -21,6 +21,7 @@
 
 #include "qbh_internal.hpp"
 #include "qbh_qudit.hpp"
+#include "qbh_mf_row.hpp"
 
 namespace qbh {
 namespace {
@@ -208,13 +209,6 @@ __global__ __launch_bounds__(256) void k_qudit_mopr(int n_sites, int d, int bits
 constexpr int kMfQuditBlock = 512;
 constexpr size_t kMfQuditLdsCap = (size_t)150 * 1024;        // the budget of launch_mf_heis
 
-__device__ __forceinline__ double qd_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // LDS layout, 16-byte items first: eval[n_ent] (TLDS) | cum | sdiag | pdiag (TLDS) | slot | eout (TLDS)
 inline size_t mf_qudit_lds_bytes(const MfQudit &t, bool tables)
 {
@@ -225,11 +219,10 @@ inline size_t mf_qudit_lds_bytes(const MfQudit &t, bool tables)
 }
 
 template <bool REALX, bool TLDS>
-__global__ __launch_bounds__(kMfQuditBlock) void k_mf_qudit(MfQuditArgs a)
+__global__ __launch_bounds__(kMfQuditBlock) void k_mf_qudit(MfQudit t, MfVec a)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t qd_lds[];
     __shared__ double red[3 * (kMfQuditBlock / 64)];
-    const MfQudit &t = a.t;
     const int tid = threadIdx.x;
     const int d = t.d, bits = t.bits, tw = t.tw, d2n = d * d;
     const int ncum = t.n_sites * tw, nsd = t.n_sites * d, npd = t.n_cls * d2n;
@@ -299,40 +292,11 @@ __global__ __launch_bounds__(kMfQuditBlock) void k_mf_qudit(MfQuditArgs a)
                 }
             }
         }
-        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-        if (a.y_re != nullptr) {
-            if (a.beta != 0.0) yo.x = a.y_re[lrow];
-            xi.x = a.xr[grow];
-        } else {
-            if (a.beta != 0.0) yo = a.y[lrow];
-            if (REALX) xi.x = a.xr[grow];
-            else       xi = a.xg[grow];
-        }
-        sum += dg * xi;
-        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-        else                   a.y[lrow] = yn;
-        acc[0] += xi.x * yn.x + xi.y * yn.y;
-        acc[1] += xi.x * yn.y - xi.y * yn.x;
-        acc[2] += yn.x * yn.x + yn.y * yn.y;
+        d2 yo, xi;
+        mf_row_load<REALX>(a, lrow, grow, yo, xi);
+        mf_row_finish(a, lrow, sum, dg, xi, yo, acc);
     }
-    if (a.partials != nullptr) {
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = qd_wave_sum(acc[c]);
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c * (kMfQuditBlock / 64) + wave] = acc[c];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < 3; ++c) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < kMfQuditBlock / 64; ++w2) v += red[c * (kMfQuditBlock / 64) + w2];
-                a.partials[(size_t)blockIdx.x * 3 + c] = v;
-            }
-        }
-    }
+    mf_block_partials<kMfQuditBlock>(acc, red, a.partials);
 }
 
 // entries a stored CSR of rows [row_begin, row_end) would hold (the diagonal always, exact zeros dropped): one sum per workgroup
@@ -471,11 +435,11 @@ int qudit_merge_terms(const char *who, int n_sites, int d, int n_pairs, const in
     return QBH_OK;
 }
 
-int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out)
+int launch_mf_qudit(const MfQudit &t, const MfVec &a, hipStream_t s, int *nparts_out)
 {
     const int ncu = device_cu_count();
-    const bool tl = a.t.tables_lds != 0;
-    const size_t lds = mf_qudit_lds_bytes(a.t, tl);
+    const bool tl = t.tables_lds != 0;
+    const size_t lds = mf_qudit_lds_bytes(t, tl);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ((size_t)158 * 1024) / (lds + 1024)));
     const int64_t nblk = (a.nrows + kMfQuditBlock - 1) / kMfQuditBlock;
     const int g = (int)std::min<int64_t>(nblk, (int64_t)ncu * per_cu);
@@ -483,7 +447,7 @@ int launch_mf_qudit(const MfQuditArgs &a, hipStream_t s, int *nparts_out)
     do {                                                                                                                          \
         QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_qudit<RX, TL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                     (int)lds));                                                                                   \
-        hipLaunchKernelGGL((k_mf_qudit<RX, TL>), dim3(g), dim3(kMfQuditBlock), lds, s, a);                                         \
+        hipLaunchKernelGGL((k_mf_qudit<RX, TL>), dim3(g), dim3(kMfQuditBlock), lds, s, t, a);                                     \
     } while (0)
     if (a.xr != nullptr) {
         if (tl) QBH_QUDIT_LAUNCH(true, true); else QBH_QUDIT_LAUNCH(true, false);
@@ -713,7 +677,7 @@ extern "C" int qbh_mf_qudit(qbh_csr **out, int n_sites, int d, int total, int n_
     for (double v : T.sdiag)
         if (v != 0.0) t.has_single = 1;
     t.tables_lds = mf_qudit_lds_bytes(t, true) <= kMfQuditLdsCap ? 1 : 0;
-    t.bytes = (int64_t)(cum.size() * 8 + pairs.size() * 4 + nrow.size() * 4 + slot.size() * 4 + T.sdiag.size() * 8 + pdiag.size() * 8 +
+    const int64_t bytes = (int64_t)(cum.size() * 8 + pairs.size() * 4 + nrow.size() * 4 + slot.size() * 4 + T.sdiag.size() * 8 + pdiag.size() * 8 +
                         eout.size() * 4 + eval.size() * 16);
     HipFree pool;
     QBH_QHIP(who, up(pool, &t.cum, cum));
@@ -738,7 +702,7 @@ extern "C" int qbh_mf_qudit(qbh_csr **out, int n_sites, int d, int total, int n_
     int64_t nnz = 0;
     for (unsigned long long v : part) nnz += (int64_t)v;
 
-    const int rc = adopt_mf_qudit(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    const int rc = adopt_mf(out, 4, &qbh_csr::mfq, t, pool.p, bytes, values_real, nrows, dim, row_begin, nnz, opts);
     if (rc == QBH_OK) pool.p.clear();                         // the handle owns the tables now
     return rc;
 }

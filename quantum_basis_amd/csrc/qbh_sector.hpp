@@ -666,6 +666,40 @@ __device__ __forceinline__ int sector_row(const KondoReprDev &R, const uint64_t 
 // kept per word besides one code byte (4x5 Hubbard at half filling has 3.4e10 words): the counts are per chunk.
 constexpr int kSectorRun = 16, kSectorChunk = kSectorRun * 256;
 
+// position of representative b in reps[0, dim) through the directory of the enumeration (sector_enumerate's chunk_pos):
+// rank_of_b, the rank of b among the family's words, names its chunk of kSectorChunk words; the directory gives the
+// positions of that chunk's first and last representatives, and a bisection of at most 12 steps ends among them.  b is a
+// representative, so this is sector_find(reps, dim, b); the result stays below dim for any word.
+static_assert(kSectorChunk == 1 << 12, "sector_dir_find shifts a rank by 12 bits to its chunk");
+__device__ __forceinline__ int64_t sector_dir_find(const uint64_t *reps, const int64_t *chunk_pos, int64_t dim, uint64_t b, uint64_t rank_of_b)
+{
+    const uint64_t c = rank_of_b >> 12;
+    int64_t lo = chunk_pos[c], hi = chunk_pos[c + 1];
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (reps[mid] < b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < dim ? lo : dim - 1;
+}
+
+// host tail of the matrix-free sector creators: launch(d_part) starts a count kernel on the null stream that leaves one sum per
+// workgroup in d_part[0, cgrid) and returns its launch error; *total = the sum of them
+template <class Launch>
+int sector_count_entries(const char *who, int cgrid, int64_t *total, Launch launch)
+{
+    unsigned long long *d_part = nullptr;
+    QBH_HIP_WHO(who, qbh::dev_alloc(&d_part, (size_t)cgrid * sizeof(unsigned long long)));
+    hipError_t ce = launch(d_part);
+    std::vector<unsigned long long> part((size_t)cgrid);
+    if (ce == hipSuccess) ce = hipMemcpy(part.data(), d_part, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_part);
+    QBH_HIP_WHO(who, ce);
+    *total = 0;
+    for (unsigned long long v : part) *total += (int64_t)v;
+    return QBH_OK;
+}
+
 // pass 1: code[r] = 0 if the word of rank r is not a representative, else |S| | (zero-norm << 7); chunk_cnt = the number of
 // representatives of each chunk
 template <class Dev>

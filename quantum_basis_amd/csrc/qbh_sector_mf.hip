@@ -184,8 +184,8 @@ __global__ __launch_bounds__(256) void k_mf_sector(MfSecArgs a)
                     for (uint32_t m = u; m; m &= m - 1) dr += T.nup[__ffs(m) - 1];
                     for (uint32_t m = d; m; m &= m - 1) dr += T.ndn[__ffs(m) - 1];
                 }
-                if (REALX) sum.x = dr * a.xr[row];
-                else       sum = dr * a.xg[row];
+                if (REALX) sum.x = dr * a.v.xr[row];
+                else       sum = dr * a.v.xg[row];
                 for (int k0 = 0; k0 < T.w_up; k0 += kSecUnroll) {          // up hops: inside the block
                     uint32_t e[kSecUnroll];
 #pragma unroll
@@ -193,14 +193,14 @@ __global__ __launch_bounds__(256) void k_mf_sector(MfSecArgs a)
                     if (REALX) {
                         double xv[kSecUnroll];
 #pragma unroll
-                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = e[q] != 0xFFFFFFFFu ? a.xr[B.row0 + (e[q] & 0xFFFFFFu)] : 0.0;
+                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = e[q] != 0xFFFFFFFFu ? a.v.xr[B.row0 + (e[q] & 0xFFFFFFu)] : 0.0;
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
                             if (e[q] != 0xFFFFFFFFu) sum.x += T.updict[e[q] >> 24] * xv[q];
                     } else {
                         d2 xv[kSecUnroll];
 #pragma unroll
-                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = e[q] != 0xFFFFFFFFu ? a.xg[B.row0 + (e[q] & 0xFFFFFFu)] : d2{0.0, 0.0};
+                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = e[q] != 0xFFFFFFFFu ? a.v.xg[B.row0 + (e[q] & 0xFFFFFFu)] : d2{0.0, 0.0};
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
                             if (e[q] != 0xFFFFFFFFu) sum += T.updict[e[q] >> 24] * xv[q];
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void k_mf_sector(MfSecArgs a)
                     if (REALX) {
                         double xv[kSecUnroll];
 #pragma unroll
-                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = h0 + q < B.nhop ? a.xr[sh[h0 + q].off + (pr[q] & 0x7FFFFFFFu)] : 0.0;
+                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = h0 + q < B.nhop ? a.v.xr[sh[h0 + q].off + (pr[q] & 0x7FFFFFFFu)] : 0.0;
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
                             if (h0 + q < B.nhop) sum.x += ((pr[q] >> 31) ? -sh[h0 + q].cr : sh[h0 + q].cr) * xv[q];
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void k_mf_sector(MfSecArgs a)
                         d2 xv[kSecUnroll];
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
-                            xv[q] = h0 + q < B.nhop ? a.xg[sh[h0 + q].off + (pr[q] & 0x7FFFFFFFu)] : d2{0.0, 0.0};
+                            xv[q] = h0 + q < B.nhop ? a.v.xg[sh[h0 + q].off + (pr[q] & 0x7FFFFFFFu)] : d2{0.0, 0.0};
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
                             if (h0 + q < B.nhop) {
@@ -234,11 +234,11 @@ __global__ __launch_bounds__(256) void k_mf_sector(MfSecArgs a)
                 }
             }
             d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-            if (a.beta != 0.0) yo = a.y_re ? d2{a.y_re[row], 0.0} : a.y[row];
-            if (a.gamma != 0.0) xi = a.y_re ? d2{a.xl_re[row], 0.0} : a.xl[row];
-            const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-            if (a.y_re) a.y_re[row] = yn.x;
-            else        a.y[row] = yn;
+            if (a.v.beta != 0.0) yo = a.v.y_re ? d2{a.v.y_re[row], 0.0} : a.v.y[row];
+            if (a.v.gamma != 0.0) xi = a.v.y_re ? d2{a.xl_re[row], 0.0} : a.v.xl[row];
+            const d2 yn = a.v.alpha * sum + a.v.beta * yo + a.v.gamma * xi;
+            if (a.v.y_re) a.v.y_re[row] = yn.x;
+            else          a.v.y[row] = yn;
         }
     }
 }
@@ -298,8 +298,8 @@ __global__ __launch_bounds__(256) void k_mf_sector_orb(MfSecArgs a)
         if (B.regular)
             for (int h = threadIdx.x; h < B.nhop; h += 256) sh[h] = T.hop[B.hop0 + h];
         __syncthreads();
-        const double *xrb = REALX ? a.xr + B.row0 : nullptr;              // the block's own x
-        const d2 *xgb = REALX ? nullptr : a.xg + B.row0;
+        const double *xrb = REALX ? a.v.xr + B.row0 : nullptr;              // the block's own x
+        const d2 *xgb = REALX ? nullptr : a.v.xg + B.row0;
         for (int j = 0; j < a.tile / 256; ++j) {
             const int tb = tile * a.tile + j * 256;                       // the same in every lane
             const uint32_t ln = threadIdx.x;
@@ -371,14 +371,14 @@ __global__ __launch_bounds__(256) void k_mf_sector_orb(MfSecArgs a)
                     if (REALX) {
                         double xv[kSecUnroll];
 #pragma unroll
-                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = h0 + q < B.nhop ? sec_at(a.xr + off[q], ix[q]) : 0.0;
+                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = h0 + q < B.nhop ? sec_at(a.v.xr + off[q], ix[q]) : 0.0;
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
                             if (h0 + q < B.nhop) sum.x += (((tp >> gg[q]) & 1ULL) ? -sh[h0 + q].cr : sh[h0 + q].cr) * xv[q];
                     } else {
                         d2 xv[kSecUnroll];
 #pragma unroll
-                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = h0 + q < B.nhop ? sec_at(a.xg + off[q], ix[q]) : d2{0.0, 0.0};
+                        for (int q = 0; q < kSecUnroll; ++q) xv[q] = h0 + q < B.nhop ? sec_at(a.v.xg + off[q], ix[q]) : d2{0.0, 0.0};
 #pragma unroll
                         for (int q = 0; q < kSecUnroll; ++q)
                             if (h0 + q < B.nhop) {
@@ -390,11 +390,11 @@ __global__ __launch_bounds__(256) void k_mf_sector_orb(MfSecArgs a)
                 }
             }
             d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-            if (a.beta != 0.0) yo = a.y_re ? d2{sec_at(a.y_re + B.row0 + tb, ln), 0.0} : sec_at(a.y + B.row0 + tb, ln);
-            if (a.gamma != 0.0) xi = a.y_re ? d2{sec_at(a.xl_re + B.row0 + tb, ln), 0.0} : sec_at(a.xl + B.row0 + tb, ln);
-            const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-            if (a.y_re) a.y_re[row] = yn.x;
-            else        a.y[row] = yn;
+            if (a.v.beta != 0.0) yo = a.v.y_re ? d2{sec_at(a.v.y_re + B.row0 + tb, ln), 0.0} : sec_at(a.v.y + B.row0 + tb, ln);
+            if (a.v.gamma != 0.0) xi = a.v.y_re ? d2{sec_at(a.xl_re + B.row0 + tb, ln), 0.0} : sec_at(a.v.xl + B.row0 + tb, ln);
+            const d2 yn = a.v.alpha * sum + a.v.beta * yo + a.v.gamma * xi;
+            if (a.v.y_re) a.v.y_re[row] = yn.x;
+            else          a.v.y[row] = yn;
         }
     }
 }
@@ -414,9 +414,9 @@ __global__ __launch_bounds__(256) void k_sec_remainder(MfSecArgs a)
         for (int64_t q = a.ria[p] + sub; q < q1; q += TPR) {
             const d2 v = a.rval[q];
             if (REALX) {
-                sum.x += v.x * a.xr[a.rja[q]];
+                sum.x += v.x * a.v.xr[a.rja[q]];
             } else {
-                const d2 xv = a.xg[a.rja[q]];
+                const d2 xv = a.v.xg[a.rja[q]];
                 sum += d2{v.x * xv.x - v.y * xv.y, v.x * xv.y + v.y * xv.x};
             }
         }
@@ -426,8 +426,8 @@ __global__ __launch_bounds__(256) void k_sec_remainder(MfSecArgs a)
         }
         if (sub == 0) {
             const int64_t row = a.rrow[p];
-            if (a.y_re) a.y_re[row] += a.alpha * sum.x;
-            else        a.y[row] += a.alpha * sum;
+            if (a.v.y_re) a.v.y_re[row] += a.v.alpha * sum.x;
+            else          a.v.y[row] += a.v.alpha * sum;
         }
     }
 }
@@ -439,8 +439,8 @@ __global__ __launch_bounds__(256) void k_sec_reduce(MfSecArgs a)
     double acc[3] = {0.0, 0.0, 0.0};
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.dim; i += stride) {
-        const d2 xi = a.y_re ? d2{a.xl_re[i], 0.0} : a.xl[i];
-        const d2 yn = a.y_re ? d2{a.y_re[i], 0.0} : a.y[i];
+        const d2 xi = a.v.y_re ? d2{a.xl_re[i], 0.0} : a.v.xl[i];
+        const d2 yn = a.v.y_re ? d2{a.v.y_re[i], 0.0} : a.v.y[i];
         acc[0] += xi.x * yn.x + xi.y * yn.y;
         acc[1] += xi.x * yn.y - xi.y * yn.x;
         acc[2] += yn.x * yn.x + yn.y * yn.y;
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(256) void k_sec_reduce(MfSecArgs a)
         for (int c = 0; c < 3; ++c) red[c * 4 + wave] = acc[c];
     __syncthreads();
     if (threadIdx.x == 0)
-        for (int c = 0; c < 3; ++c) a.partials[(size_t)blockIdx.x * 3 + c] = (red[c * 4] + red[c * 4 + 1]) + (red[c * 4 + 2] + red[c * 4 + 3]);
+        for (int c = 0; c < 3; ++c) a.v.partials[(size_t)blockIdx.x * 3 + c] = (red[c * 4] + red[c * 4 + 1]) + (red[c * 4 + 2] + red[c * 4 + 3]);
 }
 
 }  // namespace
@@ -498,14 +498,14 @@ int launch_mf_sector(const MfSecArgs &a, hipStream_t s, int *nparts_out)
         if (debug_sw().sec_unroll) un = debug_sw().sec_unroll;              // tuning experiments: 4, 8, 16
     }
     if (a.orbit) {
-        if (a.xr != nullptr) {
+        if (a.v.xr != nullptr) {
             if (un == 4) sector_orbit_launch_t<true, 4>(a, s);
             else         sector_orbit_launch_t<true, 8>(a, s);
         } else {
             if (un == 4) sector_orbit_launch_t<false, 4>(a, s);
             else         sector_orbit_launch_t<false, 8>(a, s);
         }
-    } else if (a.xr != nullptr) {
+    } else if (a.v.xr != nullptr) {
         if (un == 4)       sector_launch_t<true, 4>(a, s);
         else if (un == 16) sector_launch_t<true, 16>(a, s);
         else               sector_launch_t<true, 8>(a, s);
@@ -516,12 +516,12 @@ int launch_mf_sector(const MfSecArgs &a, hipStream_t s, int *nparts_out)
     QBH_HIP(hipGetLastError());
     if (a.n_rrows > 0) {
         const int rg = blas_grid(a.n_rrows * 8);
-        if (a.xr != nullptr) hipLaunchKernelGGL(k_sec_remainder<true>, dim3(rg), dim3(256), 0, s, a);
+        if (a.v.xr != nullptr) hipLaunchKernelGGL(k_sec_remainder<true>, dim3(rg), dim3(256), 0, s, a);
         else                 hipLaunchKernelGGL(k_sec_remainder<false>, dim3(rg), dim3(256), 0, s, a);
         QBH_HIP(hipGetLastError());
     }
     const int parts = blas_grid(a.dim);
-    if (a.partials != nullptr) {
+    if (a.v.partials != nullptr) {
         hipLaunchKernelGGL(k_sec_reduce, dim3(parts), dim3(256), 0, s, a);
         QBH_HIP(hipGetLastError());
     }

@@ -20,11 +20,11 @@
 // (4 six-bit chunks per field) and 64 translations they take at most 138,816 B.  The term arrays, the characters and the
 // permutations are read through the device copy of KondoReprDev (uniform over the lanes, cached).
 #include "qbh_sector.hpp"
+#include "qbh_mf_row.hpp"
 
 namespace qbh {
 namespace {
 
-static_assert(kSectorChunk == 1 << 12, "krepr_find shifts a rank by 12 bits to its chunk");
 constexpr int kKondoTabEntries = kKondoTab * kKondoTab;
 constexpr size_t kMfKreprLdsCap = (size_t)150 * 1024;         // the budget of launch_mf_heis
 constexpr size_t kMfKreprLdsMax =
@@ -71,24 +71,6 @@ __device__ __forceinline__ void krepr_stage(const MfKondoRepr &t, const KondoRep
     binom = A + kKondoTabEntries;
 }
 
-// position of representative b = (u, d, s) in reps[0, dim): the directory entry of its chunk of ranks, then a bisection
-// among that chunk's representatives.  b is a representative, so this is sector_find(reps, dim, b); the result stays below
-// dim for any word.
-__device__ __forceinline__ int64_t krepr_find(const KondoDev &K, const uint64_t *A, const uint64_t *binom, const uint64_t *reps,
-                                              const int64_t *chunk_pos, int64_t dim, uint64_t b)
-{
-    const int nb = K.n_sites;
-    const uint64_t mlow = (1ULL << nb) - 1ULL;
-    const uint64_t c = kd_rank(K, A, binom, b & mlow, (b >> nb) & mlow, b >> (2 * nb)) >> 12;
-    int64_t lo = chunk_pos[c], hi = chunk_pos[c + 1];
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (reps[mid] < b) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < dim ? lo : dim - 1;
-}
-
 // the terms of the row of representative a (|S_a| = sa, nonzero norm) in the order of kondo_row: sink(position of b, value)
 // for every off-diagonal term entry whose target has nonzero norm; returns the diagonal of the row's own word
 template <class Sink>
@@ -103,28 +85,20 @@ __device__ __forceinline__ d2 krepr_walk(const KondoReprDev &R, const uint64_t *
         int g = 0;
         const uint64_t b = sector_canonical(R, tab, c, &g);
         const int pt = g ? sector_parity(R, g, c) : 0;
-        const int64_t lo = krepr_find(R.k, A, binom, reps, chunk_pos, dim, b);
+        const int64_t lo = sector_dir_find(reps, chunk_pos, dim, b, kd_rank(R.k, A, binom, b & mlow, (b >> nb) & mlow, b >> (2 * nb)));
         const uint8_t cj = info[lo];
         if (cj & 0x80) return;            // zero-norm target: dropped
         sink(lo, kondo_repr_value(R, code, g, pt, cj, sa));
     });
 }
 
-__device__ __forceinline__ double krepr_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // y <- alpha H x + beta y + gamma x on rows [row_begin, row_begin + nrows) of the sector: one lane per row, grid-stride over
-// a resident grid, every row gathers (no atomics).  Epilogue and partial sums as k_mf_qudit_repr.
+// a resident grid, every row gathers (no atomics).  Epilogue and partial sums: qbh_mf_row.hpp.
 template <bool REALX, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr(MfKondoReprArgs a)
+__global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr(MfKondoRepr t, MfVec a)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t kr_lds[];
     __shared__ double red[3 * (BLOCK / 64)];
-    const MfKondoRepr &t = a.t;
     const KondoReprDev &R = *static_cast<const KondoReprDev *>(t.R);
     const int tid = threadIdx.x;
     const uint64_t *tab, *A, *binom;
@@ -134,55 +108,19 @@ __global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr(MfKondoReprArgs a)
     for (int64_t lrow = (int64_t)blockIdx.x * BLOCK + tid; lrow < a.nrows; lrow += stride) {
         const int64_t grow = a.row_begin + lrow;
         const uint8_t ci = t.info[grow];
-        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-        if (a.y_re != nullptr) {
-            if (a.beta != 0.0) yo.x = a.y_re[lrow];
-            xi.x = a.xr[grow];
-        } else {
-            if (a.beta != 0.0) yo = a.y[lrow];
-            if (REALX) xi.x = a.xr[grow];
-            else       xi = a.xg[grow];
-        }
+        d2 yo, xi;
+        mf_row_load<REALX>(a, lrow, grow, yo, xi);
         d2 sum = {0.0, 0.0};
         d2 dg;
         if (ci & 0x80) {                  // zero norm at this momentum: the decoupled row of row_zero_norm
             dg = d2{R.fake_pos + (double)grow / (double)t.dim, 0.0};
         } else {
-            dg = krepr_walk(R, tab, A, binom, t.reps, t.info, t.chunk_pos, t.dim, t.reps[grow], (double)(ci & 0x7f), [&](int64_t lo, d2 v) {
-                if (REALX) {
-                    sum.x += v.x * a.xr[lo];
-                } else {
-                    const d2 x = a.xg[lo];
-                    sum.x += v.x * x.x - v.y * x.y;
-                    sum.y += v.x * x.y + v.y * x.x;
-                }
-            });
+            dg = krepr_walk(R, tab, A, binom, t.reps, t.info, t.chunk_pos, t.dim, t.reps[grow], (double)(ci & 0x7f),
+                            [&](int64_t lo, d2 v) { mf_gather_add<REALX>(a, sum, v, lo); });
         }
-        sum += dg.x * xi;                 // the diagonal of a word is real by construction (kondo_setup drops Im of a number term)
-        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-        else                   a.y[lrow] = yn;
-        acc[0] += xi.x * yn.x + xi.y * yn.y;
-        acc[1] += xi.x * yn.y - xi.y * yn.x;
-        acc[2] += yn.x * yn.x + yn.y * yn.y;
+        mf_row_finish(a, lrow, sum, dg.x, xi, yo, acc);      // the diagonal of a word is real by construction (kondo_setup drops Im of a number term)
     }
-    if (a.partials != nullptr) {
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = krepr_wave_sum(acc[c]);
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c * (BLOCK / 64) + wave] = acc[c];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < 3; ++c) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < BLOCK / 64; ++w2) v += red[c * (BLOCK / 64) + w2];
-                a.partials[(size_t)blockIdx.x * 3 + c] = v;
-            }
-        }
-    }
+    mf_block_partials<BLOCK>(acc, red, a.partials);
 }
 
 // the contributions the apply kernel makes for rows [row_begin, row_end): one diagonal per row and every off-diagonal term
@@ -204,15 +142,7 @@ __global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr_count(MfKondoRepr t, in
             (void)krepr_walk(R, tab, A, binom, t.reps, t.info, t.chunk_pos, t.dim, t.reps[row], (double)(ci & 0x7f),
                              [&](int64_t, d2) { c += 1; });
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long v = 0;
-        for (int w = 0; w < BLOCK / 64; ++w) v += red[w];
-        part[blockIdx.x] = v;
-    }
+    mf_block_count<BLOCK>(c, red, part);
 }
 
 template <class Kernel, class... Args>
@@ -226,17 +156,17 @@ hipError_t krepr_launch(Kernel k, int grid, int block, size_t lds, hipStream_t s
 
 }  // namespace
 
-int launch_mf_kondo_repr(const MfKondoReprArgs &a, hipStream_t s, int *nparts_out)
+int launch_mf_kondo_repr(const MfKondoRepr &t, const MfVec &a, hipStream_t s, int *nparts_out)
 {
-    const size_t lds = mf_krepr_lds_bytes(a.t);
-    const int g = mf_krepr_grid(a.t, a.nrows);
+    const size_t lds = mf_krepr_lds_bytes(t);
+    const int g = mf_krepr_grid(t, a.nrows);
     const bool rx = a.xr != nullptr;
-    if (mf_krepr_large(a.t)) {
-        if (rx) QBH_HIP(krepr_launch(k_mf_kondo_repr<true, kMfKreprBlockL>, g, kMfKreprBlockL, lds, s, a));
-        else    QBH_HIP(krepr_launch(k_mf_kondo_repr<false, kMfKreprBlockL>, g, kMfKreprBlockL, lds, s, a));
+    if (mf_krepr_large(t)) {
+        if (rx) QBH_HIP(krepr_launch(k_mf_kondo_repr<true, kMfKreprBlockL>, g, kMfKreprBlockL, lds, s, t, a));
+        else    QBH_HIP(krepr_launch(k_mf_kondo_repr<false, kMfKreprBlockL>, g, kMfKreprBlockL, lds, s, t, a));
     } else {
-        if (rx) QBH_HIP(krepr_launch(k_mf_kondo_repr<true, kMfKreprBlockS>, g, kMfKreprBlockS, lds, s, a));
-        else    QBH_HIP(krepr_launch(k_mf_kondo_repr<false, kMfKreprBlockS>, g, kMfKreprBlockS, lds, s, a));
+        if (rx) QBH_HIP(krepr_launch(k_mf_kondo_repr<true, kMfKreprBlockS>, g, kMfKreprBlockS, lds, s, t, a));
+        else    QBH_HIP(krepr_launch(k_mf_kondo_repr<false, kMfKreprBlockS>, g, kMfKreprBlockS, lds, s, t, a));
     }
     if (nparts_out) *nparts_out = g;
     return QBH_OK;
@@ -313,29 +243,23 @@ extern "C" int qbh_mf_kondo_repr(qbh_csr **out, int n_sites, int n_elec, int two
     t.chunk_pos = d_pos;
     t.dim = dim;
     t.n_tab = (int)tab.size();
-    if (mf_krepr_lds_bytes(t) > kMfKreprLdsMax || bufs.pool.size() > sizeof(t.own) / sizeof(t.own[0])) {
-        set_error("%s: internal: %d table words, %d device arrays to hand over", who, t.n_tab, (int)bufs.pool.size());
+    if (mf_krepr_lds_bytes(t) > kMfKreprLdsMax) {
+        set_error("%s: internal: %d table words", who, t.n_tab);
         return QBH_EHIP;
     }
-    for (void *p : bufs.pool) t.own[t.n_own++] = p;
-    t.bytes = (int64_t)(sizeof(KondoReprDev) + tab.size() * 8) + dim * 9 + (nchunks + 1) * 8;
+    const int64_t bytes = (int64_t)(sizeof(KondoReprDev) + tab.size() * 8) + dim * 9 + (nchunks + 1) * 8;      // tables + representatives + info bytes + directory
 
     const int64_t nrows = row_end - row_begin;
     const int cgrid = mf_krepr_grid(t, nrows);
     const size_t lds = mf_krepr_lds_bytes(t);
-    unsigned long long *d_part = nullptr;
-    QBH_HIP_WHO(who, qbh::dev_alloc(&d_part, (size_t)cgrid * sizeof(unsigned long long)));
-    hipError_t ce = mf_krepr_large(t)
-                        ? krepr_launch(k_mf_kondo_repr_count<kMfKreprBlockL>, cgrid, kMfKreprBlockL, lds, (hipStream_t)0, t, row_begin, row_end, d_part)
-                        : krepr_launch(k_mf_kondo_repr_count<kMfKreprBlockS>, cgrid, kMfKreprBlockS, lds, (hipStream_t)0, t, row_begin, row_end, d_part);
-    std::vector<unsigned long long> part((size_t)cgrid);
-    if (ce == hipSuccess) ce = hipMemcpy(part.data(), d_part, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d_part);
-    QBH_HIP_WHO(who, ce);
     int64_t nnz = 0;
-    for (unsigned long long v : part) nnz += (int64_t)v;
+    QBH_TRY(sector_count_entries(who, cgrid, &nnz, [&](unsigned long long *d_part) {
+        return mf_krepr_large(t)
+                   ? krepr_launch(k_mf_kondo_repr_count<kMfKreprBlockL>, cgrid, kMfKreprBlockL, lds, (hipStream_t)0, t, row_begin, row_end, d_part)
+                   : krepr_launch(k_mf_kondo_repr_count<kMfKreprBlockS>, cgrid, kMfKreprBlockS, lds, (hipStream_t)0, t, row_begin, row_end, d_part);
+    }));
 
-    const int rc = adopt_mf_kondo_repr(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    const int rc = adopt_mf(out, 7, &qbh_csr::mfkr, t, bufs.pool, bytes, values_real, nrows, dim, row_begin, nnz, opts);
     if (rc == QBH_OK) bufs.release();     // the handle owns the tables, the representatives and the directory now
     return rc;
 }

@@ -14,31 +14,15 @@
 // representatives, and a bisection of at most 12 steps inside those (at most 32 KB, contiguous) ends at what sector_find
 // returns from 31 steps over the whole list.
 #include "qbh_sector.hpp"
+#include "qbh_mf_row.hpp"
 
 namespace qbh {
 namespace {
 
-static_assert(kSectorChunk == 1 << 12, "qrepr_find shifts a rank by 12 bits to its chunk");
 constexpr int kMfQreprBlock = 1024;      // one workgroup per CU when the tables fill LDS: 4 waves per SIMD
 constexpr size_t kMfQreprLdsCap = (size_t)150 * 1024;        // the budget of launch_mf_heis
 
 inline size_t mf_qrepr_lds_bytes(const MfQuditRepr &t) { return t.tables_lds ? ((size_t)t.n_tab + (size_t)t.n_cum) * 8 : 0; }
-
-// position of representative b in reps[0, dim): the directory entry of its chunk of ranks, then a bisection among that
-// chunk's representatives.  b is a representative, so this is sector_find(reps, dim, b); the result stays below dim for
-// any word.
-__device__ __forceinline__ int64_t qrepr_find(const QuditReprDev &R, const uint64_t *cum, const uint64_t *reps, const int64_t *chunk_pos,
-                                              int64_t dim, uint64_t b)
-{
-    const uint64_t c = qd_rank(cum, R.n_sites, R.bits, R.tw, b) >> 12;
-    int64_t lo = chunk_pos[c], hi = chunk_pos[c + 1];
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (reps[mid] < b) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < dim ? lo : dim - 1;
-}
 
 // the terms of the row of representative a (|S_a| = sa, nonzero norm) in the order of qrepr_row: sink(position of b, value)
 // for every off-diagonal term entry whose target has nonzero norm; returns the diagonal of the single-site and pair terms
@@ -60,7 +44,7 @@ __device__ __forceinline__ double qrepr_walk(const QuditReprDev &R, const uint64
             const uint64_t c = qrepr_target(a, R.bits, field, si, sj, R.eout[e]);
             int g = 0;
             const uint64_t b = sector_canonical(R, tab, c, &g);
-            const int64_t lo = qrepr_find(R, cum, reps, chunk_pos, dim, b);
+            const int64_t lo = sector_dir_find(reps, chunk_pos, dim, b, qd_rank(cum, R.n_sites, R.bits, R.tw, b));
             const uint8_t cj = info[lo];
             if (cj & 0x80) continue;      // zero-norm target: dropped
             sink(lo, qrepr_value(R, R.eval[e], g, cj, sa));
@@ -85,21 +69,13 @@ __device__ __forceinline__ void qrepr_stage(const MfQuditRepr &t, uint64_t *lds,
     }
 }
 
-__device__ __forceinline__ double qrepr_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // y <- alpha H x + beta y + gamma x on rows [row_begin, row_begin + nrows) of the sector: one lane per row, grid-stride over
-// a resident grid, every row gathers (no atomics).  Epilogue and partial sums as k_mf_qudit.
+// a resident grid, every row gathers (no atomics).  Epilogue and partial sums: qbh_mf_row.hpp.
 template <bool REALX, bool TLDS>
-__global__ __launch_bounds__(kMfQreprBlock) void k_mf_qudit_repr(MfQuditReprArgs a)
+__global__ __launch_bounds__(kMfQreprBlock) void k_mf_qudit_repr(MfQuditRepr t, MfVec a)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t qr_lds[];
     __shared__ double red[3 * (kMfQreprBlock / 64)];
-    const MfQuditRepr &t = a.t;
     const QuditReprDev &R = *static_cast<const QuditReprDev *>(t.R);
     const int tid = threadIdx.x;
     const uint64_t *tab, *cum;
@@ -109,55 +85,19 @@ __global__ __launch_bounds__(kMfQreprBlock) void k_mf_qudit_repr(MfQuditReprArgs
     for (int64_t lrow = (int64_t)blockIdx.x * kMfQreprBlock + tid; lrow < a.nrows; lrow += stride) {
         const int64_t grow = a.row_begin + lrow;
         const uint8_t ci = t.info[grow];
-        d2 yo = {0.0, 0.0}, xi = {0.0, 0.0};
-        if (a.y_re != nullptr) {
-            if (a.beta != 0.0) yo.x = a.y_re[lrow];
-            xi.x = a.xr[grow];
-        } else {
-            if (a.beta != 0.0) yo = a.y[lrow];
-            if (REALX) xi.x = a.xr[grow];
-            else       xi = a.xg[grow];
-        }
+        d2 yo, xi;
+        mf_row_load<REALX>(a, lrow, grow, yo, xi);
         d2 sum = {0.0, 0.0};
         double dg;
         if (ci & 0x80) {                  // zero norm at this momentum: the decoupled row of row_zero_norm
             dg = R.fake_pos + (double)grow / (double)t.dim;
         } else {
-            dg = qrepr_walk(R, tab, cum, t.reps, t.info, t.chunk_pos, t.dim, t.reps[grow], (double)(ci & 0x7f), [&](int64_t lo, d2 v) {
-                if (REALX) {
-                    sum.x += v.x * a.xr[lo];
-                } else {
-                    const d2 x = a.xg[lo];
-                    sum.x += v.x * x.x - v.y * x.y;
-                    sum.y += v.x * x.y + v.y * x.x;
-                }
-            });
+            dg = qrepr_walk(R, tab, cum, t.reps, t.info, t.chunk_pos, t.dim, t.reps[grow], (double)(ci & 0x7f),
+                            [&](int64_t lo, d2 v) { mf_gather_add<REALX>(a, sum, v, lo); });
         }
-        sum += dg * xi;
-        const d2 yn = a.alpha * sum + a.beta * yo + a.gamma * xi;
-        if (a.y_re != nullptr) a.y_re[lrow] = yn.x;
-        else                   a.y[lrow] = yn;
-        acc[0] += xi.x * yn.x + xi.y * yn.y;
-        acc[1] += xi.x * yn.y - xi.y * yn.x;
-        acc[2] += yn.x * yn.x + yn.y * yn.y;
+        mf_row_finish(a, lrow, sum, dg, xi, yo, acc);
     }
-    if (a.partials != nullptr) {
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = qrepr_wave_sum(acc[c]);
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c * (kMfQreprBlock / 64) + wave] = acc[c];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < 3; ++c) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < kMfQreprBlock / 64; ++w2) v += red[c * (kMfQreprBlock / 64) + w2];
-                a.partials[(size_t)blockIdx.x * 3 + c] = v;
-            }
-        }
-    }
+    mf_block_partials<kMfQreprBlock>(acc, red, a.partials);
 }
 
 // the contributions the apply kernel makes for rows [row_begin, row_end): one diagonal per row and every off-diagonal term
@@ -180,15 +120,7 @@ __global__ __launch_bounds__(kMfQreprBlock) void k_mf_qudit_repr_count(MfQuditRe
             (void)qrepr_walk(R, tab, cum, t.reps, t.info, t.chunk_pos, t.dim, t.reps[row], (double)(ci & 0x7f),
                              [&](int64_t, d2) { c += 1; });
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long v = 0;
-        for (int w = 0; w < kMfQreprBlock / 64; ++w) v += red[w];
-        part[blockIdx.x] = v;
-    }
+    mf_block_count<kMfQreprBlock>(c, red, part);
 }
 
 // the resident grid of both kernels: as many workgroups per CU as the LDS they stage allows (at most two of 1024 lanes)
@@ -202,17 +134,17 @@ inline int mf_qrepr_grid(const MfQuditRepr &t, int64_t nrows)
 
 }  // namespace
 
-int launch_mf_qudit_repr(const MfQuditReprArgs &a, hipStream_t s, int *nparts_out)
+int launch_mf_qudit_repr(const MfQuditRepr &t, const MfVec &a, hipStream_t s, int *nparts_out)
 {
-    const bool tl = a.t.tables_lds != 0;
-    const size_t lds = mf_qrepr_lds_bytes(a.t);
-    const int g = mf_qrepr_grid(a.t, a.nrows);
+    const bool tl = t.tables_lds != 0;
+    const size_t lds = mf_qrepr_lds_bytes(t);
+    const int g = mf_qrepr_grid(t, a.nrows);
 #define QBH_QREPR_LAUNCH(RX, TL)                                                                                                        \
     do {                                                                                                                               \
         if (TL)                                                                                                                        \
             QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_qudit_repr<RX, TL>),                                       \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                        \
-        hipLaunchKernelGGL((k_mf_qudit_repr<RX, TL>), dim3(g), dim3(kMfQreprBlock), lds, s, a);                                         \
+        hipLaunchKernelGGL((k_mf_qudit_repr<RX, TL>), dim3(g), dim3(kMfQreprBlock), lds, s, t, a);                                     \
     } while (0)
     if (a.xr != nullptr) {
         if (tl) QBH_QREPR_LAUNCH(true, true); else QBH_QREPR_LAUNCH(true, false);
@@ -317,39 +249,27 @@ extern "C" int qbh_mf_qudit_repr(qbh_csr **out, int n_sites, int d, int total, i
     t.n_tab = (int)tab.size();
     t.n_cum = n_sites * R.tw;
     t.tables_lds = ((size_t)t.n_tab + (size_t)t.n_cum) * 8 <= kMfQreprLdsCap ? 1 : 0;
-    if (bufs.pool.size() > sizeof(t.own) / sizeof(t.own[0])) {
-        set_error("%s: internal: %d device arrays to hand over", who, (int)bufs.pool.size());
-        return QBH_EHIP;
-    }
-    for (void *p : bufs.pool) t.own[t.n_own++] = p;
-    t.bytes = (int64_t)(sizeof(QuditReprDev) + tab.size() * 8 + (size_t)t.n_cum * 8 + T.pair_ij.size() * 4 + T.eoff.size() * 4 +
+    const int64_t bytes = (int64_t)(sizeof(QuditReprDev) + tab.size() * 8 + (size_t)t.n_cum * 8 + T.pair_ij.size() * 4 + T.eoff.size() * 4 +
                         T.eout.size() * 4 + T.pdiag.size() * 8 + T.sdiag.size() * 8 + T.eval.size() * 16) +
-              dim * 9 + (nchunks + 1) * 8;
+                          dim * 9 + (nchunks + 1) * 8;      // tables + representatives + info bytes + directory
 
     const int64_t nrows = row_end - row_begin;
     const int cgrid = mf_qrepr_grid(t, nrows);
     const size_t lds = mf_qrepr_lds_bytes(t);
-    unsigned long long *d_part = nullptr;
-    QBH_HIP_WHO(who, qbh::dev_alloc(&d_part, (size_t)cgrid * sizeof(unsigned long long)));
-    hipError_t ce;
-    if (t.tables_lds) {
-        ce = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_qudit_repr_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds);
-        if (ce == hipSuccess)
-            hipLaunchKernelGGL(k_mf_qudit_repr_count<true>, dim3(cgrid), dim3(kMfQreprBlock), lds, 0, t, row_begin, row_end, d_part);
-    } else {
-        ce = hipSuccess;
-        hipLaunchKernelGGL(k_mf_qudit_repr_count<false>, dim3(cgrid), dim3(kMfQreprBlock), 0, 0, t, row_begin, row_end, d_part);
-    }
-    std::vector<unsigned long long> part((size_t)cgrid);
-    if (ce == hipSuccess) ce = hipGetLastError();
-    if (ce == hipSuccess) ce = hipMemcpy(part.data(), d_part, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d_part);
-    QBH_HIP_WHO(who, ce);
     int64_t nnz = 0;
-    for (unsigned long long v : part) nnz += (int64_t)v;
+    QBH_TRY(sector_count_entries(who, cgrid, &nnz, [&](unsigned long long *d_part) {
+        if (t.tables_lds) {
+            const hipError_t ce = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mf_qudit_repr_count<true>),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (ce != hipSuccess) return ce;
+            hipLaunchKernelGGL(k_mf_qudit_repr_count<true>, dim3(cgrid), dim3(kMfQreprBlock), lds, 0, t, row_begin, row_end, d_part);
+        } else {
+            hipLaunchKernelGGL(k_mf_qudit_repr_count<false>, dim3(cgrid), dim3(kMfQreprBlock), 0, 0, t, row_begin, row_end, d_part);
+        }
+        return hipGetLastError();
+    }));
 
-    const int rc = adopt_mf_qudit_repr(out, t, values_real, nrows, dim, row_begin, nnz, opts);
+    const int rc = adopt_mf(out, 6, &qbh_csr::mfqr, t, bufs.pool, bytes, values_real, nrows, dim, row_begin, nnz, opts);
     if (rc == QBH_OK) bufs.release();     // the handle owns the tables, the representatives and the directory now
     return rc;
 }

@@ -589,56 +589,55 @@ int spmv_run(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double g
             }
             if (packed && !realm) QBH_TRY(expand_packed());
         }
-        qbh::MfArgs m{};
-        m.t = A->mf;
-        m.row_begin = A->row_offset;
-        m.nrows = A->nrows;
-        m.xg = xg;
-        m.xl = xl;
-        m.xr = realm ? (A->has_comm ? A->comm.d_xfull_r : xr_nocomm) : nullptr;
-        m.y = y;
-        m.y_re = A->has_comm ? nullptr : A->ovr_yr;
-        m.alpha = alpha;
-        m.beta = beta;
-        m.gamma = gamma;
-        m.partials = red ? A->d_partials : nullptr;
+        qbh::MfVec v{};
+        v.row_begin = A->row_offset;
+        v.nrows = A->nrows;
+        v.xg = xg;
+        v.xl = xl;
+        v.xr = realm ? (A->has_comm ? A->comm.d_xfull_r : xr_nocomm) : nullptr;
+        v.y = y;
+        v.y_re = A->has_comm ? nullptr : A->ovr_yr;
+        v.alpha = alpha;
+        v.beta = beta;
+        v.gamma = gamma;
+        v.partials = red ? A->d_partials : nullptr;
         const bool profm = A->opts.profile != 0;
         if (profm) {
             QBH_TRY(next_event_set(A));
             QBH_HIP(hipEventRecord(A->ev0, A->stream));
         }
         int mf_parts = A->grid;
-        if (A->kind == 3) {
+        switch (A->kind) {
+        case 1: QBH_TRY(qbh::launch_mf_hubbard(qbh::MfArgs{A->mf, v}, A->grid, A->stream, &mf_parts)); break;
+        case 2: QBH_TRY(qbh::launch_mf_heis(A->mfh, v, A->stream, &mf_parts)); break;
+        case 4: QBH_TRY(qbh::launch_mf_qudit(A->mfq, v, A->stream, &mf_parts)); break;
+        case 5: QBH_TRY(qbh::launch_mf_kondo(A->mfk, v, A->stream, &mf_parts)); break;
+        case 6: QBH_TRY(qbh::launch_mf_qudit_repr(A->mfqr, v, A->stream, &mf_parts)); break;
+        case 7: QBH_TRY(qbh::launch_mf_kondo_repr(A->mfkr, v, A->stream, &mf_parts)); break;
+        case 3: {
+            const qbh::MfSec &t = *A->mfsec;
             qbh::MfSecArgs ms{};
             ms.t = A->d_mfsec;
-            ms.n_items = A->mfsec->n_items;
+            ms.n_items = t.n_items;
             ms.dim = A->nrows;
-            ms.n_rrows = A->mfsec->n_rrows;
-            ms.rrow = A->mfsec->rrow;
-            ms.ria = A->mfsec->ria;
-            ms.rja = A->mfsec->rja;
-            ms.rval = A->mfsec->rval;
-            ms.xg = m.xg;
-            ms.xl = m.xl;
-            ms.xr = m.xr;
-            ms.xl_re = m.y_re ? xr_nocomm : nullptr;
-            ms.y = m.y;
-            ms.y_re = m.y_re;
-            ms.alpha = alpha;
-            ms.beta = beta;
-            ms.gamma = gamma;
-            ms.partials = m.partials;
-            ms.orbit = A->mfsec->orbit;
-            ms.ucfg = A->mfsec->ucfg;
-            ms.oid = A->mfsec->oid;
-            ms.utab = A->mfsec->utab;
-            ms.oek = A->mfsec->oek;
-            ms.uext = A->mfsec->uext;
-            ms.tpar = A->mfsec->tpar;
-            ms.usgn = A->mfsec->usgn;
-            ms.n_orb = A->mfsec->n_orb;
-            ms.w_orb = A->mfsec->w_orb;
-            ms.tile = A->mfsec->tile;
+            ms.n_rrows = t.n_rrows;
+            ms.rrow = t.rrow;
+            ms.ria = t.ria;
+            ms.rja = t.rja;
+            ms.rval = t.rval;
+            ms.v = v;
+            ms.xl_re = v.y_re ? xr_nocomm : nullptr;
+            ms.orbit = t.orbit;
+            ms.ucfg = t.ucfg;
+            ms.oid = t.oid;
+            ms.utab = t.utab;
+            ms.oek = t.oek;
+            ms.uext = t.uext;
+            ms.tpar = t.tpar;
+            ms.usgn = t.usgn;
+            ms.n_orb = t.n_orb;
+            ms.w_orb = t.w_orb;
+            ms.tile = t.tile;
             // items drawn from per-XCD counters: the orbit-order kernel by default (its workgroups finish far apart under a
             // static assignment: 87 -> 61 ms on 4x5 with 8+8), the rank-table kernel only on request (it got slower: 223 -> 233 ms)
             const int sec_walk = A->dbg.sec_walk < 0 ? (ms.orbit ? 1 : 0) : A->dbg.sec_walk;
@@ -648,83 +647,11 @@ int spmv_run(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double g
                 ms.ctr = reinterpret_cast<unsigned int *>(A->d_wctr);
             }
             QBH_TRY(qbh::launch_mf_sector(ms, A->stream, &mf_parts));
-        } else if (A->kind == 2) {
-            qbh::MfHeisArgs h{};
-            h.t = A->mfh;
-            h.row_begin = m.row_begin;
-            h.nrows = m.nrows;
-            h.xg = m.xg;
-            h.xl = m.xl;
-            h.xr = m.xr;
-            h.y = m.y;
-            h.y_re = m.y_re;
-            h.alpha = alpha;
-            h.beta = beta;
-            h.gamma = gamma;
-            h.partials = m.partials;
-            QBH_TRY(qbh::launch_mf_heis(h, A->stream, &mf_parts));
-        } else if (A->kind == 4) {
-            qbh::MfQuditArgs h{};
-            h.t = A->mfq;
-            h.row_begin = m.row_begin;
-            h.nrows = m.nrows;
-            h.xg = m.xg;
-            h.xl = m.xl;
-            h.xr = m.xr;
-            h.y = m.y;
-            h.y_re = m.y_re;
-            h.alpha = alpha;
-            h.beta = beta;
-            h.gamma = gamma;
-            h.partials = m.partials;
-            QBH_TRY(qbh::launch_mf_qudit(h, A->stream, &mf_parts));
-        } else if (A->kind == 5) {
-            qbh::MfKondoArgs h{};
-            h.t = A->mfk;
-            h.row_begin = m.row_begin;
-            h.nrows = m.nrows;
-            h.xg = m.xg;
-            h.xl = m.xl;
-            h.xr = m.xr;
-            h.y = m.y;
-            h.y_re = m.y_re;
-            h.alpha = alpha;
-            h.beta = beta;
-            h.gamma = gamma;
-            h.partials = m.partials;
-            QBH_TRY(qbh::launch_mf_kondo(h, A->stream, &mf_parts));
-        } else if (A->kind == 6) {
-            qbh::MfQuditReprArgs h{};
-            h.t = A->mfqr;
-            h.row_begin = m.row_begin;
-            h.nrows = m.nrows;
-            h.xg = m.xg;
-            h.xl = m.xl;
-            h.xr = m.xr;
-            h.y = m.y;
-            h.y_re = m.y_re;
-            h.alpha = alpha;
-            h.beta = beta;
-            h.gamma = gamma;
-            h.partials = m.partials;
-            QBH_TRY(qbh::launch_mf_qudit_repr(h, A->stream, &mf_parts));
-        } else if (A->kind == 7) {
-            qbh::MfKondoReprArgs h{};
-            h.t = A->mfkr;
-            h.row_begin = m.row_begin;
-            h.nrows = m.nrows;
-            h.xg = m.xg;
-            h.xl = m.xl;
-            h.xr = m.xr;
-            h.y = m.y;
-            h.y_re = m.y_re;
-            h.alpha = alpha;
-            h.beta = beta;
-            h.gamma = gamma;
-            h.partials = m.partials;
-            QBH_TRY(qbh::launch_mf_kondo_repr(h, A->stream, &mf_parts));
-        } else {
-            QBH_TRY(qbh::launch_mf_hubbard(m, A->grid, A->stream, &mf_parts));
+            break;
+        }
+        default:
+            qbh::set_error("internal: operator kind %d has no matrix-free kernel", A->kind);
+            return QBH_EUNSUPP;
         }
         if (profm) {
             QBH_HIP(hipEventRecord(A->ev1, A->stream));
@@ -831,14 +758,14 @@ int spmv_run(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double g
             // no tiled copy, no far sums: x read (+ its neighbour rows through the caches), old y read, y written
             qbh::MfArgs m{};
             m.t = K.tables;
-            m.row_begin = 0;
-            m.nrows = A->nrows;
-            m.xr = a.xr;
-            m.y_re = a.y_re;
-            m.alpha = a.alpha;
-            m.beta = a.beta;
-            m.gamma = a.gamma;
-            m.partials = red ? A->d_partials : nullptr;
+            m.v.row_begin = 0;
+            m.v.nrows = A->nrows;
+            m.v.xr = a.xr;
+            m.v.y_re = a.y_re;
+            m.v.alpha = a.alpha;
+            m.v.beta = a.beta;
+            m.v.gamma = a.gamma;
+            m.v.partials = red ? A->d_partials : nullptr;
             m.dcode = K.sl.dcode;
             m.ddict = K.sl.d_dictr;
             K.xt_of = nullptr;
