@@ -926,6 +926,51 @@ int qbh_mf_kondo_repr(qbh_csr **out, int n_sites, int n_elec, int two_sz,
 int qbh_mopr_diag_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int n_trans, const int32_t *perms,
                                  const double *chars_new, const qbh_z *coef_up, const qbh_z *coef_dn, const qbh_z *coef_spin,
                                  const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_out);
+/* Operators that take a Kondo-lattice vector to another sector: vec_new = sum_s coef[s] O_s vec_old in the basis of
+ * qbh_gen_kondo / qbh_mf_kondo (ascending words w = u | d << n | s << 2n; operator string: all up operators, then all down
+ * operators, sites ascending; the local spins commute with everything).
+ *     op                        O_s                                        target sector
+ *     0 QBH_KONDO_C_UP          c_{s,up}                                   (n_elec - 1, two_sz - 1)
+ *     1 QBH_KONDO_C_DN          c_{s,dn}                                   (n_elec - 1, two_sz + 1)
+ *     2 QBH_KONDO_CDAG_UP       c^dag_{s,up}                               (n_elec + 1, two_sz + 1)
+ *     3 QBH_KONDO_CDAG_DN       c^dag_{s,dn}                               (n_elec + 1, two_sz - 1)
+ *     4 QBH_KONDO_SPIN_PLUS     coef_elec[s] s^+_s + coef_spin[s] S^+_s    (n_elec, two_sz + 2)
+ *     5 QBH_KONDO_SPIN_MINUS    coef_elec[s] s^-_s + coef_spin[s] S^-_s    (n_elec, two_sz - 2)
+ * c_{s,up} |u d s> = (-1)^popcount(u below s) |u \ s, d, s>; c_{s,dn} carries (-1)^(popcount(u) + popcount(d below s)); c^dag
+ * carries the same sign with the orbital empty before it acts; s^+_s = c^dag_{s,up} c_{s,dn} and s^-_s = c^dag_{s,dn} c_{s,up}
+ * (the product applied right to left); S^+_s turns the local spin up (clears bit s of the s field), S^-_s turns it down, both
+ * with element 1.  Ops 0-3 take coef_elec [n_sites] and coef_spin must be NULL.  Ops 4 and 5 take either set or both (a NULL
+ * set is all zero; both NULL: QBH_EINVAL): the electrons' flip, the local spins' flip or the total-spin flip in one call.
+ * Both vectors are device vectors; every target row gathers its contributions in site order (no atomics; two runs are bit
+ * identical) and every element of d_vec_new is written.  Rows and ranks are 64-bit: dim < 2^31 of qbh_gen_kondo does not
+ * apply.  *dim_old_out, *dim_new_out (may be NULL) receive the two sector dimensions.
+ * Order of the checks: arguments (op outside 0..5, a coefficient set the op does not take, a NULL vector: QBH_EINVAL) -> the
+ * shape of the source as in qbh_gen_kondo, then of the target ("the target sector does not exist": QBH_EINVAL) -> a sector of
+ * 2^40 words or more: QBH_EUNSUPP -> only then the device is looked for (QBH_ENODEVICE). */
+#define QBH_KONDO_C_UP       0
+#define QBH_KONDO_C_DN       1
+#define QBH_KONDO_CDAG_UP    2
+#define QBH_KONDO_CDAG_DN    3
+#define QBH_KONDO_SPIN_PLUS  4
+#define QBH_KONDO_SPIN_MINUS 5
+int qbh_mopr_kondo_dev(int n_sites, int n_elec_old, int two_sz_old, int op,
+                       const qbh_z *coef_elec /* [n_sites] or NULL */, const qbh_z *coef_spin /* [n_sites] or NULL */,
+                       const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out, void *stream);
+/* moprXvec_repr (src/model.cc:1715-1846) for the operators of qbh_mopr_kondo_dev between momentum sectors of
+ * qbh_gen_kondo_repr / qbh_mf_kondo_repr.  Contract of qbh_mopr_qudit_repr_dev: the coefficient sets given transform with ONE
+ * character, coef[g(s)] = eta(g) coef[s] for every translation (else QBH_EINVAL), and the operator maps the sector
+ * (n_elec_old, two_sz_old, chars_old) to (target of the table above, chars_old * eta).  Both vectors are device vectors
+ * indexed by all representatives ascending, the order of the sector generators.  Every target representative gathers
+ *     <b, k'| O |a, k> = sum_s w_s sigma(g*) conj(chi_old(g*)) sqrt(|S_a| / |S_b|),   a = g* c,  w_s = coef[s] <b|O_s|c>
+ * in site order (no atomics; two runs are bit identical); target representatives of zero norm receive 0, sources of zero norm
+ * are skipped.  The source is found through the directory of its enumeration, not by a search of the whole list.
+ * Order of the checks: arguments -> the shapes of source and target as above -> the symmetry as in qbh_gen_kondo_repr (more
+ * than 64 translations: QBH_EUNSUPP) -> the coefficient character -> a sector of 2^40 words or more: QBH_EUNSUPP -> only then
+ * the device is looked for (QBH_ENODEVICE).  Below 2^31 representatives per sector remain. */
+int qbh_mopr_kondo_repr_dev(int n_sites, int n_elec_old, int two_sz_old, int op,
+                            int n_trans, const int32_t *perms, const double *chars_old,
+                            const qbh_z *coef_elec /* [n_sites] or NULL */, const qbh_z *coef_spin /* [n_sites] or NULL */,
+                            const qbh_z *d_vec_old, qbh_z *d_vec_new, int64_t *dim_old_out, int64_t *dim_new_out, void *stream);
 /* Measurement harness (SURVEY 7 hard-part 1): the operator of qbh_gen_heisenberg (kind 0) / qbh_gen_hubbard (kind 1), built with
  * complex128 values on one GPU, re-expressed ON THE DEVICE in the reference's own basis order and fermion convention, i.e.
  * exactly the matrix the unchanged host code assembles (src/model.cc:619-685) at sizes that code cannot reach: basis sorted

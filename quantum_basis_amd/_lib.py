@@ -110,6 +110,7 @@ EXPORTS = [
     "qbh_gen_hubbard", "qbh_mf_hubbard", "qbh_gen_heisenberg", "qbh_mf_heisenberg", "qbh_gen_heisenberg_repr", "qbh_gen_hubbard_repr", "qbh_gen_heisenberg_repr_cuts", "qbh_gen_hubbard_repr_cuts", "qbh_mf_hubbard_repr", "qbh_mopr_diag_hubrepr_dev", "qbh_mopr_c_hubrepr_dev", "qbh_csr_download", "qbh_csr_reference_order", "qbh_csr_set_basis",
     "qbh_gen_qudit", "qbh_mf_qudit", "qbh_mopr_qudit_dev", "qbh_gen_qudit_repr", "qbh_gen_qudit_repr_cuts", "qbh_mf_qudit_repr", "qbh_mopr_qudit_repr_dev",
     "qbh_gen_kondo", "qbh_mf_kondo", "qbh_gen_kondo_repr", "qbh_gen_kondo_repr_cuts", "qbh_mf_kondo_repr", "qbh_mopr_diag_kondo_repr_dev",
+    "qbh_mopr_kondo_dev", "qbh_mopr_kondo_repr_dev",
 ]
 
 _lib = None
@@ -246,6 +247,9 @@ def lib():
                                                                       C.POINTER(Opts)]
     L.qbh_mf_kondo_repr.argtypes = [C.POINTER(vp)] + kterms + [C.c_int, vp, vp, dbl, i64, i64, C.POINTER(i64), C.POINTER(Opts)]
     L.qbh_mopr_diag_kondo_repr_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.qbh_mopr_kondo_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
+    L.qbh_mopr_kondo_repr_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
+                                          C.POINTER(i64), vp]
     L.qbh_csr_reference_order.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     _lib = L
     return L

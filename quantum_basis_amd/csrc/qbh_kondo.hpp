@@ -179,4 +179,61 @@ __device__ __forceinline__ d2 kd_row_terms(const KondoDev &K, uint64_t u, uint64
     return dg;
 }
 
+// ---- operators between sectors (qbh_kondo_mopr.hip): O = sum_s coef[s] O_s from (n_elec, two_sz) to another sector ----
+//   op 0 / 1  c_{s,up} / c_{s,dn}           (n_elec - 1, two_sz -/+ 1)        op 2 / 3  c^dag_{s,up} / c^dag_{s,dn}  (n_elec + 1, two_sz +/- 1)
+//   op 4      ce[s] s^+_s + cs[s] S^+_s     (n_elec, two_sz + 2)              op 5      ce[s] s^-_s + cs[s] S^-_s    (n_elec, two_sz - 2)
+// with s^+_s = c^dag_{s,up} c_{s,dn}, s^-_s = c^dag_{s,dn} c_{s,up} (the product applied right to left) and S^+_s turning the
+// local spin up (bit s of the s field cleared).  An electron operator carries (-1)^(operators left of it in the string "all up
+// ascending, then all down ascending"): the particles of its species below s, and for the down species the whole up field.
+constexpr int kKondoMoprOps = 6;
+
+inline void kondo_mopr_target(int op, int n_elec, int two_sz, int *n_elec_new, int *two_sz_new)
+{
+    static const int de[kKondoMoprOps] = {-1, -1, 1, 1, 0, 0}, ds[kKondoMoprOps] = {-1, 1, 1, -1, 2, -2};
+    *n_elec_new = n_elec + de[op];
+    *two_sz_new = two_sz + ds[op];
+}
+
+// For the TARGET word (bu, bd, bs), site s and part (0: the electron operator, 1: the local-spin flip of ops 4 / 5) the SOURCE
+// word (cu, cd, cs) and w = coef <b|O_s|c>, or false.  A row walks the sites ascending, part 0 before part 1.
+struct KondoSiteOp {
+    int n_sites, op;
+    double ce_re[kKondoMaxSites], ce_im[kKondoMaxSites], cs_re[kKondoMaxSites], cs_im[kKondoMaxSites];
+    __host__ __device__ __forceinline__ int parts() const { return op >= 4 ? 2 : 1; }
+    __device__ __forceinline__ bool operator()(uint64_t bu, uint64_t bd, uint64_t bs, int s, int part, uint64_t &cu, uint64_t &cd,
+                                               uint64_t &cs, d2 &w) const
+    {
+        const uint64_t bit = 1ULL << s, low = bit - 1ULL;
+        if (part) {                           // S^+: the target's local spin is up (bit clear); S^-: down; the element is 1
+            const bool down = (bs & bit) != 0;
+            if ((op == 4 ? down : !down) || (cs_re[s] == 0.0 && cs_im[s] == 0.0)) return false;
+            cu = bu;
+            cd = bd;
+            cs = bs ^ bit;
+            w = d2{cs_re[s], cs_im[s]};
+            return true;
+        }
+        if (ce_re[s] == 0.0 && ce_im[s] == 0.0) return false;
+        int par;
+        cs = bs;
+        if (op < 4) {                         // b and c differ in the particle (s, species) alone
+            const int species = op & 1, create = op >> 1;
+            const uint64_t occ = species ? bd : bu;
+            const bool has = (occ & bit) != 0;
+            if (create ? !has : has) return false;
+            par = (species ? __popcll(bu) : 0) + __popcll(occ & low);
+            cu = species ? bu : bu ^ bit;
+            cd = species ? bd ^ bit : bd;
+        } else {                              // s^+: the target holds (s, up) alone, the source (s, dn) alone; s^-: the reverse
+            const bool hu = (bu & bit) != 0, hd = (bd & bit) != 0;
+            if (op == 4 ? (!hu || hd) : (hu || !hd)) return false;
+            par = __popcll(bu & low) + __popcll(bu & ~bit) + __popcll(bd & low);      // as the Kondo flip of kd_row_terms
+            cu = bu ^ bit;
+            cd = bd ^ bit;
+        }
+        w = (par & 1) ? d2{-ce_re[s], -ce_im[s]} : d2{ce_re[s], ce_im[s]};
+        return true;
+    }
+};
+
 }  // namespace qbh

@@ -1013,6 +1013,37 @@ inline int qrepr_invariant(const QuditTerms &T, int n_sites, int d, int n_trans,
     return QBH_OK;
 }
 
+// "the coefficients transform with a character": c_{g(s)} = eta(g) c_s in every one of the n_sets coefficient sets, with one
+// eta for all of them.  eta(g) is read off the coefficient of largest magnitude (the first one on ties; eta = 1 if all
+// vanish), then every set is checked on every site.  perms must be validated already (the family's *_symmetry does it).
+inline int coef_character(const char *who, int n_sites, int n_trans, const int32_t *perms, const qbh_z *const *sets, int n_sets,
+                          std::complex<double> *eta_out)
+{
+    auto at = [&](int q, int s) { return std::complex<double>(sets[q][s].re, sets[q][s].im); };
+    int q0 = 0, s0 = 0;
+    double best = 0.0;
+    for (int q = 0; q < n_sets; ++q)
+        for (int s = 0; s < n_sites; ++s)
+            if (std::abs(at(q, s)) > best) {
+                best = std::abs(at(q, s));
+                q0 = q;
+                s0 = s;
+            }
+    for (int g = 0; g < n_trans; ++g) {
+        const int32_t *pg = perms + (size_t)g * n_sites;
+        const std::complex<double> eta = best > 0.0 ? at(q0, pg[s0]) / at(q0, s0) : 1.0;
+        for (int q = 0; q < n_sets; ++q)
+            for (int s = 0; s < n_sites; ++s)
+                if (std::abs(at(q, pg[s]) - eta * at(q, s)) > 1e-10 * std::max(1.0, best)) {
+                    set_error("%s: the coefficients do not transform with a character under translation %d (set %d, site %d)", who, g,
+                              q, s);
+                    return QBH_EINVAL;
+                }
+        if (eta_out) eta_out[g] = eta;
+    }
+    return QBH_OK;
+}
+
 }  // namespace
 }  // namespace qbh
 

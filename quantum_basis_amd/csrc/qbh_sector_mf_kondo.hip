@@ -16,60 +16,22 @@
 // chunk's first and last representatives, and a bisection of at most 12 steps inside those (at most 32 KB, contiguous) ends at
 // what sector_find returns from 31 steps over the whole list.
 //
-// The translation tables and the two counting tables A and binom of KondoDev are always staged in LDS: with at most 21 sites
-// (4 six-bit chunks per field) and 64 translations they take at most 138,816 B.  The term arrays, the characters and the
-// permutations are read through the device copy of KondoReprDev (uniform over the lanes, cached).
-#include "qbh_sector.hpp"
+// The translation tables and the two counting tables A and binom of KondoDev are always staged in LDS (qbh_kondo_lds.hpp, which
+// also chooses between the two workgroup shapes).  The term arrays, the characters and the permutations are read through the
+// device copy of KondoReprDev (uniform over the lanes, cached).
+#include "qbh_kondo_lds.hpp"
 #include "qbh_mf_row.hpp"
 
 namespace qbh {
 namespace {
 
-constexpr int kKondoTabEntries = kKondoTab * kKondoTab;
-constexpr size_t kMfKreprLdsCap = (size_t)150 * 1024;         // the budget of launch_mf_heis
-constexpr size_t kMfKreprLdsMax =
-    ((size_t)kReprMaxTrans * ((kKondoMaxSites + 5) / 6) * 64 + 2 * (size_t)kKondoTabEntries) * sizeof(uint64_t);
-static_assert(kMfKreprLdsMax == 138816 && kMfKreprLdsMax <= kMfKreprLdsCap,
-              "the translation tables, A and binom of every admissible sector fit LDS: there is no global-memory path");
-
-// Two workgroup shapes for one kernel body.  The compiler reports 85 VGPRs for every instance of the apply kernel (88
-// allocated: 5 waves per SIMD, 20 per CU) and 0 bytes of scratch, so a CU holds at most five workgroups of 256 lanes or one
-// of 1024, and the LDS the tables take (160 KB per CU) decides between them:
-//   four or more workgroups of 256 lanes fit:  256 lanes, min(5, 160 KB / footprint) per CU: 16 or 20 waves per CU
-//   fewer fit (footprint above 40 KB):         1024 lanes, one workgroup per CU: 16 waves per CU instead of 4 to 12
-constexpr int kMfKreprBlockS = 256, kMfKreprBlockL = 1024;
+// The compiler reports 85 VGPRs for every instance of the apply kernel (88 allocated: 5 waves per SIMD, 20 per CU) and 0 bytes
+// of scratch, so a CU holds at most five workgroups of 256 lanes or one of 1024: 16 or 20 waves per CU in the small shape.
 constexpr int kMfKreprPerCuS = 5;                             // VGPR-limited workgroups of 256 lanes per CU
-constexpr size_t kMfKreprLdsCu = (size_t)160 * 1024;
-constexpr size_t kMfKreprLdsStatic = 1024;                    // the reduction scratch of a workgroup and allocation granules
 
-inline size_t mf_krepr_lds_bytes(const MfKondoRepr &t) { return ((size_t)t.n_tab + 2 * (size_t)kKondoTabEntries) * sizeof(uint64_t); }
-inline int mf_krepr_fit(const MfKondoRepr &t) { return (int)(kMfKreprLdsCu / (mf_krepr_lds_bytes(t) + kMfKreprLdsStatic)); }
-inline bool mf_krepr_large(const MfKondoRepr &t) { return mf_krepr_fit(t) < 4; }
-
-// the resident grid of both kernels
-inline int mf_krepr_grid(const MfKondoRepr &t, int64_t nrows)
-{
-    const bool large = mf_krepr_large(t);
-    const int block = large ? kMfKreprBlockL : kMfKreprBlockS;
-    const int per_cu = large ? 1 : std::min(kMfKreprPerCuS, mf_krepr_fit(t));
-    const int64_t nblk = (nrows + block - 1) / block;
-    return (int)std::min<int64_t>(nblk, std::min<int64_t>((int64_t)device_cu_count() * per_cu, kMaxRedBlocks));
-}
-
-// tab | A | binom into LDS and the pointers the row walk reads them through
-__device__ __forceinline__ void krepr_stage(const MfKondoRepr &t, const KondoReprDev &R, uint64_t *lds, int nthreads, const uint64_t *&tab,
-                                            const uint64_t *&A, const uint64_t *&binom)
-{
-    for (int k = threadIdx.x; k < t.n_tab; k += nthreads) lds[k] = t.tab[k];
-    for (int k = threadIdx.x; k < kKondoTabEntries; k += nthreads) {
-        lds[t.n_tab + k] = R.k.A[k];
-        lds[t.n_tab + kKondoTabEntries + k] = R.k.binom[k];
-    }
-    __syncthreads();
-    tab = lds;
-    A = lds + t.n_tab;
-    binom = A + kKondoTabEntries;
-}
+inline size_t mf_krepr_lds_bytes(const MfKondoRepr &t) { return krepr_lds_bytes(t.n_tab); }
+inline bool mf_krepr_large(const MfKondoRepr &t) { return krepr_large(t.n_tab); }
+inline int mf_krepr_grid(const MfKondoRepr &t, int64_t nrows) { return krepr_grid(t.n_tab, nrows, kMfKreprPerCuS); }
 
 // the terms of the row of representative a (|S_a| = sa, nonzero norm) in the order of kondo_row: sink(position of b, value)
 // for every off-diagonal term entry whose target has nonzero norm; returns the diagonal of the row's own word
@@ -102,7 +64,7 @@ __global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr(MfKondoRepr t, MfVec a)
     const KondoReprDev &R = *static_cast<const KondoReprDev *>(t.R);
     const int tid = threadIdx.x;
     const uint64_t *tab, *A, *binom;
-    krepr_stage(t, R, kr_lds, BLOCK, tab, A, binom);
+    krepr_stage(t.tab, t.n_tab, R.k, kr_lds, BLOCK, tab, A, binom);
     double acc[3] = {0.0, 0.0, 0.0};
     const int64_t stride = (int64_t)gridDim.x * BLOCK;
     for (int64_t lrow = (int64_t)blockIdx.x * BLOCK + tid; lrow < a.nrows; lrow += stride) {
@@ -132,7 +94,7 @@ __global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr_count(MfKondoRepr t, in
     __shared__ unsigned long long red[BLOCK / 64];
     const KondoReprDev &R = *static_cast<const KondoReprDev *>(t.R);
     const uint64_t *tab, *A, *binom;
-    krepr_stage(t, R, kr_lds, BLOCK, tab, A, binom);
+    krepr_stage(t.tab, t.n_tab, R.k, kr_lds, BLOCK, tab, A, binom);
     unsigned long long c = 0;
     const int64_t stride = (int64_t)gridDim.x * BLOCK;
     for (int64_t row = row_begin + (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < row_end; row += stride) {
@@ -143,15 +105,6 @@ __global__ __launch_bounds__(BLOCK) void k_mf_kondo_repr_count(MfKondoRepr t, in
                              [&](int64_t, d2) { c += 1; });
     }
     mf_block_count<BLOCK>(c, red, part);
-}
-
-template <class Kernel, class... Args>
-hipError_t krepr_launch(Kernel k, int grid, int block, size_t lds, hipStream_t s, Args... args)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, args...);
-    return hipGetLastError();
 }
 
 }  // namespace

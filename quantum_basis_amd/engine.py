@@ -953,6 +953,48 @@ def moprXvec_diag_kondo_repr(n_sites, n_elec, two_sz, perms, chars_new, coef_up,
     return dim.value
 
 
+def _kondo_coef(coef, n_sites, name):
+    if coef is None:
+        return None
+    c = np.ascontiguousarray(coef, dtype=np.complex128)
+    if c.size != n_sites:
+        raise ValueError("%s must hold one coefficient per site" % name)
+    return c
+
+
+def moprXvec_kondo(n_sites, n_elec_old, two_sz_old, op, coef_elec, coef_spin, d_vec_old, d_vec_new, stream=None):
+    """vec_new = sum_s coef[s] O_s vec_old from the sector (n_elec_old, two_sz_old) of qbh_gen_kondo / qbh_mf_kondo to the
+    sector kondo.mopr_target(n_elec_old, two_sz_old, op) (qbh_mopr_kondo_dev).  op: kondo.C_UP, C_DN, CDAG_UP, CDAG_DN (coef_elec,
+    coef_spin = None) or kondo.SPIN_PLUS / SPIN_MINUS, which apply coef_elec[s] s^+-_s + coef_spin[s] S^+-_s: the electrons'
+    flip, the local spins' flip or, with both sets, the total-spin flip (either may be None: all zero).  Both vectors are
+    device addresses in the order of the generators (ascending words); a device vector of a handle with
+    info().basis_internal != 0 needs from_internal first, as measure_full_dynamic_dev does for its target.
+    Returns (dim_old, dim_new)."""
+    ce, cs = _kondo_coef(coef_elec, n_sites, "coef_elec"), _kondo_coef(coef_spin, n_sites, "coef_spin")
+    d0, d1 = C.c_int64(0), C.c_int64(0)
+    check(lib().qbh_mopr_kondo_dev(n_sites, n_elec_old, two_sz_old, int(op), None if ce is None else _p(ce), None if cs is None else _p(cs),
+                                   d_vec_old, d_vec_new, C.byref(d0), C.byref(d1), stream), "qbh_mopr_kondo_dev")
+    return d0.value, d1.value
+
+
+def moprXvec_kondo_repr(n_sites, n_elec_old, two_sz_old, op, perms, chars_old, coef_elec, coef_spin, d_vec_old, d_vec_new, stream=None):
+    """moprXvec_repr (src/model.cc:1715-1846) for the operators of moprXvec_kondo between momentum sectors of
+    qbh_gen_kondo_repr / qbh_mf_kondo_repr (qbh_mopr_kondo_repr_dev): from (n_elec_old, two_sz_old, chars_old) to
+    (kondo.mopr_target(...), chars_old * eta), where both coefficient sets transform with the one character eta,
+    coef[g(s)] = eta(g) coef[s].  Both vectors are device addresses in the order of the generators (all representatives,
+    ascending); a device vector of a handle with info().basis_internal != 0 needs from_internal first, as
+    measure_full_dynamic_dev does for its target.  Target representatives of zero norm receive 0.  Returns (dim_old, dim_new)."""
+    p = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+    co = np.ascontiguousarray(np.asarray(chars_old, dtype=np.complex128))
+    ce, cs = _kondo_coef(coef_elec, n_sites, "coef_elec"), _kondo_coef(coef_spin, n_sites, "coef_spin")
+    assert p.shape == (len(co), n_sites)
+    d0, d1 = C.c_int64(0), C.c_int64(0)
+    check(lib().qbh_mopr_kondo_repr_dev(n_sites, n_elec_old, two_sz_old, int(op), len(co), _p(p), _p(co), None if ce is None else _p(ce),
+                                        None if cs is None else _p(cs), d_vec_old, d_vec_new, C.byref(d0), C.byref(d1), stream),
+          "qbh_mopr_kondo_repr_dev")
+    return d0.value, d1.value
+
+
 def moprXvec_c_hubrepr(n_sites, n_up_old, n_dn_old, species, kind, perms, chars_old, chars_new, coef, d_vec_old, d_vec_new):
     """moprXvec_repr for sum_s coef[s] c_{s,sigma} (kind -1) / c^dag_{s,sigma} (kind +1), species 0 up / 1 down, between
     momentum sectors of qbh_gen_hubbard_repr with one particle less / more; returns (dim_old, dim_new)."""

@@ -24,6 +24,16 @@ MAX_SITES = 21
 
 Terms = namedtuple("Terms", "hops kz kxy sbonds")
 
+# the operators between sectors (qbh_mopr_kondo_dev, qbh_mopr_kondo_repr_dev): sum_s coef[s] O_s
+C_UP, C_DN, CDAG_UP, CDAG_DN, SPIN_PLUS, SPIN_MINUS = range(6)
+_MOPR_SHIFT = {C_UP: (-1, -1), C_DN: (-1, 1), CDAG_UP: (1, 1), CDAG_DN: (1, -1), SPIN_PLUS: (0, 2), SPIN_MINUS: (0, -2)}
+
+
+def mopr_target(n_elec, two_sz, op):
+    """(n_elec_new, two_sz_new) of the sector the operator `op` takes the sector (n_elec, two_sz) to."""
+    de, ds = _MOPR_SHIFT[int(op)]
+    return n_elec + de, two_sz + ds
+
 
 def sector_blocks(n_sites, n_elec, two_sz):
     """[(n_up, n_dn, m), ...] for every number m of down local spins that the sector admits, m ascending."""
