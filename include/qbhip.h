@@ -469,6 +469,30 @@ int qbh_mopr_flip_repr_dev(int n_sites, int n_dn_old, int kind, int n_trans, con
                            const double *chars_new, const qbh_z *coef, const qbh_z *d_vec_old, qbh_z *d_vec_new,
                            int64_t *dim_old_out, int64_t *dim_new_out);
 
+/* ------------------------------------------- all-pair static correlations --- */
+/* Every two-site expectation value of a resident state in ONE pass over it, without a temporary vector (the reference's
+ * measure_full_static, src/model.cc:1660-1694, applies the operators of one product one after another into sector-sized
+ * temporaries, one pair of sites per call).  Handle-free, like qbh_mopr_spin_dev.  d_vec (complex128) or d_vec_re (the packed real
+ * parts of a real state) -- exactly one of them -- is the WHOLE sector on the device in the generators' order; rows are 64-bit
+ * throughout, so the dimension may exceed 2^31.  Row shards and communicators are out of scope: a sharded state has to be
+ * gathered on one device first.  The outputs are HOST arrays, filled before the call returns, raw bilinear forms <psi| O |psi>
+ * (nothing is divided by *norm2).  Any output pointer may be NULL: that group is not computed and the gathers only it needs are
+ * not issued; the other outputs keep their bits.  No atomics: two calls on the same input return the same bits.
+ * Checked before the device is looked for: n_sites outside 1 .. 62 (spin) / 1 .. 31 (fermions), particle numbers out of range
+ * (n_dn > 33 for spins), both or neither vector pointer -> QBH_EINVAL; tables that do not fit LDS or 2^62 rows -> QBH_EUNSUPP.
+ * qbh_corr_spin_dev: spin-1/2, n_dn down spins, basis of qbh_gen_heisenberg (colex rank of the down-spin pattern, bit set = down).
+ *   sz[i] = <S^z_i>; zz[i*N + j] = <S^z_i S^z_j>, full symmetric matrix, diagonal norm2 / 4; pm[i*N + j] = <S^+_i S^-_j>,
+ *   Hermitian, diagonal <1/2 + S^z_i>.
+ * qbh_corr_hubbard_dev: two-species fermions, basis / operator order / signs of qbh_gen_hubbard and qbh_mopr_terms_dev family 1.
+ *   dens[s*N + i] = <n_{i,s}> (s = 0 up, 1 down); nn[(2a + b)*N*N + i*N + j] = <n_{i,a} n_{j,b}>; hop[s*N*N + i*N + j] =
+ *   <c+_{i,s} c_{j,s}> (diagonal = dens); flip[i*N + j] = <S^+_i S^-_j> = <c+_{i,up} c_{i,dn} c+_{j,dn} c_{j,up}>, diagonal
+ *   <n_{i,up} (1 - n_{i,dn})>. */
+int qbh_corr_spin_dev(int n_sites, int n_dn, const qbh_z *d_vec, const double *d_vec_re, double *norm2, double *sz /* [N] */,
+                      double *zz /* [N*N] */, qbh_z *pm /* [N*N] */, void *stream);
+int qbh_corr_hubbard_dev(int n_sites, int n_up, int n_dn, const qbh_z *d_vec, const double *d_vec_re, double *norm2,
+                         double *dens /* [2][N] */, double *nn /* [4][N][N] */, qbh_z *hop /* [2][N][N] */, qbh_z *flip /* [N][N] */,
+                         void *stream);
+
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.
  * qbh_vec_disk_write / _read: vec_disk_write / vec_disk_read (src/miscellaneous.cc:391-469): int64 n | n * elem_size

@@ -1,0 +1,154 @@
+"""All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev), and the host
+arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
+
+The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
+reference's measure_full_static (src/model.cc:1660-1694) applies one product of operators per call into sector-sized temporaries.
+Momentum-sector states are not covered here: measure_repr_static_hubbard stays the route there.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+
+
+def _addr(d_vec):
+    """device address of a DeviceVec, a torch tensor on the device, a ctypes pointer or an integer"""
+    if hasattr(d_vec, "data_ptr"):
+        return C.c_void_p(d_vec.data_ptr())
+    p = getattr(d_vec, "ptr", d_vec)
+    return p if isinstance(p, C.c_void_p) else C.c_void_p(int(p))
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _generator_order(d_vec, real, source):
+    """(device address in the generators' order, buffer to free afterwards)"""
+    if source is None or source.info().basis_internal == 0:
+        return _addr(d_vec), None
+    if real:
+        raise ValueError("a packed-real vector of a handle that keeps another basis order internally (basis_internal != 0) cannot be "
+                         "translated: pass the complex vector, or a vector in the generators' order without `source`")
+    conv = source.vec(1)
+    source.from_internal(conv.ptr, _addr(d_vec))
+    source.sync()
+    return conv.ptr, conv
+
+
+def _nonzero_norm(norm2, who):
+    if not norm2 > 0.0:
+        raise ValueError("%s: <psi|psi> = %r, nothing to normalise by (normalize=False returns the raw sums)" % (who, norm2))
+
+
+def spin_correlations(n_sites, n_dn, d_vec, real=False, source=None, normalize=True, stream=None):
+    """<S^z_i>, <S^z_i S^z_j> and <S^+_i S^-_j> for ALL pairs of sites of a spin-1/2 state with n_dn down spins (basis of
+    csr_mat.heisenberg), one pass over the state.  d_vec: device address (or DeviceVec) of the whole sector, complex128, or its
+    packed real parts (real=True: n doubles).  source: the handle the vector belongs to -- needed when that handle keeps another
+    order internally (info().basis_internal != 0); the vector is translated first (a packed-real one cannot be: ValueError).
+    Returns dict(norm2, sz[N], zz[N][N], pm[N][N], ss[N][N]) with ss = <S_i . S_j> = zz + Re pm (3/4 on the diagonal); with
+    normalize the arrays are divided by norm2 = <psi|psi> (norm2 itself is returned as measured)."""
+    N = int(n_sites)
+    addr, conv = _generator_order(d_vec, real, source)
+    try:
+        n2 = C.c_double()
+        sz, zz, pm = np.zeros(N), np.zeros((N, N)), np.zeros((N, N), dtype=np.complex128)
+        check(lib().qbh_corr_spin_dev(N, int(n_dn), None if real else addr, addr if real else None, C.byref(n2), _p(sz), _p(zz), _p(pm),
+                                      stream), "qbh_corr_spin_dev")
+    finally:
+        if conv is not None:
+            conv.free()
+    norm2 = n2.value
+    ss = zz + pm.real
+    ss[np.diag_indices(N)] = 0.75 * norm2
+    out = {"norm2": norm2, "sz": sz, "zz": zz, "pm": pm, "ss": ss}
+    if normalize:
+        _nonzero_norm(norm2, "spin_correlations")
+        for k in ("sz", "zz", "pm", "ss"):
+            out[k] = out[k] / norm2
+    return out
+
+
+def hubbard_correlations(n_sites, n_up, n_dn, d_vec, real=False, source=None, normalize=True, want=("dens", "nn", "hop", "flip"), stream=None):
+    """<n_{i,s}>, <n_{i,a} n_{j,b}>, <c+_{i,s} c_{j,s}> and <S^+_i S^-_j> for ALL pairs of sites of a two-species fermion state
+    (basis, operator order and signs of csr_mat.hubbard / moprXvec_terms family 1), one pass over the state.  d_vec / real /
+    source / normalize as in spin_correlations.  want: the groups to compute (a group left out costs nothing, its gathers are not
+    issued).  Returns dict(norm2, dens[2][N], nn[4][N][N] (uu, ud, du, dd), hop[2][N][N], flip[N][N]) for the wanted groups, and
+    derived from them: docc[N] = <n_up n_dn>, szsz[N][N], nn_total[N][N] (from nn); ss[N][N] = <S_i . S_j> (from nn and flip)."""
+    N = int(n_sites)
+    want = set(want)
+    unknown = want - {"dens", "nn", "hop", "flip"}
+    if unknown:
+        raise ValueError("hubbard_correlations: unknown group(s) %s" % sorted(unknown))
+    addr, conv = _generator_order(d_vec, real, source)
+    try:
+        n2 = C.c_double()
+        dens = np.zeros((2, N)) if "dens" in want else None
+        nn = np.zeros((4, N, N)) if "nn" in want else None
+        hop = np.zeros((2, N, N), dtype=np.complex128) if "hop" in want else None
+        flip = np.zeros((N, N), dtype=np.complex128) if "flip" in want else None
+        check(lib().qbh_corr_hubbard_dev(N, int(n_up), int(n_dn), None if real else addr, addr if real else None, C.byref(n2), _p(dens),
+                                         _p(nn), _p(hop), _p(flip), stream), "qbh_corr_hubbard_dev")
+    finally:
+        if conv is not None:
+            conv.free()
+    out = {"norm2": n2.value}
+    for k, a in (("dens", dens), ("nn", nn), ("hop", hop), ("flip", flip)):
+        if a is not None:
+            out[k] = a
+    if nn is not None:
+        out["docc"] = np.diag(nn[1]).copy()
+        out["szsz"] = 0.25 * (nn[0] - nn[1] - nn[2] + nn[3])
+        out["nn_total"] = nn[0] + nn[1] + nn[2] + nn[3]
+        if flip is not None:
+            ss = out["szsz"] + flip.real
+            ss[np.diag_indices(N)] = 3.0 * np.diag(out["szsz"])        # S_i^2 = 3 (S^z_i)^2 for a spin-1/2 or an empty / doubly occupied site
+            out["ss"] = ss
+    if normalize:
+        _nonzero_norm(out["norm2"], "hubbard_correlations")
+        for k in out:
+            if k != "norm2":
+                out[k] = out[k] / out["norm2"]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------- host helpers --
+def _phases(positions, qs):
+    r, q = np.asarray(positions, dtype=float), np.asarray(qs, dtype=float)
+    if r.ndim == 1:
+        r = r[:, None]                                  # positions on a line
+    if q.ndim == 1:
+        q = q[:, None] if r.shape[1] == 1 else q[None, :]
+    return np.exp(1j * (q @ r.T))                       # [n_q][N]: e^{i q . r_i}
+
+
+def structure_factor(corr, positions, qs):
+    """S(q) = (1/N) sum_ij e^{i q . (r_i - r_j)} corr[i][j] for a Hermitian N x N correlation matrix (ss, zz, nn_total, ...);
+    positions [N][d] (or [N] in one dimension), qs [n_q][d].  Returns n_q real numbers."""
+    c = np.asarray(corr)
+    ph = _phases(positions, qs)
+    return np.einsum("qi,ij,qj->q", ph, c, ph.conj()).real / c.shape[-1]
+
+
+def momentum_distribution(hop, positions, ks):
+    """n(k) = <c+_k c_k> = (1/N) sum_ij e^{i k . (r_i - r_j)} <c+_i c_j>, c+_k = N^{-1/2} sum_i e^{i k . r_i} c+_i.  hop: [N][N], or
+    [2][N][N] for both species (returns [2][n_k])."""
+    h = np.asarray(hop)
+    if h.ndim == 3:
+        return np.stack([momentum_distribution(x, positions, ks) for x in h])
+    return structure_factor(h, positions, ks)
+
+
+def energy_from_correlations(corr, bonds, J=1.0, t=1.0, U=0.0):
+    """<psi| H |psi> from the two-site expectation values, for ANY vector (not only eigenvectors), in the units of `corr` (raw or
+    normalised).  bonds: the list the operator was built from (a bond listed twice counts twice, as in csr_mat.heisenberg /
+    csr_mat.hubbard).  Spin correlations (a dict with "pm"):    H = J sum_bonds S_i . S_j,  <H> = J sum_bonds (zz + Re pm).
+    Fermion correlations (a dict with "hop" and "nn"):  H = -t sum_bonds,s (c+_i c_j + h.c.) + U sum_i n_up n_dn,
+    <H> = -t sum_bonds,s 2 Re hop[s][i][j] + U sum_i nn_ud[i][i]."""
+    b = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
+    i, j = b[:, 0], b[:, 1]
+    if "pm" in corr:
+        return float(J * np.sum(corr["zz"][i, j] + corr["pm"][i, j].real))
+    hop, nn = corr["hop"], corr["nn"]
+    return float(-t * 2.0 * np.sum(hop[0][i, j].real + hop[1][i, j].real) + U * np.trace(nn[1]))
