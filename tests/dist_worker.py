@@ -335,5 +335,54 @@ def gpu_sharded_probe(rank, world, port, backend, out_dir, L, n_up, n_dn, bonds_
     dist.destroy_process_group()
 
 
+def gpu_hostforms_shards(rank, world, port, backend, out_dir, names, native=False):
+    """Row shards of the synthetic host matrices of tests/hostforms.py (uniform blocks, qbh_csr_create_rows), coded with 1-byte or
+    2-byte codes or uncoded: the download before the communicator is attached, the download after it (the attachment splits the
+    shard by column, qbh_csrprep.hip k_split_count / k_split_fill) and one y = alpha H x + beta y + gamma x_local through the
+    exchange -- the host-staged hooks over gloo, or (native) the library's own communicator on whatever librccl QBH_RCCL_LIB names.
+    Saves everything for test_gpu_hostforms.py to compare."""
+    import torch
+    dist = _init(rank, world, port, backend)
+    torch.cuda.set_device(0)
+    import hostforms as hf
+    import quantum_basis_amd as q
+    from quantum_basis_amd import dist as qdist
+
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        for name in names:
+            dim, ia, ja, val, sym, _ = hf.make(name)
+            opts = q.make_opts(device=0, stream=stream.cuda_stream, value_dict=1 if name.startswith("dict_") else 0, real_fast_path=0,
+                               kron_split=0, basis_detect=0, autotune=0)
+            nblk, ranges = qdist.row_partition(dim, world)
+            r0, r1 = ranges[rank]
+            n = r1 - r0
+            A = q.csr_mat(dim, ia, ja, val, sym=bool(sym), opts=opts, rows=(r0, r1))
+            before = A.download()
+            n_dict, bytes_before, blocks_before = A.info().value_dict, A.info().bytes_matrix, A.info().n_blocks
+            if native:
+                comm = qdist.NativeComm(dim, rank=rank, world=world).attach(A)
+            else:
+                comm = qdist.ShardComm(dim, rank=rank, world=world, device=torch.device("cuda", 0), stream=stream).attach(A)
+            after = A.download()
+            v = q.DeviceVec(A, 2 * n)
+            v.upload(hf.probe_vector(dim, 11)[r0:r1], 0)
+            v.upload(hf.probe_vector(dim, 12)[r0:r1], n)
+            n_gather = A.stats().n_gather
+            A.spmv(v.at(0), v.at(n), *hf.TRIPLE)
+            y = v.download(n, n)
+            assert native or not comm.errors, comm.errors
+            assert A.stats().n_gather == n_gather + 1, "the SpMV did not go through the exchange"
+            np.savez(os.path.join(out_dir, "%s_%d.npz" % (name, rank)), r0=r0, r1=r1, n_dict=n_dict, y=y, bia=before[0], bja=before[1],
+                     bval=before[2], aia=after[0], aja=after[1], aval=after[2], bytes_before=bytes_before, bytes_after=A.info().bytes_matrix,
+                     blocks_before=blocks_before, blocks_after=A.info().n_blocks)
+            v.free()
+            if native:
+                comm.detach(A)
+            A.destroy()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 if __name__ == "__main__":
     pass
