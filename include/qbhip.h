@@ -446,7 +446,8 @@ int qbh_mopr_onebody_dev(int n_sites, int n_up, int n_dn, int n_terms, const int
  *       o = s + species * n_sites (all up operators left of all down operators), c^dag_o |w> = (-1)^{occupied orbitals below o} |w + o>
  * Any local 2 x 2 matrix of the reference's opr<T> is a combination of {1, S^z, S^+, S^-} resp. {1, n, c^dag, c}, so every
  * opr_prod / mopr over these site types is such a list.  Every product must change the particle numbers by the same amount (one
- * target sector: sec_new of the reference); *dim_new_out (may be NULL) = its dimension, d_vec_new must hold that many elements.
+ * target sector: sec_new of the reference); *dim_new_out (may be NULL) = its dimension, written once every check has passed
+ * (before the device is looked for, as in qbh_mopr_qudit_dev); d_vec_new must hold that many elements.
  * Every target row gathers its contributions (the adjoint factors run over the row's own pattern): no atomics, deterministic.
  * <= 4096 factors in all. */
 int qbh_mopr_terms_dev(int family, int n_sites, int n_a_old, int n_b_old, int n_terms, const int32_t *term_ptr, const int32_t *op_kind,

@@ -405,6 +405,12 @@ extern "C" int qbh_mopr_terms_dev(int family, int n_sites, int n_a_old, int n_b_
         set_error("qbh_mopr_terms_dev: invalid argument");
         return QBH_EINVAL;
     }
+    // ascending first: only then does term_ptr[n_terms] bound every factor index the loops below read and write
+    for (int t = 0; t < n_terms; ++t)
+        if (term_ptr[t + 1] < term_ptr[t]) {
+            set_error("qbh_mopr_terms_dev: term_ptr is not ascending");
+            return QBH_EINVAL;
+        }
     const int n_ops = term_ptr[n_terms];
     if (n_ops <= 0 || n_ops > kMaxTermOps) {
         set_error("qbh_mopr_terms_dev: %d elementary factors (1 .. %d allowed)", n_ops, kMaxTermOps);
@@ -414,10 +420,6 @@ extern "C" int qbh_mopr_terms_dev(int family, int n_sites, int n_a_old, int n_b_
     std::vector<TermOp> ops((size_t)n_ops);
     int da = 0, db = 0;
     for (int t = 0; t < n_terms; ++t) {
-        if (term_ptr[t + 1] < term_ptr[t]) {
-            set_error("qbh_mopr_terms_dev: term_ptr is not ascending");
-            return QBH_EINVAL;
-        }
         int ta = 0, tb = 0;
         for (int k = term_ptr[t]; k < term_ptr[t + 1]; ++k) {
             const int sp = family == 1 ? op_species[k] : 0;
@@ -443,22 +445,25 @@ extern "C" int qbh_mopr_terms_dev(int family, int n_sites, int n_a_old, int n_b_
         set_error("qbh_mopr_terms_dev: the target sector (%d, %d) does not exist", na_new, nb_new);
         return QBH_EINVAL;
     }
+    // the dimension is the caller's before the device is looked for, as in qbh_mopr_qudit_dev
+    int64_t dim_new = 0, nd_new = 1, nd_old = 1;
+    if (family == 1) {
+        nd_new = (int64_t)binom_host(n_sites, nb_new);
+        nd_old = (int64_t)binom_host(n_sites, n_b_old);
+        dim_new = (int64_t)binom_host(n_sites, na_new) * nd_new;
+    } else {
+        dim_new = (int64_t)binom_host(n_sites, na_new);
+    }
+    if (dim_new_out) *dim_new_out = dim_new;
     if (qbh_device_count() <= 0) {
         set_error("no HIP device visible");
         return QBH_ENODEVICE;
     }
     std::vector<uint32_t> cu, cd;
-    int64_t dim_new = 0, nd_new = 1, nd_old = 1;
     if (family == 1) {
         enumerate(n_sites, na_new, cu);
         enumerate(n_sites, nb_new, cd);
-        nd_new = (int64_t)cd.size();
-        nd_old = (int64_t)binom_host(n_sites, n_b_old);
-        dim_new = (int64_t)cu.size() * nd_new;
-    } else {
-        dim_new = (int64_t)binom_host(n_sites, na_new);
     }
-    if (dim_new_out) *dim_new_out = dim_new;
     uint32_t *d_cu = nullptr, *d_cd = nullptr;
     int32_t *d_ptr = nullptr;
     TermOp *d_ops = nullptr;

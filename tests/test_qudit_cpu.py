@@ -106,6 +106,35 @@ def test_mopr_argument_checks_before_the_device():
                                 C.byref(dim), None) == EUNSUPP
 
 
+def test_mopr_local_matrix_must_sit_on_the_dq_diagonal():
+    """|dq| >= d: no level can change by dq, so every nonzero entry is off the diagonal and refused, although the target charge
+    exists; dq = +-2: an entry one off the dq diagonal is refused and named, the matrix without it passes every check."""
+    L = _lib.lib()
+    coef = np.ones(4, dtype=np.complex128)
+    x = C.c_void_p(16)                       # never dereferenced
+    dim = C.c_int64(-1)
+
+    def call(d, total_old, dq, loc):
+        loc = np.ascontiguousarray(loc, dtype=np.complex128)
+        return L.qbh_mopr_qudit_dev(4, d, total_old, dq, coef.ctypes.data, loc.ctypes.data, x, x, C.byref(dim), None)
+
+    for dq, total in ((3, 4), (-3, 4), (4, 2)):                        # d = 3: charges 0 .. 8, so total + dq is a sector
+        loc = np.zeros((3, 3), dtype=np.complex128)
+        loc[2, 0] = 1.0
+        assert call(3, total, dq, loc) == EINVAL
+        msg = L.qbh_last_error().decode()
+        assert "qbh_mopr_qudit_dev" in msg and "local[2][0]" in msg and "dq = %d" % dq in msg
+    for dq, good, off in ((2, (2, 0), (1, 0)), (-2, (0, 2), (0, 1)), (2, (3, 1), (3, 2)), (-2, (1, 3), (1, 2))):
+        loc = np.zeros((4, 4), dtype=np.complex128)
+        loc[good] = 0.5 - 1j
+        if L.qbh_device_count() <= 0:                                     # with a device the call would run on the fake addresses
+            assert call(4, 6, dq, loc) == -2 and dim.value == {2: 31, -2: 31}[dq]
+        loc[off] = 1e-300
+        assert call(4, 6, dq, loc) == EINVAL
+        msg = L.qbh_last_error().decode()
+        assert "qbh_mopr_qudit_dev" in msg and "local[%d][%d]" % off in msg and "dq = %d" % dq in msg
+
+
 @pytest.mark.parametrize("S", [0.5, 1, 1.5, 2])
 def test_spin_matrices_algebra(S):
     sz, sp, sm = qudit.spin_matrices(S)
