@@ -654,7 +654,9 @@ int qbh_mf_hubbard(qbh_csr **out, int n_sites, int n_up, int n_dn, int n_bonds,
                    const int32_t *bonds /* [2*n_bonds] */, double t, double U,
                    int64_t row_begin, int64_t row_end, const qbh_opts *opts);
 /* Spin-1/2 Heisenberg, H = J sum_<ij> S_i.S_j, fixed number of down spins; basis index =
- * colexicographic rank of the down-spin bit pattern. */
+ * colexicographic rank of the down-spin bit pattern.  As in qbh_gen_hubbard and the reference's lil_mat::add, an
+ * off-diagonal amplitude |0.5 J w| < QBH_SPARSE_PRECISION is not stored (its bond still adds to the diagonal, which is
+ * always stored); the nnz qbh_mf_heisenberg reports follows the same rule. */
 int qbh_gen_heisenberg(qbh_csr **out, int n_sites, int n_dn, int n_bonds,
                        const int32_t *bonds, double J,
                        int64_t row_begin, int64_t row_end, const qbh_opts *opts);

@@ -221,6 +221,10 @@ __global__ __launch_bounds__(256) void k_gen_hubbard(HubDev h, int64_t row_begin
     if (blockIdx.x == 0 && threadIdx.x == 0) ia[row_end - row_begin] = hub_rowptr(h, row_end) - p_begin;
 }
 
+// lil_mat::add drop rule, as in build_hops: a bond whose off-diagonal amplitude is below the sparse precision adds to the
+// diagonal only.  The count and the fill pass ask the same question.
+__device__ __forceinline__ bool heis_stores(const HeisDev &h, int bnd) { return fabs(h.offd[bnd]) >= QBH_SPARSE_PRECISION; }
+
 __global__ __launch_bounds__(256) void k_heis_count(const HeisDev *hp, int64_t row_begin, int64_t row_end,
                                                     int32_t *cnt)
 {
@@ -229,7 +233,8 @@ __global__ __launch_bounds__(256) void k_heis_count(const HeisDev *hp, int64_t r
     for (int64_t row = row_begin + (int64_t)blockIdx.x * 256 + threadIdx.x; row < row_end; row += stride) {
         const uint64_t s = heis_unrank(h, (uint64_t)row);
         int c = 1;
-        for (int bnd = 0; bnd < h.n_bonds; ++bnd) c += (int)(((s >> h.sa[bnd]) ^ (s >> h.sb[bnd])) & 1ULL);
+        for (int bnd = 0; bnd < h.n_bonds; ++bnd)
+            if (heis_stores(h, bnd)) c += (int)(((s >> h.sa[bnd]) ^ (s >> h.sb[bnd])) & 1ULL);
         cnt[row - row_begin] = c;
     }
 }
@@ -250,6 +255,7 @@ __global__ __launch_bounds__(256) void k_heis_fill(const HeisDev *hp, int64_t ro
             const bool differ = (((s >> h.sa[bnd]) ^ (s >> h.sb[bnd])) & 1ULL) != 0;
             if (differ) {
                 dg -= h.diag[bnd];
+                if (!heis_stores(h, bnd)) continue;
                 const int32_t c = (int32_t)heis_rank(h, s ^ ma ^ mb);
                 int q = n++;                               // insertion sort by column
                 while (q > 0 && cols[q - 1] > c) {
@@ -668,7 +674,7 @@ extern "C" int qbh_mf_heisenberg(qbh_csr **out, int n_sites, int n_dn, int n_bon
         mask[(size_t)i] = (1ULL << bw.first.first) | (1ULL << bw.first.second);
         offd[(size_t)i] = 0.5 * J * bw.second;
         diag[(size_t)i] = 0.25 * J * bw.second;
-        if (n_sites >= 2 && n_dn >= 1 && n_dn <= n_sites - 1) nnz_full += 2 * (int64_t)binom_u64(n_sites - 2, n_dn - 1);
+        if (n_sites >= 2 && n_dn >= 1 && n_dn <= n_sites - 1 && std::fabs(offd[(size_t)i]) >= QBH_SPARSE_PRECISION) nnz_full += 2 * (int64_t)binom_u64(n_sites - 2, n_dn - 1);
         ++i;
     }
     MfHeis t;

@@ -164,11 +164,14 @@ def _popcount(x):
     return c
 
 
-def hubbard_csr(Lx, Ly, n_up, n_dn, t=1.0, U=1.1, upper=True, pbc=True):
+def hubbard_csr(Lx, Ly, n_up, n_dn, t=1.0, U=1.1, upper=True, pbc=True, bonds=None):
     """Fermi-Hubbard on the square lattice in the reference's conventions.
 
-    H = -t sum_<ij>,s (c+_is c_js + h.c.) + U sum_i n_iup n_idn   (examples/.../square_Fermi_Hubbard.cc)."""
+    H = -t sum_<ij>,s (c+_is c_js + h.c.) + U sum_i n_iup n_idn   (examples/.../square_Fermi_Hubbard.cc).
+    bonds: another bond list (pairs with multiplicity) on the Lx * Ly sites instead of the square lattice's."""
     nsites = Lx * Ly
+    if bonds is None:
+        bonds = square_bonds(Lx, Ly, pbc)
     basis = electron_basis(nsites, n_up, n_dn)
     dim = len(basis)
     perm = np.argsort(basis, kind="stable")
@@ -182,7 +185,7 @@ def hubbard_csr(Lx, Ly, n_up, n_dn, t=1.0, U=1.1, upper=True, pbc=True):
     rows.append(all_rows)
     cols.append(all_rows)
     vals.append((U * dbl).astype(np.complex128))
-    for (i, j) in square_bonds(Lx, Ly, pbc):
+    for (i, j) in bonds:
         for spin in (0, 1):
             for (a, b) in ((2 * i + spin, 2 * j + spin), (2 * j + spin, 2 * i + spin)):
                 # term -t c+_a c_b applied to |row>: needs b occupied, a empty
