@@ -39,6 +39,7 @@ int wave_geometry_for(qbh_csr *A, const int64_t *ia, int64_t nr, int64_t nnz, do
                       int *tpr_o, int *grid_o, int64_t shift = 0);
 int kron_geometry(qbh_csr *A);
 int kron_short_cols(qbh_csr *A);
+int kron_near_lens(qbh_csr *A);
 int kron_build(qbh_csr *A);
 int kron_restore(qbh_csr *A);
 void kronc_release(qbh_csr *A);

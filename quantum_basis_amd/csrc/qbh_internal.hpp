@@ -39,6 +39,8 @@ struct DebugSw {
     int kronc_abl = 0, kronc_far_chunk = 0, kronc_far_ng = 0, kronc_far_nt = 0;
     int no_far_align = 0;     // in-place split: the far part directly behind the near part (unaligned)
     int far_cols8 = -1;       // 0: the sliced far pass keeps reading its 2-byte columns slot by slot (no grouped copy, KronSplit::c8_f; A/B only)
+    int near_lens = -1;       // 0: the near pass keeps reading its row pointers (no length array, KronSplit::len_n; A/B only)
+    int near_len_cap = 0;     // > 0: the longest near row the length array takes (default 255: one byte); a lower cap lets a test reach the fallback
     int no_defer = 0;         // Lanczos: read <u, w> back every step instead of keeping it on the device
     int host_delay_us = 0;    // Lanczos: the host spins this long after every read-back of a step's scalars (models a slow / descheduled host)
     int pipe_nospec = 0;      // pipelined Lanczos loop: 1 = never enqueue a step before the one before it has been read back (debugging)
@@ -136,6 +138,10 @@ struct SpmvArgs {
     // sliced far part whose 8 slots of a line all name the same major index (T (x) 1): that value once per 8 slots, entry i >> 3 for
     // slot i (k_spmv_wave2<.., G8 = true>: one column load per lane and block instead of eight); nullptr: ja16 is read
     const uint16_t *ja8;
+    // one-class near part (k_spmv_wave2<.., NL > 0>, pass forms 1 and 2): the length of every near row, one byte each, nrows + 64
+    // entries (the tail zero); a block's row offsets are the prefix sums of its rows' lengths, formed across the lanes.  ia stays
+    // the stored form and is still read for a row longer than the tile.  nullptr: ia is read.
+    const uint8_t *len8;
     // k_spmv_wave2 under the dynamic walk, passes with the fused epilogue: one slot of three sums per chunk of blocks
     // (wave2_chunk_slots(n_wb) slots; never nullptr for those launches), added up in a fixed order by launch_reduce_chunks
     double *chunk_red;
@@ -311,6 +317,9 @@ int launch_kron_desc_c16(WaveDesc *wd, int64_t n_wb, int64_t div, bool far, bool
 int launch_kron_c16_near(const WaveDesc *wd, int64_t n_wb, const int32_t *ja, int64_t S, int64_t col0, uint16_t *out, int *flag, hipStream_t s);
 int launch_kron_c16_far(const WaveDesc *wd, const int32_t *ja, int64_t slots, int64_t NU, uint16_t *out, int *flag, hipStream_t s);
 int launch_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *flag, hipStream_t s);
+// near row lengths as bytes (out[r] = ia[r + 1] - ia[r]); *flag is raised when a row is longer than cap, or when the lengths of a
+// wave block's rows do not add up to the block's span of entries
+int launch_kron_near_lens(const int64_t *ia, int64_t nrows, const WaveDesc *wd, int64_t n_wb, int cap, uint8_t *out, int *flag, hipStream_t s);
 int launch_kron_check2(const int64_t *ia, const int32_t *ja, int64_t nrows, int64_t S, int64_t U0, int *d_flag, hipStream_t s);
 // qbh_opts.basis_kind (qbh_reorder.hip): re-express the plain CSR of A in the library's internal order, keep the vector map
 int basis_to_internal(qbh_csr *A, int kind, int n_sites, int n_up, int n_dn, bool *applied);
@@ -791,6 +800,7 @@ struct qbh_csr {
         int32_t *ja_n = nullptr, *ja_f = nullptr;
         uint16_t *c16_n = nullptr, *c16_f = nullptr;    // 2-byte columns (qbh_opts.kron_cols16): allocations of their own; the int32 form of that part is gone
         uint16_t *c8_f = nullptr;       // c16_f once per 8 slots, where the 8 are equal throughout: what the far pass reads (derived; lives and dies with c16_f)
+        uint8_t *len_n = nullptr;       // ia_n[r + 1] - ia_n[r], one byte per near row (+ 64 zeroed): what the one-class near pass reads (derived; ia_n stays the stored form)
         qbh::d2 *val_n = nullptr, *val_f = nullptr;
         qbh::WaveDesc *wd_n = nullptr, *wd_f = nullptr;
         int64_t  nwb_n = 0, nwb_f = 0;

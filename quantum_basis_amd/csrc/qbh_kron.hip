@@ -321,7 +321,41 @@ __global__ __launch_bounds__(kBlock) void k_kron_c8_far(const uint16_t *c16, int
     if (bad) *flag = 1;
 }
 
+// near row lengths as bytes: what the near pass reads in place of the row pointers.  A row longer than cap raises the flag.
+__global__ __launch_bounds__(kBlock) void k_kron_near_lens(const int64_t *ia, int64_t nrows, int cap, uint8_t *out, int *flag)
+{
+    bool bad = false;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t len = ia[r + 1] - ia[r];
+        bad = bad || len < 0 || len > cap;
+        out[r] = (uint8_t)len;
+    }
+    if (bad) *flag = 1;
+}
+
+// ... and the lengths of every wave block's rows must add up to the block's span of entries (descriptor to descriptor): the
+// pass forms a block's row offsets from them alone
+__global__ __launch_bounds__(kBlock) void k_kron_near_lens_check(const WaveDesc *wd, int64_t n_wb, const uint8_t *len, int *flag)
+{
+    bool bad = false;
+    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_wb; w += (int64_t)gridDim.x * blockDim.x) {
+        int64_t sum = 0;
+        for (int64_t r = wd[w].r0; r < wd[w + 1].r0; ++r) sum += len[r];
+        bad = bad || sum != wd[w + 1].p0 - wd[w].p0;
+    }
+    if (bad) *flag = 1;
+}
+
 }  // namespace
+
+int launch_kron_near_lens(const int64_t *ia, int64_t nrows, const WaveDesc *wd, int64_t n_wb, int cap, uint8_t *out, int *flag, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kron_near_lens, dim3(4096), dim3(kBlock), 0, s, ia, nrows, cap, out, flag);
+    QBH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_kron_near_lens_check, dim3(4096), dim3(kBlock), 0, s, wd, n_wb, (const uint8_t *)out, flag);
+    QBH_HIP(hipGetLastError());
+    return QBH_OK;
+}
 
 int launch_kron_desc_c16(WaveDesc *wd, int64_t n_wb, int64_t div, bool far, bool undo, hipStream_t s)
 {

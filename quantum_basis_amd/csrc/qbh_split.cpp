@@ -24,7 +24,7 @@ void kron_free_aux(qbh_csr *A)
 {
     qbh_csr::KronSplit &K = A->kron;
     for (void *q : {(void *)K.ia_n, (void *)K.ia_f, (void *)K.wd_n, (void *)K.wd_f, (void *)K.d_xt, (void *)K.d_far, (void *)K.ia_x, (void *)K.xrow,
-                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
+                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.len_n, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
         if (q) (void)hipFree(q);
     if (K.own_far) {
         if (K.ja_f) (void)hipFree(K.ja_f);
@@ -211,6 +211,41 @@ int kron_short_cols(qbh_csr *A)
     }
     if (K.c16_n) K.ja_n = nullptr;
     if (K.c16_f) K.ja_f = nullptr;
+    return QBH_OK;
+}
+
+// The near pass needs a block's row OFFSETS, and those are the prefix sums of its rows' lengths from the descriptor's first entry on:
+// one byte per row (len_n) in place of two 8-byte row pointers -- 2-3 lines that miss to HBM per block fewer, and no pointer load
+// inside the row loop of a block with more rows than one pass takes (k_spmv_wave2's NL).  A derived array only: ia_n stays what
+// download, restore, merge, shards and k_kron_need read, and what the pass itself reads for a row longer than the tile.  One class
+// only (pass forms 1 and 2).  A row longer than the cap, lengths that do not add up to a block's span, no room, or any error: the
+// whole operator keeps reading ia_n.  QBH_DEBUG=near_lens=0 skips it (A/B of the two forms from one build), near_len_cap=N lowers the
+// cap (default 255).
+int kron_near_lens(qbh_csr *A)
+{
+    qbh_csr::KronSplit &K = A->kron;
+    const qbh::DebugSw &dbg = qbh::debug_sw();
+    if (K.len_n || K.map.nc != 1 || K.nnz_n <= 0 || !K.ia_n || !K.wd_n || dbg.near_lens == 0) return QBH_OK;
+    hipStream_t s = A->stream;
+    const int cap = (dbg.near_len_cap > 0 && dbg.near_len_cap < 255) ? dbg.near_len_cap : 255;
+    uint8_t *l = nullptr;
+    if (hipMalloc(&l, (size_t)A->nrows + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        return QBH_OK;                                   // no room: the pass keeps the row pointers
+    }
+    int bad = 0;
+    hipError_t he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+    if (he == hipSuccess) he = hipMemsetAsync(l + A->nrows, 0, 64, s);
+    const int rc = he == hipSuccess ? qbh::launch_kron_near_lens(K.ia_n, A->nrows, K.wd_n, K.nwb_n, cap, l, A->d_flag, s) : QBH_OK;
+    if (rc == QBH_OK && he == hipSuccess) he = hipMemcpyAsync(&bad, A->d_flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (rc == QBH_OK && he == hipSuccess) he = hipStreamSynchronize(s);
+    if (rc == QBH_OK && he == hipSuccess) he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+    if (rc != QBH_OK || he != hipSuccess || bad) {
+        (void)hipGetLastError();
+        (void)hipFree(l);
+    } else {
+        K.len_n = l;
+    }
     return QBH_OK;
 }
 
@@ -524,6 +559,7 @@ int kron_build(qbh_csr *A)
     K.inplace = true;
     KRON_TRY(kron_geometry(A));
     KRON_TRY(kron_short_cols(A));
+    KRON_TRY(kron_near_lens(A));
     if (qbh::debug_sw().print_ptrs)
         fprintf(stderr, "qbhip kron arrays: ia %p ja %p val %p | ia_n %p fp %p | ja_f %p val_f %p | wd_n %p wd_f %p | far %p | nnz_n %lld far_slots %lld\n", (void *)A->d_ia,
                 (void *)A->d_ja, (void *)A->d_val, (void *)K.ia_n, (void *)K.ia_f, (void *)K.ja_f, (void *)K.val_f, (void *)K.wd_n, (void *)K.wd_f, (void *)K.d_far,

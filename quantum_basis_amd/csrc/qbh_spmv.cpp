@@ -356,6 +356,7 @@ int spmv_kron(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double 
     nr.ia = K.ia_n;
     nr.ja = K.ja_n;
     nr.ja16 = K.c16_n;
+    nr.len8 = K.len_n;                                       // one class only (kron_near_lens): pass forms 1 and 2
     nr.val = K.val_n;
     nr.wd = K.wd_n;
     nr.n_wb = K.nwb_n;

@@ -263,12 +263,20 @@ int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, Wa
 // at conversion) and a.ja8 holds that value once per line -- ONE column load per lane and block (1 line of the 512-slot block's ~140
 // instead of 8), and one register instead of eight carried across the pipeline stage; the per-slot values are formed by cross-lane
 // moves where the gathers are issued.  Gather addresses, and everything behind them, are those of the per-slot stream.
-template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false>
+// NL (the one-class near passes only): a.len8 holds the rows' lengths, one byte each.  ONE clamped 1-byte load per lane and block, issued
+// with the block's stream (lane l: row l of the block), replaces the two 8-byte row-pointer loads -- a block's ~28 rows are a
+// quarter of a line instead of 2-3 lines -- and one register instead of two is carried across the pipeline stage.  The rows' offsets
+// are the exclusive prefix sums from the descriptor's lead on, formed across the lanes when the block is reduced; every pass of the
+// row loop takes its row's (offset, length) from the owning lane, so a block with more rows than one pass takes (6 % of the
+// headline's) loads no pointers behind the next block's stream.  A block with more than 64 rows takes a further round of 64 lengths
+// inside the loop.  The epilogue operands of the later passes are still loaded there, as before.
+template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false, bool NL = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES, (OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES))) void k_spmv_wave2(SpmvArgs a)
 {
     spmv_args_resolve(a);
     static_assert(!C16 || OPS == 1 || OPS == 2 || OPS == 3, "2-byte columns: the one-class near passes and the sliced far pass");
     static_assert(!G8 || (C16 && OPS == 3), "grouped columns: the sliced far pass with 2-byte columns");
+    static_assert(!NL || OPS == 1 || OPS == 2, "row lengths: the one-class near passes");
     constexpr int NW = 512, RP = 64 / TPR;
     constexpr bool EPI = OPS == 1 || OPS == 2 || OPS == 4, FAR = OPS == 2 || OPS == 4;      // OPS 1: the fused epilogue WITHOUT a far addend
     // The fused reductions under the ordered dynamic walk: which wavefront takes which chunk depends on the run, so per-wavefront
@@ -411,6 +419,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
             int64_t rel = a.ia[g] - base;
             rel = rel < -4096 ? -4096 : rel > 4096 ? 4096 : rel;
             o.s = (int)rel;
+            o.e = 0;
+        } else if constexpr (NL) {
+            // the length of row `lane` of the block, as loaded (the lanes at or beyond b.nr re-read the last row's and are masked where
+            // the prefix sums are formed: nothing here waits for the load)
+            const int last = b.nr > 0 ? b.nr - 1 : 0;
+            o.s = a.len8[(int64_t)b.r0 + (lane < last ? lane : last)];
             o.e = 0;
         } else {
             const bool mine = rloc < b.nr;
@@ -601,6 +615,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
             const int nrows_blk = OPS == 3 ? 8 * b0.nr : b0.nr;
             const int64_t first_row = OPS == 3 ? (int64_t)b0.r0 * 8 : (int64_t)b0.r0;
             open_block(first_row, nrows_blk, b0.cont0, true);
+            // NL: lane l keeps (offset from p0 | length << 16) of row l of the current round of 64 rows; the offsets are the exclusive
+            // prefix sums of the lengths from the end of the round before on (first round: the descriptor's lead).  An offset is at
+            // most the tile's 512, a length at most 255.
+            int pk = 0, round_end = b0.lead;
+            auto lens_round = [&](int len_raw, int rb) {
+                const int len = rb + lane < b0.nr ? len_raw : 0;
+                // inclusive prefix sum over the wavefront by data-parallel moves (no LDS traffic): shifts inside the rows of 16 lanes,
+                // then lane 15 of a row into the next row, lane 31 into the upper half; a lane without a source adds 0
+                int inc = len;
+                inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);       // row_shr:1
+                inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);       // row_shr:2
+                inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false);       // row_shr:4
+                inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false);       // row_shr:8
+                inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);       // row_bcast:15 into rows 1 and 3
+                inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);       // row_bcast:31 into rows 2 and 3
+                pk = (round_end + inc - len) | (len << 16);
+                round_end += __builtin_amdgcn_readlane(inc, 63);
+            };
+            if constexpr (NL) lens_round(oA.s, 0);
             for (int rbase = 0; rbase < nrows_blk; rbase += RP) {
                 const int row = rbase + rloc;
                 int s_ = oA.s, e_ = oA.e;
@@ -609,6 +642,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
                 if (OPS == 3) {
                     group_range(b0, oA.s, row, s_, e_, clip);        // every lane takes part in the cross-lane moves
                     if (row >= nrows_blk) s_ = e_ = 0;
+                } else if constexpr (NL) {
+                    if (rbase > 0 && (rbase & 63) == 0) {            // more than 64 rows: the next 64 lengths, loaded here (correctness path)
+                        const int last = b0.nr - rbase - 1;
+                        lens_round(a.len8[(int64_t)b0.r0 + rbase + (lane < last ? lane : last)], rbase);
+                    }
+                    const int q = __shfl(pk, row & 63, 64);           // every lane takes part in the cross-lane moves
+                    s_ = q & 0xffff;
+                    e_ = s_ + (q >> 16);
+                    if (row >= nrows_blk) s_ = e_ = 0;
+                    if (EPI && rbase > 0 && sub == 0 && row < nrows_blk) {
+                        yo = need_y ? a.yin[b0.r0 + row] : d2{0.0, 0.0};
+                        xi = a.xl[b0.r0 + row];
+                        if (FAR) fr = far_at((int64_t)b0.r0 + row, b0.cls);
+                    }
                 } else if (rbase > 0) {
                     s_ = e_ = 0;
                     if (row < nrows_blk) {
@@ -743,34 +790,42 @@ int64_t wave2_chunk_slots(int64_t n_wb)
 }
 
 // instance table of k_spmv_wave2: every tpr other than 2 and 4 takes the 8 form, every pass form other than 0, 1, 3 and 4 is 2;
-// 2-byte columns (c16) exist for the one-class near passes and the sliced far pass only, grouped ones (g8) for the latter only
-template <int OPS, bool C16, bool G8 = false>
+// 2-byte columns (c16) exist for the one-class near passes and the sliced far pass only, grouped ones (g8) for the latter only,
+// row lengths (nl) for the one-class near passes only
+template <int OPS, bool C16, bool G8 = false, bool NL = false>
 static SpmvKernel wave2_kernel_tpr(int tpr, bool dyn)
 {
     switch (tpr) {
-    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8> : k_spmv_wave2<2, OPS, false, C16, G8>;
-    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8> : k_spmv_wave2<4, OPS, false, C16, G8>;
-    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8> : k_spmv_wave2<8, OPS, false, C16, G8>;
+    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8, NL> : k_spmv_wave2<2, OPS, false, C16, G8, NL>;
+    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8, NL> : k_spmv_wave2<4, OPS, false, C16, G8, NL>;
+    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8, NL> : k_spmv_wave2<8, OPS, false, C16, G8, NL>;
     }
 }
 
-static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8)
+template <int OPS, bool C16>
+static SpmvKernel wave2_kernel_nl(int tpr, bool dyn, bool nl)
 {
+    return nl ? wave2_kernel_tpr<OPS, C16, false, true>(tpr, dyn) : wave2_kernel_tpr<OPS, C16>(tpr, dyn);
+}
+
+static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8, bool nl)
+{
+    if (nl && ops != 1 && ops != 2) return nullptr;
     if (g8) return (c16 && ops == 3) ? wave2_kernel_tpr<3, true, true>(tpr, dyn) : nullptr;
     if (c16) {
         switch (ops) {
-        case 1:  return wave2_kernel_tpr<1, true>(tpr, dyn);
-        case 2:  return wave2_kernel_tpr<2, true>(tpr, dyn);
+        case 1:  return wave2_kernel_nl<1, true>(tpr, dyn, nl);
+        case 2:  return wave2_kernel_nl<2, true>(tpr, dyn, nl);
         case 3:  return wave2_kernel_tpr<3, true>(tpr, dyn);
         default: return nullptr;
         }
     }
     switch (ops) {
     case 0:  return wave2_kernel_tpr<0, false>(tpr, dyn);
-    case 1:  return wave2_kernel_tpr<1, false>(tpr, dyn);
+    case 1:  return wave2_kernel_nl<1, false>(tpr, dyn, nl);
     case 3:  return wave2_kernel_tpr<3, false>(tpr, dyn);
     case 4:  return wave2_kernel_tpr<4, false>(tpr, dyn);
-    default: return wave2_kernel_tpr<2, false>(tpr, dyn);
+    default: return wave2_kernel_nl<2, false>(tpr, dyn, nl);
     }
 }
 
@@ -782,9 +837,9 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
         set_error("launch_spmv_wave2: the dynamic walk of an epilogue pass needs its chunk-partial slots");
         return QBH_EINVAL;
     }
-    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr);
+    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr, a.len8 != nullptr);
     if (k == nullptr) {
-        set_error("launch_spmv_wave2: 2-byte%s columns with pass form %d", a.ja8 ? " grouped" : "", ops);
+        set_error("launch_spmv_wave2: 2-byte%s columns%s with pass form %d", a.ja8 ? " grouped" : "", a.len8 ? " / row lengths" : "", ops);
         return QBH_EINVAL;
     }
     return launch_kernel(k, grid, kBlock, s, a);
@@ -793,7 +848,7 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
 // asks about the ordered dynamic walk with int32 columns (DYN = true, C16 = false) whatever the launch will use: kept as found
 int wave2_kernel_occupancy(int tpr, int ops)
 {
-    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false));
+    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false, false));
 }
 
 }  // namespace qbh
