@@ -783,7 +783,8 @@ int qbh_gen_qudit(qbh_csr **out, int n_sites, int d, int total,
  * The handle behaves like that of qbh_mf_heisenberg: SpMV with its fused epilogue and reductions, qbh_multmv(2), every
  * solver, qbh_csr_set_comm on row shards [row_begin, row_end); qbh_csr_download returns QBH_EUNSUPP.  qbh_csr_get_info
  * reports kernel = QBH_KERNEL_MATRIX_FREE, nnz = the entries qbh_gen_qudit would store for these rows (counted on the
- * device) and bytes_matrix = the tables held.  The real fast path and the packed-real drivers apply when every merged pair
+ * device), bytes_matrix = the tables held and kron_table_kernel = 1 when the class tables (diagonals, targets, amplitudes)
+ * are staged in LDS beside the counting table (0: they exceed the LDS budget and are read from global memory).  The real fast path and the packed-real drivers apply when every merged pair
  * matrix is real; a complex operator (Peierls phases) runs on complex vectors only. */
 int qbh_mf_qudit(qbh_csr **out, int n_sites, int d, int total,
                  int n_pairs, const int32_t *pair_sites /* [2*n_pairs] */, const qbh_z *pair_mat /* [n_pairs * d^4] */,

@@ -973,6 +973,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
     info->basis_detect_ms = A->detect_ms;
     info->kron_table_kernel = (A->kronc.active && A->kronc.table_route) ? 1 : 0;
     if (A->kind == 6) info->kron_table_kernel = A->mfqr.tables_lds;      // the sector's tables in LDS (1) or in global memory (0)
+    if (A->kind == 4) info->kron_table_kernel = A->mfq.tables_lds;       // the class tables in LDS (1) or in global memory (0)
     if (A->kronc.active) {                       // the coded form of the split (row kernel, packed-double vectors)
         info->kron_minor = A->kronc.t.S;
         info->kron_far_nnz = A->kronc.sl.active ? A->kronc.sl.slots_f : A->kronc.far_p.nnz;      // sliced: stored far entries (padding included)

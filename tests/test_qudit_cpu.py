@@ -226,3 +226,17 @@ def test_spin_charge():
     assert qudit.spin_charge(14, 1.5, 0) == 21
     with pytest.raises(ValueError):
         qudit.spin_charge(3, 0.5, 0)
+
+
+def test_row_capacity_and_dimension_at_their_edges():
+    """d = 2: every pair adds one entry to the longest row.  239 pairs give 240 entries, the capacity; 240 give 241.  The largest
+    dimension with int32 columns: C(34, 15) passes, C(34, 16) >= 2^31 - 1 does not."""
+    X = np.zeros((4, 4))
+    X[1, 2] = X[2, 1] = 0.5
+    sites = [(i, j) for i in range(64) for j in range(i + 1, 64)]
+    assert _gen(64, 2, 63, [(i, j, X) for i, j in sites[:239]])[0] in (0, -2)
+    assert _gen(64, 2, 63, [(i, j, X) for i, j in sites[:240]])[0] == EUNSUPP and "241" in _err()
+    rc, dim = _gen(34, 2, 15, [(0, 1, X)], rows=(0, 1))
+    assert rc in (0, -2) and dim == 1_855_967_520 < 2 ** 31 - 1
+    rc, dim = _gen(34, 2, 16, [(0, 1, X)], rows=(0, 1))
+    assert rc == EUNSUPP and dim == 2_203_961_430 and "int32" in _err()

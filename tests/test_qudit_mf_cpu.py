@@ -123,3 +123,20 @@ def test_a_valid_call_without_a_device_fails_loudly():
     got = _mf(4, 3, 4, [(0, 1, M), (1, 2, M)], singles=[(0, np.ones(3))])
     assert got == _call("qbh_gen_qudit", 4, 3, 4, [(0, 1, M), (1, 2, M)], singles=[(0, np.ones(3))]) == (ENODEVICE, 19)
     assert "no HIP device" in _err()
+
+
+def test_row_capacity_241_and_the_largest_sector_are_accepted():
+    """A longest row of 241 entries (240 pairs at d = 2) is QBH_EUNSUPP from qbh_gen_qudit and passes qbh_mf_qudit's checks.
+    qbh_mf_qudit refuses dim >= 2^62, but no shape that packs into 64 bits has such a sector: the largest, C(64, 32) for 64 sites
+    of 2 levels, is 1.83e18 < 2^62 = 4.61e18 (the other widths hold 4^32 and 8^21 words in all, their largest sectors smaller still),
+    so the refusal cannot be reached through the interface and the largest sector is accepted."""
+    X = np.zeros((4, 4))
+    X[1, 2] = X[2, 1] = 0.5
+    sites = [(i, j) for i in range(64) for j in range(i + 1, 64)][:240]
+    assert _call("qbh_gen_qudit", 64, 2, 63, [(i, j, X) for i, j in sites])[0] == EUNSUPP
+    assert _mf(64, 2, 63, [(i, j, X) for i, j in sites])[0] in (0, ENODEVICE)
+    shapes = [(d, n) for d in range(2, 9) for n in (64 // (1 if d <= 2 else 2 if d <= 4 else 3),)]
+    largest = max(qudit.qudit_dim(n, d, n * (d - 1) // 2) for d, n in shapes)
+    assert largest == qudit.qudit_dim(64, 2, 32) == 1832624140942590534 < 2 ** 62
+    rc, dim = _mf(64, 2, 32, [(0, 63, X)], rows=(largest - 4096, largest))
+    assert rc in (0, ENODEVICE) and dim == largest
