@@ -493,6 +493,25 @@ int qbh_corr_spin_dev(int n_sites, int n_dn, const qbh_z *d_vec, const double *d
 int qbh_corr_hubbard_dev(int n_sites, int n_up, int n_dn, const qbh_z *d_vec, const double *d_vec_re, double *norm2,
                          double *dens /* [2][N] */, double *nn /* [4][N][N] */, qbh_z *hop /* [2][N][N] */, qbh_z *flip /* [N][N] */,
                          void *stream);
+/* qbh_corr_qudit_dev: sites with d levels (spin S, bosons with at most d - 1 per site), the sector `total` of qbh_gen_qudit in that
+ * generator's order; l_s is the level of site s in a basis word.  Tables: diag[a*d + l] = f_a(l) for n_diag = K in 0..4 diagonal
+ * one-site functions; string_end[l] = h(l) and string_mid[l] = g(l) (real; both or neither); lower[l] = <l-1| A |l> of an operator
+ * A that lowers the level by one (real, lower[0] ignored).
+ *   pop[s*d + l]                = sum |psi|^2 [l_s = l]   (every one-site diagonal expectation value follows on the host)
+ *   dd[((a*K + b)*N + i)*N + j] = <f_a(i) f_b(j)>, all i, j; the diagonal is <f_a f_b> of the site
+ *   str[i*N + j]                = sum |psi|^2 h(l_i) prod_{i<k<j} g(l_k) h(l_j) for i < j, mirrored; diagonal sum |psi|^2 h(l_i)^2
+ *   aa[i*N + j]                 = <A_i A+_j> = sum over rows w with l_i >= 1, l_j <= d-2 of conj(psi(w')) psi(w) lower[l_i]
+ *                                 lower[l_j + 1], w' = w with l_i - 1 and l_j + 1; Hermitian (i < j is gathered, j < i is its
+ *                                 conjugate), diagonal sum |psi|^2 lower[l_i + 1]^2.  Spin S (l = S - m), A = S^+: <S^+_i S^-_j>;
+ *                                 d = 2 with lower = {0, 1}: pm of qbh_corr_spin_dev.
+ * Checked in this order before the device is looked for: the shape as qbh_gen_qudit (QBH_EINVAL / QBH_EUNSUPP); total outside
+ * 0 .. n_sites (d-1); both or neither vector pointer; n_diag outside 0..4 or diag NULL with n_diag > 0; only one string table; dd
+ * wanted with n_diag = 0, str wanted without tables, aa wanted without lower; a table value that is not finite -> QBH_EINVAL, each
+ * with a message that names the argument; 2^62 rows or more -> QBH_EUNSUPP.  Nothing is written on a refusal. */
+int qbh_corr_qudit_dev(int n_sites, int d, int total, const qbh_z *d_vec, const double *d_vec_re, int n_diag,
+                       const double *diag /* [n_diag][d] */, const double *string_end /* [d] */, const double *string_mid /* [d] */,
+                       const double *lower /* [d] */, double *norm2, double *pop /* [N][d] */, double *dd /* [n_diag][n_diag][N][N] */,
+                       double *str /* [N][N] */, qbh_z *aa /* [N][N] */, void *stream);
 
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.

@@ -1,4 +1,5 @@
-"""All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev), and the host
+"""All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev /
+qbh_corr_qudit_dev), and the host
 arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
 
 The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
@@ -107,6 +108,100 @@ def hubbard_correlations(n_sites, n_up, n_dn, d_vec, real=False, source=None, no
             out["ss"] = ss
     if normalize:
         _nonzero_norm(out["norm2"], "hubbard_correlations")
+        for k in out:
+            if k != "norm2":
+                out[k] = out[k] / out["norm2"]
+    return out
+
+
+def qudit_correlations(n_sites, d, total, d_vec, diag=(), string=None, lower=None, real=False, normalize=True, stream=None):
+    """The thin wrapper of qbh_corr_qudit_dev: a state of the sector `total` of csr_mat.qudit (d levels per site, l_s the level of
+    site s), complex128 or its packed real parts (real=True), in the generator's order.  diag: up to four tables f_a[l];
+    string = (h[l], g[l]); lower[l] = <l-1| A |l> of an operator that lowers the level by one.  Returns dict(norm2, pop[N][d]) and,
+    for the tables that were given, dd[K][K][N][N] = <f_a(i) f_b(j)>, str[N][N] = <h_i prod_{i<k<j} g_k h_j> (diagonal <h_i^2>),
+    aa[N][N] = <A_i A+_j>; with normalize the arrays are divided by norm2 (norm2 itself is returned as measured)."""
+    N, d = int(n_sites), int(d)
+    f = np.ascontiguousarray(np.asarray(diag, dtype=np.float64).reshape(-1, d)) if len(diag) else None
+    K = 0 if f is None else f.shape[0]
+    h = g = None
+    if string is not None:
+        h, g = (np.ascontiguousarray(t, dtype=np.float64).reshape(d) for t in string)
+    low = np.ascontiguousarray(lower, dtype=np.float64).reshape(d) if lower is not None else None
+    addr = _addr(d_vec)
+    n2 = C.c_double()
+    pop = np.zeros((N, d))
+    dd = np.zeros((K, K, N, N)) if K else None
+    st = np.zeros((N, N)) if string is not None else None
+    aa = np.zeros((N, N), dtype=np.complex128) if low is not None else None
+    check(lib().qbh_corr_qudit_dev(N, d, int(total), None if real else addr, addr if real else None, K, _p(f), _p(h), _p(g), _p(low),
+                                   C.byref(n2), _p(pop), _p(dd), _p(st), _p(aa), stream), "qbh_corr_qudit_dev")
+    out = {"norm2": n2.value, "pop": pop}
+    for k, a in (("dd", dd), ("str", st), ("aa", aa)):
+        if a is not None:
+            out[k] = a
+    if normalize:
+        _nonzero_norm(out["norm2"], "qudit_correlations")
+        for k in out:
+            if k != "norm2":
+                out[k] = out[k] / out["norm2"]
+    return out
+
+
+def _spin_s_from_raw(S, raw):
+    """host arithmetic of spin_s_correlations on the raw arrays of qudit_correlations (diag = (m,), A = S^+)"""
+    from . import qudit as qd
+    d = qd._two_s(S) + 1
+    Sv = (d - 1) / 2.0
+    m = Sv - np.arange(d)
+    zz, pm = raw["dd"][0, 0], raw["aa"]
+    ss = zz + pm.real
+    ss[np.diag_indices(len(zz))] = Sv * (Sv + 1) * raw["norm2"]
+    return {"norm2": raw["norm2"], "sz": raw["pop"] @ m, "sz2": raw["pop"] @ (m * m), "zz": zz, "pm": pm, "ss": ss,
+            "string": raw.get("str")}
+
+
+def spin_s_correlations(n_sites, S, two_sz, d_vec, real=False, normalize=True):
+    """<S^z_i>, <(S^z_i)^2>, <S^z_i S^z_j>, <S^+_i S^-_j>, <S_i . S_j> = zz + Re pm (S(S+1) on the diagonal) and, for integer S, the
+    den Nijs-Rommelse string correlator <S^z_i exp(i pi sum_{i<k<j} S^z_k) S^z_j> of a spin-S state with 2 S^z = two_sz (basis of
+    csr_mat.spin_heisenberg), all pairs in one pass.  Returns dict(norm2, sz, sz2, zz, pm, ss, string); string is None for
+    half-integer S (its phases are complex).  With the keys zz and pm, energy_from_correlations gives <H> of the spin-S Heisenberg
+    operator."""
+    from . import qudit as qd
+    two_s = qd._two_s(S)
+    d, Sv = two_s + 1, two_s / 2.0
+    m = Sv - np.arange(d)
+    lower = np.real(np.append(0.0, np.diag(qd.spin_matrices(S)[1], 1)))            # <l-1| S^+ |l>
+    string = (m, np.where(np.arange(d) % 2 == (two_s // 2) % 2, 1.0, -1.0)) if two_s % 2 == 0 else None      # (-1)^m, m = S - l
+    raw = qudit_correlations(n_sites, d, qd.spin_charge(n_sites, S, two_sz), d_vec, diag=(m,), string=string, lower=lower, real=real,
+                             normalize=False)
+    out = _spin_s_from_raw(S, raw)
+    if normalize:
+        _nonzero_norm(out["norm2"], "spin_s_correlations")
+        for k in out:
+            if k != "norm2" and out[k] is not None:
+                out[k] = out[k] / out["norm2"]
+    return out
+
+
+def _bose_from_raw(n_max, raw):
+    """host arithmetic of bose_correlations on the raw arrays of qudit_correlations (diag = (n,), A = b, string = (1, (-1)^n))"""
+    n = np.arange(n_max + 1, dtype=np.float64)
+    obdm = raw["aa"].T.copy()                                 # <b+_i b_j> = <b_j b+_i> off the diagonal
+    k = np.diag_indices(len(obdm))
+    obdm[k] = raw["aa"][k] - raw["norm2"]                     # b+ b = b b+ - 1 (exact while level n_max carries no weight; dens is <n> always)
+    return {"norm2": raw["norm2"], "dens": raw["pop"] @ n, "nn": raw["dd"][0, 0], "obdm": obdm, "parity": raw["str"]}
+
+
+def bose_correlations(n_sites, n_bosons, n_max, d_vec, real=False, normalize=True):
+    """<n_i>, <n_i n_j>, the one-body density matrix obdm[i][j] = <b+_i b_j> and the parity string <prod_{i<k<j} (-1)^{n_k}> of a
+    state of n_bosons bosons with at most n_max per site (basis of csr_mat.bose_hubbard), all pairs in one pass.  Returns
+    dict(norm2, dens, nn, obdm, parity); momentum_distribution(obdm, ...) and structure_factor(nn, ...) take them as they are."""
+    n = np.arange(n_max + 1, dtype=np.float64)
+    raw = qudit_correlations(n_sites, n_max + 1, n_bosons, d_vec, diag=(n,), string=(np.ones(n_max + 1), 1.0 - 2.0 * (np.arange(n_max + 1) % 2)),
+                             lower=np.sqrt(n), real=real, normalize=False)
+    out = _bose_from_raw(n_max, raw)
+    if normalize:
+        _nonzero_norm(out["norm2"], "bose_correlations")
         for k in out:
             if k != "norm2":
                 out[k] = out[k] / out["norm2"]

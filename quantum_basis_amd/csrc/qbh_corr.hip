@@ -14,32 +14,10 @@
 #include "qbh_internal.hpp"
 #include "qbh_device.hpp"
 #include "qbh_gen_util.hpp"
+#include "qbh_corr.hpp"                                      // kCorrBlock, kCorrLdsCap, corr_block_partials, corr_uniform
 
 namespace qbh {
 namespace {
-
-constexpr int kCorrBlock = 256;                              // 155 VGPRs (real spin form): three workgroups of four wavefronts per CU
-constexpr size_t kCorrLdsCap = (size_t)150 * 1024;           // the budget of launch_mf_heis
-
-// acc summed over the workgroup into partials[(blockIdx.x * gridDim.y + blockIdx.y) * NA ..]: every wavefront, then lane c adds
-// the wavefronts of accumulator c in order (the pattern of mf_block_partials for NA accumulators).  red: NA * (kCorrBlock / 64).
-template <int NA>
-__device__ __forceinline__ void corr_block_partials(double (&acc)[NA], double *red, double *partials)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int c = 0; c < NA; ++c) acc[c] = wave_sum(acc[c]);
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < NA; ++c) red[c * (kCorrBlock / 64) + wave] = acc[c];
-    }
-    __syncthreads();
-    if (tid < NA) {
-        double s = 0.0;
-        for (int w = 0; w < kCorrBlock / 64; ++w) s += red[tid * (kCorrBlock / 64) + w];
-        partials[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * NA + tid] = s;
-    }
-}
 
 // Second stage: out[c] = sum of partials[i][c] over the workgroups i.  One lane per component (a launch has hundreds of them, and
 // k_reduce_partials would walk them one after another); the 16 wavefronts of a workgroup take every 16th partial and are added in
@@ -96,12 +74,6 @@ constexpr int spin_acc() { return (REALX ? 2 : 3) * kSpinGroup; }
 template <typename W>
 constexpr int spin_rows() { return 32 / (int)sizeof(W); }        // R: rows per lane and tile (9 - 10 KB of patterns per workgroup)
 
-// v is the same in every lane: keep it in scalar registers
-__device__ __forceinline__ uint32_t corr_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t corr_uniform(uint64_t v)
-{
-    return ((uint64_t)corr_uniform((uint32_t)(v >> 32)) << 32) | corr_uniform((uint32_t)v);
-}
 __device__ __forceinline__ int corr_popc(uint32_t v) { return __popc(v); }
 __device__ __forceinline__ int corr_popc(uint64_t v) { return __popcll(v); }
 __device__ __forceinline__ int corr_ctz(uint32_t v) { return v ? __ffs((int)v) - 1 : 0; }
@@ -391,6 +363,8 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_hubbard(CorrHub t)
 }
 
 // ------------------------------------------------------------------------------------------------------ host side --
+}  // namespace
+
 // workgroups along x: what the LDS lets a CU hold (four at most), each walking its share of the `rows_per_block`-row pieces
 int corr_grid(int64_t dim, size_t lds, int rows_per_block)
 {
@@ -410,6 +384,8 @@ int corr_finish(double *d_partials, int n_parts, int ncomp, std::vector<double> 
     QBH_HIP(hipStreamSynchronize(s));
     return QBH_OK;
 }
+
+namespace {
 
 size_t corr_spin_lds(int n_sites, int n_dn)
 {

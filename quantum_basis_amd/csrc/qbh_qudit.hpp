@@ -44,6 +44,36 @@ __device__ __forceinline__ int qd_level(uint64_t w, int bits, int s)
     return (int)((w >> (s * bits)) & ((1ULL << bits) - 1));
 }
 
+// charge of sites 0..s
+__device__ __forceinline__ int qd_charge(uint64_t w, int bits, int s)
+{
+    const int nb = (s + 1) * bits;
+    if (nb < 64) w &= (1ULL << nb) - 1;
+    if (bits == 1) return __popcll(w);
+    if (bits == 2) return __popcll(w & 0x5555555555555555ULL) + 2 * __popcll(w & 0xAAAAAAAAAAAAAAAAULL);
+    const uint64_t m0 = 0x9249249249249249ULL;          // bit 0 of every 3-bit field
+    return __popcll(w & m0) + 2 * __popcll(w & (m0 << 1)) + 4 * __popcll(w & (m0 << 2));
+}
+
+// rank(new) - rank(old) for the move (l_i, l_j) -> (ni, nj) on sites i < j of w, Q = charge of sites 0..j (mod 2^64)
+__device__ __forceinline__ uint64_t qd_move_delta(const uint64_t *cum, int tw, int bits, uint64_t w, int i, int j, int Q, int lj,
+                                                 int ni, int nj)
+{
+    const uint64_t *cj = cum + j * tw;
+    uint64_t delta = cj[Q - lj] - cj[Q - nj];
+    int Qo = Q - lj, Qn = Q - nj;
+    for (int t = j - 1; t > i; --t) {
+        const uint64_t *ct = cum + t * tw;
+        const int l = qd_level(w, bits, t);
+        delta += (ct[Qn] - ct[Qn - l]) - (ct[Qo] - ct[Qo - l]);
+        Qo -= l;
+        Qn -= l;
+    }
+    (void)ni;                                              // Qn - ni == Qo - l_i: the lower halves cancel
+    const uint64_t *ci = cum + i * tw;
+    return delta + ci[Qn] - ci[Qo];
+}
+
 // the word of rank r among the words of charge `total` (walks from the most significant site down)
 __device__ __forceinline__ uint64_t qd_unrank(const uint64_t *cum, int n_sites, int d, int bits, int tw, int total, uint64_t r)
 {
