@@ -274,7 +274,9 @@ void qbh_csr_destroy(qbh_csr *A);
 typedef struct qbh_csr_info {
     int64_t nrows, ncols, row_offset, nnz;   /* nnz as applied (full storage)                 */
     int64_t n_blocks;                        /* row blocks of the CSR geometry (both parts of a split shard) */
-    int64_t bytes_matrix;                    /* HBM bytes held by the matrix arrays            */
+    int64_t bytes_matrix;                    /* HBM bytes held by the matrix arrays, the streams derived from them for the passes
+                                              * of a split included (near row lengths; the sliced far part's columns, 2 bytes, and
+                                              * values, 16 bytes, once per 8 slots, each with a 64-entry tail)                   */
     int64_t bytes_algorithmic;               /* nnz*20 + (nrows+1)*8 + nrows*16 + nrows*16     */
     int     kernel;                          /* QBH_KERNEL_* actually selected                 */
     int     value_dict;                      /* number of dictionary entries, 0 = not coded    */

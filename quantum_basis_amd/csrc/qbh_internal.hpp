@@ -39,6 +39,7 @@ struct DebugSw {
     int kronc_abl = 0, kronc_far_chunk = 0, kronc_far_ng = 0, kronc_far_nt = 0;
     int no_far_align = 0;     // in-place split: the far part directly behind the near part (unaligned)
     int far_cols8 = -1;       // 0: the sliced far pass keeps reading its 2-byte columns slot by slot (no grouped copy, KronSplit::c8_f; A/B only)
+    int far_vals8 = -1;       // 0: the sliced far pass keeps reading its values slot by slot (no grouped copy, KronSplit::v8_f; A/B only).  far_cols8=0 implies it
     int near_lens = -1;       // 0: the near pass keeps reading its row pointers (no length array, KronSplit::len_n; A/B only)
     int near_len_cap = 0;     // > 0: the longest near row the length array takes (default 255: one byte); a lower cap lets a test reach the fallback
     int no_defer = 0;         // Lanczos: read <u, w> back every step instead of keeping it on the device
@@ -138,6 +139,10 @@ struct SpmvArgs {
     // sliced far part whose 8 slots of a line all name the same major index (T (x) 1): that value once per 8 slots, entry i >> 3 for
     // slot i (k_spmv_wave2<.., G8 = true>: one column load per lane and block instead of eight); nullptr: ja16 is read
     const uint16_t *ja8;
+    // ... and whose 8 values of a line are equal bit for bit as well (an up hop's sign does not depend on the down configuration): that
+    // value once per 8 slots, entry i >> 3 for slot i (k_spmv_wave2<.., V8 = true>: the 8 lanes of a line load one address, 8 lines per block instead of 64).
+    // Only with ja8; nullptr: val is read
+    const d2      *val8;
     // one-class near part (k_spmv_wave2<.., NL > 0>, pass forms 1 and 2): the length of every near row, one byte each, nrows + 64
     // entries (the tail zero); a block's row offsets are the prefix sums of its rows' lengths, formed across the lanes.  ia stays
     // the stored form and is still read for a row longer than the tile.  nullptr: ia is read.
@@ -317,6 +322,8 @@ int launch_kron_desc_c16(WaveDesc *wd, int64_t n_wb, int64_t div, bool far, bool
 int launch_kron_c16_near(const WaveDesc *wd, int64_t n_wb, const int32_t *ja, int64_t S, int64_t col0, uint16_t *out, int *flag, hipStream_t s);
 int launch_kron_c16_far(const WaveDesc *wd, const int32_t *ja, int64_t slots, int64_t NU, uint16_t *out, int *flag, hipStream_t s);
 int launch_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *flag, hipStream_t s);
+// the far values once per 8 slots; *flag is raised when the 8 values of a line are not the same 128 bits
+int launch_kron_v8_far(const d2 *val, int64_t slots, d2 *out, int *flag, hipStream_t s);
 // near row lengths as bytes (out[r] = ia[r + 1] - ia[r]); *flag is raised when a row is longer than cap, or when the lengths of a
 // wave block's rows do not add up to the block's span of entries
 int launch_kron_near_lens(const int64_t *ia, int64_t nrows, const WaveDesc *wd, int64_t n_wb, int cap, uint8_t *out, int *flag, hipStream_t s);
@@ -800,6 +807,7 @@ struct qbh_csr {
         int32_t *ja_n = nullptr, *ja_f = nullptr;
         uint16_t *c16_n = nullptr, *c16_f = nullptr;    // 2-byte columns (qbh_opts.kron_cols16): allocations of their own; the int32 form of that part is gone
         uint16_t *c8_f = nullptr;       // c16_f once per 8 slots, where the 8 are equal throughout: what the far pass reads (derived; lives and dies with c16_f)
+        qbh::d2 *v8_f = nullptr;        // val_f once per 8 slots (+ 64 zeroed), where the 8 are the same bits throughout: what the far pass reads (derived, only beside c8_f; val_f stays the stored form)
         uint8_t *len_n = nullptr;       // ia_n[r + 1] - ia_n[r], one byte per near row (+ 64 zeroed): what the one-class near pass reads (derived; ia_n stays the stored form)
         qbh::d2 *val_n = nullptr, *val_f = nullptr;
         qbh::WaveDesc *wd_n = nullptr, *wd_f = nullptr;

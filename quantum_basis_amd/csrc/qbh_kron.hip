@@ -321,6 +321,23 @@ __global__ __launch_bounds__(kBlock) void k_kron_c8_far(const uint16_t *c16, int
     if (bad) *flag = 1;
 }
 
+// the far values once per 8 slots, the same way.  Compared as bits, both doubles as 64-bit integers: a floating-point compare would
+// take -0.0 for 0.0 and never find a NaN equal to itself, and the pass must multiply by exactly what the per-slot stream holds.
+__global__ __launch_bounds__(kBlock) void k_kron_v8_far(const d2 *val, int64_t slots, d2 *out, int *flag)
+{
+    bool bad = false;
+    for (int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; l < (slots >> 3); l += (int64_t)gridDim.x * blockDim.x) {
+        const d2 v = val[l << 3];
+        const long long re = __double_as_longlong(v.x), im = __double_as_longlong(v.y);
+        for (int j = 1; j < 8; ++j) {
+            const d2 w = val[(l << 3) + j];
+            bad = bad || __double_as_longlong(w.x) != re || __double_as_longlong(w.y) != im;
+        }
+        out[l] = v;
+    }
+    if (bad) *flag = 1;
+}
+
 // near row lengths as bytes: what the near pass reads in place of the row pointers.  A row longer than cap raises the flag.
 __global__ __launch_bounds__(kBlock) void k_kron_near_lens(const int64_t *ia, int64_t nrows, int cap, uint8_t *out, int *flag)
 {
@@ -381,6 +398,13 @@ int launch_kron_c16_far(const WaveDesc *wd, const int32_t *ja, int64_t slots, in
 int launch_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *flag, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kron_c8_far, dim3(4096), dim3(kBlock), 0, s, c16, slots, out, flag);
+    QBH_HIP(hipGetLastError());
+    return QBH_OK;
+}
+
+int launch_kron_v8_far(const d2 *val, int64_t slots, d2 *out, int *flag, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kron_v8_far, dim3(4096), dim3(kBlock), 0, s, val, slots, out, flag);
     QBH_HIP(hipGetLastError());
     return QBH_OK;
 }

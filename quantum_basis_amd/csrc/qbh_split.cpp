@@ -24,7 +24,7 @@ void kron_free_aux(qbh_csr *A)
 {
     qbh_csr::KronSplit &K = A->kron;
     for (void *q : {(void *)K.ia_n, (void *)K.ia_f, (void *)K.wd_n, (void *)K.wd_f, (void *)K.d_xt, (void *)K.d_far, (void *)K.ia_x, (void *)K.xrow,
-                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.len_n, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
+                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.v8_f, (void *)K.len_n, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
         if (q) (void)hipFree(q);
     if (K.own_far) {
         if (K.ja_f) (void)hipFree(K.ja_f);
@@ -202,6 +202,35 @@ int kron_short_cols(qbh_csr *A)
                 (void)hipFree(c);
             } else {
                 K.c8_f = c;
+            }
+        }
+    }
+    // ... and the 8 VALUES of such a line are equal too wherever the hop's amplitude and sign depend on the major index alone (a
+    // generator that orders all up operators before all down operators: 88 % of what the far pass reads is then repetition).  The far
+    // pass reads the value once per line from a copy 1/8 the size (k_spmv_wave2's V8).  A derived stream only, taken beside c8_f and
+    // never without it: val_f stays what download, restore, merge, shards and checkpoints read.  The comparison is on the bits (-0.0
+    // and 0.0, or two NaNs, are different values); one line that is not uniform, no room, or any error: the whole operator keeps the
+    // per-slot values.  QBH_DEBUG=far_vals8=0 skips it (A/B of the two streams from one build).
+    if (K.c8_f && K.val_f && qbh::debug_sw().far_vals8 != 0) {
+        const int64_t cnt = K.far_slots / 8;
+        d2 *v = nullptr;
+        if (hipMalloc(&v, (size_t)(cnt + 64) * sizeof(d2)) != hipSuccess) {
+            (void)hipGetLastError();
+            v = nullptr;
+        }
+        if (v) {
+            int bad = 0;
+            hipError_t he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+            if (he == hipSuccess) he = hipMemsetAsync(v + cnt, 0, 64 * sizeof(d2), s);
+            const int rc = he == hipSuccess ? qbh::launch_kron_v8_far(K.val_f, K.far_slots, v, A->d_flag, s) : QBH_OK;
+            if (rc == QBH_OK && he == hipSuccess) he = hipMemcpyAsync(&bad, A->d_flag, sizeof(int), hipMemcpyDeviceToHost, s);
+            if (rc == QBH_OK && he == hipSuccess) he = hipStreamSynchronize(s);
+            if (rc == QBH_OK && he == hipSuccess) he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+            if (rc != QBH_OK || he != hipSuccess || bad) {
+                (void)hipGetLastError();
+                (void)hipFree(v);
+            } else {
+                K.v8_f = v;
             }
         }
     }

@@ -337,6 +337,7 @@ int spmv_kron(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double 
     f.ja = K.ja_f;
     f.ja16 = K.c16_f;
     f.ja8 = K.c8_f;
+    f.val8 = K.v8_f;
     f.kS = K.t.S;
     f.kNU = K.NUg;
     f.kB = K.t.B;

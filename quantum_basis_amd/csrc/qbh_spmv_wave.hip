@@ -263,6 +263,12 @@ int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, Wa
 // at conversion) and a.ja8 holds that value once per line -- ONE column load per lane and block (1 line of the 512-slot block's ~140
 // instead of 8), and one register instead of eight carried across the pipeline stage; the per-slot values are formed by cross-lane
 // moves where the gathers are issued.  Gather addresses, and everything behind them, are those of the per-slot stream.
+// V8 (only with G8): the 8 values of every line are the same bits as well (verified at conversion) and a.val8 holds that value once per
+// line -- the eight value loads of a block stay, but the 8 lanes of a line share one address: each load is ONE 128-byte line instead
+// of eight (8 lines of the block's stream instead of 64).  Every lane holds the value of its own slot as before, so nothing behind
+// the loads changes: the operands of every product are those of the per-slot stream.  (The other form -- one load per lane and
+// block, the slot's value taken from the line's lane by cross-lane moves: 96 VGPRs instead of 154 -- measured 0.28 ms slower on the
+// headline's far pass, profiles/far_vals8_time.txt; LDS, not registers, caps this pass's occupancy.)
 // NL (the one-class near passes only): a.len8 holds the rows' lengths, one byte each.  ONE clamped 1-byte load per lane and block, issued
 // with the block's stream (lane l: row l of the block), replaces the two 8-byte row-pointer loads -- a block's ~28 rows are a
 // quarter of a line instead of 2-3 lines -- and one register instead of two is carried across the pipeline stage.  The rows' offsets
@@ -270,13 +276,14 @@ int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, Wa
 // row loop takes its row's (offset, length) from the owning lane, so a block with more rows than one pass takes (6 % of the
 // headline's) loads no pointers behind the next block's stream.  A block with more than 64 rows takes a further round of 64 lengths
 // inside the loop.  The epilogue operands of the later passes are still loaded there, as before.
-template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false, bool NL = false>
+template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false, bool NL = false, bool V8 = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES, (OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES))) void k_spmv_wave2(SpmvArgs a)
 {
     spmv_args_resolve(a);
     static_assert(!C16 || OPS == 1 || OPS == 2 || OPS == 3, "2-byte columns: the one-class near passes and the sliced far pass");
     static_assert(!G8 || (C16 && OPS == 3), "grouped columns: the sliced far pass with 2-byte columns");
     static_assert(!NL || OPS == 1 || OPS == 2, "row lengths: the one-class near passes");
+    static_assert(!V8 || G8, "grouped values: only beside the grouped columns");
     constexpr int NW = 512, RP = 64 / TPR;
     constexpr bool EPI = OPS == 1 || OPS == 2 || OPS == 4, FAR = OPS == 2 || OPS == 4;      // OPS 1: the fused epilogue WITHOUT a far addend
     // The fused reductions under the ordered dynamic walk: which wavefront takes which chunk depends on the run, so per-wavefront
@@ -407,10 +414,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
         if constexpr (C16 && OPS != 3) {
             if (b.n > 0 && lane < b.lead) c[0] = 0;
         }
+        if constexpr (V8) {
+            // slot lane + 64 u sits in line lane / 8 + 8 u: the 8 lanes of a line read the line's value themselves (one 128-byte line
+            // per load); a line past the block's end reads the last one, which is what the clamped per-slot loads name there
+            const int lm = nm1 >> 3;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = lane + u * 64;
-            v[u] = ntload(a.val + base + (i < nn ? i : nm1));
+            for (int u = 0; u < 8; ++u) {
+                const int l = (lane >> 3) + 8 * u;
+                v[u] = ntload(a.val8 + (base >> 3) + (l < lm ? l : lm));
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = lane + u * 64;
+                v[u] = ntload(a.val + base + (i < nn ? i : nm1));
+            }
         }
         if (OPS == 3) {
             const int64_t ng = (a.nrows + 7) >> 3;
@@ -791,14 +809,14 @@ int64_t wave2_chunk_slots(int64_t n_wb)
 
 // instance table of k_spmv_wave2: every tpr other than 2 and 4 takes the 8 form, every pass form other than 0, 1, 3 and 4 is 2;
 // 2-byte columns (c16) exist for the one-class near passes and the sliced far pass only, grouped ones (g8) for the latter only,
-// row lengths (nl) for the one-class near passes only
-template <int OPS, bool C16, bool G8 = false, bool NL = false>
+// row lengths (nl) for the one-class near passes only; grouped values (v8) only beside grouped columns
+template <int OPS, bool C16, bool G8 = false, bool NL = false, bool V8 = false>
 static SpmvKernel wave2_kernel_tpr(int tpr, bool dyn)
 {
     switch (tpr) {
-    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8, NL> : k_spmv_wave2<2, OPS, false, C16, G8, NL>;
-    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8, NL> : k_spmv_wave2<4, OPS, false, C16, G8, NL>;
-    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8, NL> : k_spmv_wave2<8, OPS, false, C16, G8, NL>;
+    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8, NL, V8> : k_spmv_wave2<2, OPS, false, C16, G8, NL, V8>;
+    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8, NL, V8> : k_spmv_wave2<4, OPS, false, C16, G8, NL, V8>;
+    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8, NL, V8> : k_spmv_wave2<8, OPS, false, C16, G8, NL, V8>;
     }
 }
 
@@ -808,10 +826,14 @@ static SpmvKernel wave2_kernel_nl(int tpr, bool dyn, bool nl)
     return nl ? wave2_kernel_tpr<OPS, C16, false, true>(tpr, dyn) : wave2_kernel_tpr<OPS, C16>(tpr, dyn);
 }
 
-static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8, bool nl)
+static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8, bool nl, bool v8)
 {
     if (nl && ops != 1 && ops != 2) return nullptr;
-    if (g8) return (c16 && ops == 3) ? wave2_kernel_tpr<3, true, true>(tpr, dyn) : nullptr;
+    if (v8 && !g8) return nullptr;
+    if (g8) {
+        if (!c16 || ops != 3) return nullptr;
+        return v8 ? wave2_kernel_tpr<3, true, true, false, true>(tpr, dyn) : wave2_kernel_tpr<3, true, true>(tpr, dyn);
+    }
     if (c16) {
         switch (ops) {
         case 1:  return wave2_kernel_nl<1, true>(tpr, dyn, nl);
@@ -837,9 +859,10 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
         set_error("launch_spmv_wave2: the dynamic walk of an epilogue pass needs its chunk-partial slots");
         return QBH_EINVAL;
     }
-    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr, a.len8 != nullptr);
+    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr, a.len8 != nullptr, a.val8 != nullptr);
     if (k == nullptr) {
-        set_error("launch_spmv_wave2: 2-byte%s columns%s with pass form %d", a.ja8 ? " grouped" : "", a.len8 ? " / row lengths" : "", ops);
+        set_error("launch_spmv_wave2: 2-byte%s columns%s%s with pass form %d", a.ja8 ? " grouped" : "", a.len8 ? " / row lengths" : "",
+                  a.val8 ? " / grouped values" : "", ops);
         return QBH_EINVAL;
     }
     return launch_kernel(k, grid, kBlock, s, a);
@@ -848,7 +871,7 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
 // asks about the ordered dynamic walk with int32 columns (DYN = true, C16 = false) whatever the launch will use: kept as found
 int wave2_kernel_occupancy(int tpr, int ops)
 {
-    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false, false));
+    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false, false, false));
 }
 
 }  // namespace qbh
