@@ -1,6 +1,6 @@
 // qbh_api.cpp -- the extern "C" surface of libqbhip.so, part 1: errors, options, operator lifetime (create / adopt / destroy /
 // info / set_basis), geometry of the unsplit forms, device vectors, download.  The other parts: qbh_split.cpp, qbh_commattach.cpp,
-// qbh_spmv.cpp, qbh_solvers.cpp (qbh_api_priv.hpp says what each holds).  Each entry point names the reference function it
+// qbh_spmv.cpp, qbh_spmv_kron.cpp, qbh_solvers.cpp (qbh_api_priv.hpp says what each holds).  Each entry point names the reference function it
 // replaces in include/qbhip.h.
 #include <algorithm>
 #include <chrono>
@@ -42,7 +42,7 @@ static void parse_debug(const char *e, DebugSw &d)
                         {"grid", &d.grid, nullptr}, {"wave_tpr", &d.wave_tpr, nullptr}, {"chunk_mult", &d.chunk_mult, nullptr},
                         {"trace_create", &d.trace_create, nullptr}, {"trace_tune", &d.trace_tune, nullptr}, {"trace_dict", &d.trace_dict, nullptr},
                         {"print_ptrs", &d.print_ptrs, nullptr}, {"sec_walk", &d.sec_walk, nullptr}, {"sec_grid", &d.sec_grid, nullptr}, {"sec_tile", &d.sec_tile, nullptr},
-                        {"sec_unroll", &d.sec_unroll, nullptr}, {"wave_pipelined", &d.wave_pipelined, nullptr}, {"create_chunk", nullptr, &d.create_chunk},
+                        {"sec_unroll", &d.sec_unroll, nullptr}, {"create_chunk", nullptr, &d.create_chunk},
                         {"force_ragged", &d.force_ragged, nullptr}, {"mf_row", &d.mf_row, nullptr}, {"mf_chunk", &d.mf_chunk, nullptr},
                         {"mf_window", &d.mf_window, nullptr}, {"kronc_abl", &d.kronc_abl, nullptr}, {"kronc_far_chunk", &d.kronc_far_chunk, nullptr},
                         {"kronc_far_ng", &d.kronc_far_ng, nullptr}, {"kronc_far_nt", &d.kronc_far_nt, nullptr}, {"no_far_align", &d.no_far_align, nullptr}, {"far_cols8", &d.far_cols8, nullptr},

@@ -4,8 +4,9 @@
 //   qbh_split.cpp   the Kronecker split built in place (complex128) and its coded sibling: kron_build, kron_short_cols,
 //                   kron_restore, kronc_build
 //   qbh_commattach.cpp   qbh_csr_set_comm: the collective agreement on the exchange form, the gather in parts
-//   qbh_spmv.cpp    SpMV dispatch (spmv_run, spmv_kron), reductions, the real wire format, BLAS-1 runs, device building blocks,
-//                   the host-vector seam (qbh_multmv / qbh_multmv2)
+//   qbh_spmv.cpp    SpMV dispatch (spmv_run) with the matrix-free and stored-CSR routes, the steps all routes share, reductions,
+//                   the real wire format, BLAS-1 runs, device building blocks, the host-vector seam (qbh_multmv / qbh_multmv2)
+//   qbh_spmv_kron.cpp    spmv_kron: the SpMV of an operator split in place, on one GPU and under a communicator
 //   qbh_solvers.cpp lanczos_core, cg_core, qbh_iram, qbh_hess_eigen
 #pragma once
 
@@ -56,7 +57,19 @@ int finish_reduction(qbh_csr *A, int nparts, int ncomp, double *host_out);
 void harvest_events(qbh_csr *A);
 int next_event_set(qbh_csr *A);
 int deferred_reduction(qbh_csr *A, int nparts);
-int spmv_kron(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double gamma, double *red);
+// the steps every SpMV route takes: the profiling bracket (ev0; then k = 1, 2 or 3 for ev1 / ev2 / ev3), the CU count of the
+// device, the wait for a whole gather (expand: packed real parts -> complex), and the counters and reductions at the end
+int prof_begin(qbh_csr *A);
+int prof_mark(qbh_csr *A, int k);
+int cu_count(qbh_csr *A);
+int gather_wait(qbh_csr *A, bool expand);
+int spmv_finish(qbh_csr *A, int nparts, double *red, bool real_gather);
+// y <- alpha*H x + beta*y + gamma*x_local ; red (host, 3 doubles) optional.
+// Without a communicator x is the full-length vector (ncols) and the shard-local part is
+// x + row_offset; with one, x is shard-local and is gathered through the hooks first.
+// A split shard runs two launches: the locally-owned columns (which only need this rank's block of x
+// and therefore overlap with the all-gather), then the remote columns, accumulating into y; the fused
+// reductions are produced by the last launch, on the final y.
 int spmv_run(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double gamma, double *red);
 int enable_real_wire(qbh_csr *A, std::initializer_list<const d2 *> vecs);
 int finish_real_wire(qbh_csr *A);
@@ -65,6 +78,8 @@ int axpy_norm_run(qbh_csr *A, d2 alpha, const d2 *x, d2 *y, double *nrm2sq);
 int axpy_norm_deferred(qbh_csr *A, double scale, const d2 *x, d2 *y, double *dot_out, double *nrm2sq);
 int nrm2_run(qbh_csr *A, const d2 *x, double *nrm);
 int multmv_host(qbh_csr *A, const qbh_z *x_host, qbh_z *y_host, double beta);
+// ---- qbh_spmv_kron.cpp ----
+int spmv_kron(qbh_csr *A, const d2 *x, d2 *y, double alpha, double beta, double gamma, double *red);
 
 struct Bind {   // make the operator's device current for the duration of a call
     int prev = -1;
@@ -82,12 +97,6 @@ struct Bind {   // make the operator's device current for the duration of a call
 
 inline double *scal_buf(qbh_csr *A) { return A->has_comm ? A->comm.d_scal : A->d_scal; }
 
-// y <- alpha*H x + beta*y + gamma*x_local ; red (host, 3 doubles) optional.
-// Without a communicator x is the full-length vector (ncols) and the shard-local part is
-// x + row_offset; with one, x is shard-local and is gathered through the hooks first.
-// A split shard runs two launches: the locally-owned columns (which only need this rank's block of x
-// and therefore overlap with the all-gather), then the remote columns, accumulating into y; the fused
-// reductions are produced by the last launch, on the final y.
 // does the next complex SpMV of this handle take the passes of the Kronecker split?  (An operator split in place has no
 // other form: spmv_run refuses whatever would need its CSR.)
 inline bool kron_path(const qbh_csr *A)

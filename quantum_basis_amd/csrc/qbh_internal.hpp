@@ -32,7 +32,6 @@ struct DebugSw {
     int tpr = 0, unroll = 0, grid = 0, wave_tpr = 0, chunk_mult = 0;      // launch-geometry overrides
     int trace_create = 0, trace_tune = 0, trace_dict = 0, print_ptrs = 0;
     int sec_walk = -1, sec_grid = 0, sec_unroll = 0, sec_tile = 0;        // matrix-free sector kernel
-    int wave_pipelined = 0;   // the pipelined wave kernel on an unsplit operator
     long long create_chunk = 0;                                           // staging chunk of qbh_csr_create (nonzeros)
     int force_ragged = 0;     // native communicator: the send/recv all-gather-v even for uniform cuts
     int mf_row = -1, mf_chunk = 0, mf_window = 0;                         // matrix-free Hubbard kernel

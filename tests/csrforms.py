@@ -278,7 +278,7 @@ def route(kernel_opt, value_dict, ia, val, npb_opt=0, xcd_swizzle=2, wave_walk=-
     """What an unsplit, unsharded-or-sharded CSR operator created with these options runs under qbh_spmv_dev (complex x, y):
     dict(kernel, info_kernel, dict_mode, n_dict, tpr, npb, unroll, n_blocks (info.n_blocks), walk, grid_max, key) or None when
     creation rejects the options.  key is the template instance: ("stream", NPB, TPR, DICT), ("vector", G, DICT),
-    ("rows", NPB, P, DICT), ("wave", TPR, DYN).  Mirrors qbh_api.cpp:566-568 (kernel), 453 (use_wave), spmv.cpp:739-760 (walk)."""
+    ("rows", NPB, P, DICT), ("wave", TPR, DYN).  Mirrors qbh_api.cpp:566-568 (kernel), 453 (use_wave), qbh_spmv.cpp local_part (walk)."""
     dict_mode, nd = coding(kernel_opt, value_dict, val, nd)
     k = KERNEL_VECTOR if kernel_opt == KERNEL_VECTOR else KERNEL_STREAM if kernel_opt == KERNEL_STREAM else KERNEL_ROWS
     g = rows_geometry(k, ia, dict_mode, npb_opt)

@@ -1,4 +1,4 @@
-"""Host-only helpers for the element-wise tests of the complex Kronecker-split SpMV (qbh_split.cpp kron_build, qbh_spmv.cpp
+"""Host-only helpers for the element-wise tests of the complex Kronecker-split SpMV (qbh_split.cpp kron_build, qbh_spmv_kron.cpp
 spmv_kron, k_spmv_wave2 and the kernels of qbh_kron.hip / qbh_kron_prep.hip), in the style of tests/csrforms.py.
 
 Three parts, none of which needs a GPU:
