@@ -1,8 +1,9 @@
 // qbh_api_priv.hpp -- what the translation units behind the extern "C" surface share (round 5: qbh_api.cpp was one 3,900-line file):
 //   qbh_api.cpp     errors, options, operator lifetime (create / adopt / destroy / info / set_basis), geometry of the unsplit
 //                   forms, vectors, download
-//   qbh_split.cpp   the Kronecker split built in place (complex128) and its coded sibling: kron_build, kron_short_cols,
-//                   kron_restore, kronc_build
+//   qbh_split.cpp   the Kronecker split built in place (complex128: kron_build as a sequence of named steps, the derived streams,
+//                   kron_restore) and its coded sibling (kronc_build, kronc_build_sliced, kronc_table_route); the temporaries
+//                   of those builds are DevPtr owners, their device-side checks go through flag_verdict (both below)
 //   qbh_commattach.cpp   qbh_csr_set_comm: the collective agreement on the exchange form, the gather in parts
 //   qbh_spmv.cpp    SpMV dispatch (spmv_run) with the matrix-free and stored-CSR routes, the steps all routes share, reductions,
 //                   the real wire format, BLAS-1 runs, device building blocks, the host-vector seam (qbh_multmv / qbh_multmv2)
@@ -94,6 +95,65 @@ struct Bind {   // make the operator's device current for the duration of a call
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+// Owner of one device allocation of the split builds: freed when it goes out of scope, or now (reset), or handed to the handle
+// (release).  Plain hipMalloc, not qbh::dev_alloc: device_alloc releases live splits before it reports out of memory, and a
+// split's own allocations must not do that (qbh_internal.hpp).  Not DevBufs (qbh_gen_util.hpp) either: that is a pool on
+// dev_alloc that frees nothing before its end, and the builds free early for the sake of peak memory.
+template <typename T>
+class DevPtr {
+    T *p_ = nullptr;
+
+  public:
+    DevPtr() = default;
+    DevPtr(DevPtr &&o) noexcept : p_(o.release()) {}
+    DevPtr(const DevPtr &) = delete;
+    DevPtr &operator=(const DevPtr &) = delete;
+    DevPtr &operator=(DevPtr &&) = delete;
+    ~DevPtr() { reset(); }
+    hipError_t alloc(size_t count)             // count elements; the owner is empty again after a failure
+    {
+        reset();
+        const hipError_t e = hipMalloc(&p_, count * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    T *get() const { return p_; }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    T *release()
+    {
+        T *q = p_;
+        p_ = nullptr;
+        return q;
+    }
+};
+
+// What a checking kernel found: A->d_flag zeroed on the handle's stream, the caller's launch (which gets the flag to raise),
+// the flag read back, one synchronisation, the flag zeroed again -- also after a failure, as long as the stream takes it.  The
+// launch's return code, the HIP error and the flag come back apart: every caller has its own rule for what an error means.
+struct FlagVerdict {
+    int rc = QBH_OK;
+    hipError_t he = hipSuccess;
+    int flag = 0;
+    bool ok() const { return rc == QBH_OK && he == hipSuccess; }
+};
+template <class Launch>
+FlagVerdict flag_verdict(qbh_csr *A, Launch &&launch)
+{
+    FlagVerdict v;
+    hipStream_t s = A->stream;
+    v.he = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+    if (v.ok()) v.rc = launch(A->d_flag);
+    if (v.ok()) v.he = hipMemcpyAsync(&v.flag, A->d_flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (v.ok()) v.he = hipStreamSynchronize(s);
+    const hipError_t z = hipMemsetAsync(A->d_flag, 0, sizeof(int), s);
+    if (v.ok()) v.he = z;
+    return v;
+}
 
 inline double *scal_buf(qbh_csr *A) { return A->has_comm ? A->comm.d_scal : A->d_scal; }
 
