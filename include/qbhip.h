@@ -514,6 +514,29 @@ int qbh_corr_qudit_dev(int n_sites, int d, int total, const qbh_z *d_vec, const 
                        const double *diag /* [n_diag][d] */, const double *string_end /* [d] */, const double *string_mid /* [d] */,
                        const double *lower /* [d] */, double *norm2, double *pop /* [N][d] */, double *dd /* [n_diag][n_diag][N][N] */,
                        double *str /* [N][N] */, qbh_z *aa /* [N][N] */, void *stream);
+/* qbh_corr_kondo_dev: the Kondo lattice (a conduction-electron orbital and a local spin-1/2 on every site), the WHOLE sector
+ * (n_elec, two_sz) in the order of qbh_gen_kondo / qbh_mf_kondo (ascending words u | d << n | s << 2n).  Ranks and rank differences
+ * are 64-bit: the only shape limit is n_sites <= 21 (neither the generator's 2^31 rows nor the 2^40 words of the qbh_mopr_kondo_dev
+ * enumeration apply).  Row shards, communicators and momentum-sector states are out of scope.  s = 0 is up, 1 is down; S is the
+ * local spin, s the electron's; operator order and fermion signs are those of qbh_gen_kondo and of qbh_mopr_kondo_dev ops 0 - 5.
+ *   site[c*N + i]             c = 0 .. 3: <n_{i,up}>, <n_{i,dn}>, <n_{i,up} n_{i,dn}>, <S^z_i> (+1/2 where bit i of s is clear)
+ *   nn[(2a + b)*N*N + i*N + j] = <n_{i,a} n_{j,b}>, the layout of qbh_corr_hubbard_dev
+ *   zn[s*N*N + i*N + j]       = <S^z_i n_{j,s}> for all i, j (i = j included)
+ *   zz[i*N + j]               = <S^z_i S^z_j> of the local spins, symmetric, diagonal norm2 / 4
+ *   hop[s*N*N + i*N + j]      = <c+_{i,s} c_{j,s}>, Hermitian, diagonal = site[s]
+ *   ee[i*N + j]               = <s^+_i s^-_j>, s^+ = c+_up c_dn, Hermitian, diagonal <n_{i,up} (1 - n_{i,dn})>
+ *   ll[i*N + j]               = <S^+_i S^-_j>, Hermitian, diagonal <1/2 + S^z_i>
+ *   le[i*N + j]               = <S^+_i s^-_j> for ALL ordered (i, j), the diagonal (the transverse Kondo term) included; NOT
+ *                               Hermitian, <s^+_j S^-_i> is its conjugate
+ * Of the Hermitian groups only i < j is gathered; the mirror and the diagonals are filled on the host from the site sums.  With
+ * d_vec_re every imaginary part is exactly 0.  norm2 is required, every other output may be NULL.
+ * Checked in this order before the device is looked for: the shape as qbh_gen_kondo (n_sites outside 1 .. 21, n_elec outside
+ * 0 .. 2 n_sites, n_elec + two_sz - n_sites odd -> QBH_EINVAL); an empty sector -> QBH_EUNSUPP; both or neither vector pointer ->
+ * QBH_EINVAL; norm2 NULL -> QBH_EINVAL; each with a message that names the argument.  Nothing is written on a refusal. */
+int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh_z *d_vec, const double *d_vec_re, double *norm2,
+                       double *site /* [4][N] */, double *nn /* [4][N][N] */, double *zn /* [2][N][N] */, double *zz /* [N][N] */,
+                       qbh_z *hop /* [2][N][N] */, qbh_z *ee /* [N][N] */, qbh_z *ll /* [N][N] */, qbh_z *le /* [N][N] */,
+                       void *stream);
 
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.

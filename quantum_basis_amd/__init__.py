@@ -13,4 +13,5 @@ from .engine import (csr_mat, DeviceVec, lanczos, lanczos_real, eigenvec_CG, eig
                      balanced_row_cuts, moprXvec_spin, moprXvec_onebody, moprXvec_terms, moprXvec_sz_repr, moprXvec_flip_repr, moprXvec_diag_hubrepr, moprXvec_c_hubrepr, moprXvec_qudit, moprXvec_qudit_repr, moprXvec_diag_kondo_repr, moprXvec_kondo, moprXvec_kondo_repr, measure_full_dynamic_dev,
                      measure_full_static_spin_dev, measure_repr_static_hubbard, energy_scale)
 from .correlations import (spin_correlations, hubbard_correlations, structure_factor, momentum_distribution,  # noqa: F401
-                           energy_from_correlations, qudit_correlations, spin_s_correlations, bose_correlations)
+                           energy_from_correlations, qudit_correlations, spin_s_correlations, bose_correlations,
+                           kondo_correlations, kondo_energy_from_correlations)

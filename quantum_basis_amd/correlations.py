@@ -1,5 +1,5 @@
 """All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev /
-qbh_corr_qudit_dev), and the host
+qbh_corr_qudit_dev / qbh_corr_kondo_dev), and the host
 arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
 
 The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
@@ -206,6 +206,99 @@ def bose_correlations(n_sites, n_bosons, n_max, d_vec, real=False, normalize=Tru
             if k != "norm2":
                 out[k] = out[k] / out["norm2"]
     return out
+
+
+_KONDO_GROUPS = ("dens", "docc", "sz_local", "nn", "zn", "zz_ll", "hop", "pm_ee", "pm_ll", "pm_le")
+
+
+def _kondo_derived(out):
+    """the derived quantities of kondo_correlations, each where its inputs are present (host arithmetic on the raw groups)"""
+    if "dens" in out:
+        out["sz_elec"] = 0.5 * (out["dens"][0] - out["dens"][1])
+    if "zn" in out:
+        out["zz_le"] = 0.5 * (out["zn"][0] - out["zn"][1])
+    if "nn" in out:
+        nn = out["nn"]
+        out["zz_ee"] = 0.25 * (nn[0] - nn[1] - nn[2] + nn[3])
+    if "zz_ll" in out and "pm_ll" in out:
+        out["ss_ll"] = out["zz_ll"] + out["pm_ll"].real
+    if "zz_ee" in out and "pm_ee" in out:
+        out["ss_ee"] = out["zz_ee"] + out["pm_ee"].real
+    if "zz_le" in out and "pm_le" in out:
+        out["ss_le"] = out["zz_le"] + out["pm_le"].real
+    if "ss_ll" in out and "ss_ee" in out and "ss_le" in out:
+        out["total_spin"] = float(np.sum(out["ss_ll"] + out["ss_ee"] + 2.0 * out["ss_le"]))
+    return out
+
+
+def kondo_correlations(n_sites, n_elec, two_sz, d_vec, real=False, normalize=True, want=_KONDO_GROUPS, stream=None):
+    """Every one- and two-site expectation value of a Kondo-lattice state (basis, operator order and signs of csr_mat.kondo /
+    moprXvec_kondo: words u | d << n | s << 2n ascending), one pass over the state and no second vector: qbh_corr_kondo_dev.
+    d_vec: device address (or DeviceVec) of the WHOLE sector (n_elec, two_sz), complex128, or its packed real parts (real=True).
+    want: the groups to compute (a group left out costs nothing, its passes and gathers are not issued).  S is the local spin, s
+    the electron's.  Raw groups: norm2; dens[2][N] = <n_{i,s}>; docc[N] = <n_up n_dn>; sz_local[N] = <S^z_i>; nn[4][N][N]
+    (uu, ud, du, dd); zn[2][N][N] = <S^z_i n_{j,s}>; zz_ll[N][N] = <S^z_i S^z_j>; hop[2][N][N] = <c+_{i,s} c_{j,s}>; pm_ee =
+    <s^+_i s^-_j>; pm_ll = <S^+_i S^-_j>; pm_le[i][j] = <S^+_i s^-_j> (all ordered pairs, not Hermitian).  Derived, each where its
+    inputs were asked for: sz_elec = (n_up - n_dn) / 2; zz_le[i][j] = <S^z_i s^z_j>; zz_ee = <s^z_i s^z_j>; ss_ll, ss_ee, ss_le =
+    zz + Re pm (<S_i . S_j>, <s_i . s_j>, <S_i . s_j>; ss_le[i][i] is the Kondo singlet); total_spin = <S_tot^2>.  With normalize
+    the arrays are divided by norm2 (norm2 itself is returned as measured)."""
+    N = int(n_sites)
+    want = set(want)
+    unknown = want - set(_KONDO_GROUPS)
+    if unknown:
+        raise ValueError("kondo_correlations: unknown group(s) %s" % sorted(unknown))
+    addr = _addr(d_vec)
+    n2 = C.c_double()
+    site = np.zeros((4, N)) if want & {"dens", "docc", "sz_local"} else None
+    nn = np.zeros((4, N, N)) if "nn" in want else None
+    zn = np.zeros((2, N, N)) if "zn" in want else None
+    zz = np.zeros((N, N)) if "zz_ll" in want else None
+    hop = np.zeros((2, N, N), dtype=np.complex128) if "hop" in want else None
+    ee = np.zeros((N, N), dtype=np.complex128) if "pm_ee" in want else None
+    ll = np.zeros((N, N), dtype=np.complex128) if "pm_ll" in want else None
+    le = np.zeros((N, N), dtype=np.complex128) if "pm_le" in want else None
+    check(lib().qbh_corr_kondo_dev(N, int(n_elec), int(two_sz), None if real else addr, addr if real else None, C.byref(n2), _p(site),
+                                   _p(nn), _p(zn), _p(zz), _p(hop), _p(ee), _p(ll), _p(le), stream), "qbh_corr_kondo_dev")
+    out = {"norm2": n2.value}
+    if "dens" in want:
+        out["dens"] = site[0:2].copy()
+    if "docc" in want:
+        out["docc"] = site[2].copy()
+    if "sz_local" in want:
+        out["sz_local"] = site[3].copy()
+    for k, a in (("nn", nn), ("zn", zn), ("zz_ll", zz), ("hop", hop), ("pm_ee", ee), ("pm_ll", ll), ("pm_le", le)):
+        if a is not None:
+            out[k] = a
+    _kondo_derived(out)
+    if normalize:
+        _nonzero_norm(out["norm2"], "kondo_correlations")
+        for k in out:
+            if k != "norm2":
+                out[k] = out[k] / out["norm2"]
+    return out
+
+
+def kondo_energy_from_correlations(corr, terms, U=0.0):
+    """<psi| H |psi> of the Kondo-lattice operator of a kondo.Terms (and U sum_i n_up n_dn) from the arrays of kondo_correlations,
+    for ANY vector, in the units of `corr` (raw or normalised):  sum_hops (a_up hop[0][i][j] + a_dn hop[1][i][j]) + U sum docc +
+    sum_i (kz_i zz_le[i][i] + kxy_i Re pm_le[i][i]) + sum_sbonds (bz zz_ll[i][j] + bxy Re pm_ll[i][j]).  The imaginary parts cancel
+    for a Hermitian set of hops; the real part is returned."""
+    e = 0.0 + 0.0j
+    for (i, j, a_up, a_dn) in terms.hops:
+        e += a_up * corr["hop"][0][int(i), int(j)] + a_dn * corr["hop"][1][int(i), int(j)]
+    if U != 0.0:
+        e += U * np.sum(corr["docc"])
+    kz, kxy = np.asarray(terms.kz, dtype=np.float64), np.asarray(terms.kxy, dtype=np.float64)
+    if np.any(kz != 0.0):
+        e += np.sum(kz * np.diag(corr["zz_le"]))
+    if np.any(kxy != 0.0):
+        e += np.sum(kxy * np.diag(corr["pm_le"]).real)
+    for (i, j, bz, bxy) in terms.sbonds:
+        if bz != 0.0:
+            e += bz * corr["zz_ll"][int(i), int(j)]
+        if bxy != 0.0:
+            e += bxy * corr["pm_ll"][int(i), int(j)].real
+    return float(np.real(e))
 
 
 # ------------------------------------------------------------------------------------------------------- host helpers --

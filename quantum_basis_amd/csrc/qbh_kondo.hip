@@ -101,19 +101,6 @@ __global__ __launch_bounds__(kKondoFillBlock) void k_kondo_fill(const KondoDev *
 constexpr int kMfKondoBlock = 256;
 constexpr int kMfKondoPerCu = 7;         // workgroups per CU of the resident grid: 66 VGPRs admit 7 waves per SIMD
 
-// rank(to) - rank(from) (mod 2^64) of two patterns with the same popcount that stand above k0 set bits
-__device__ __forceinline__ uint64_t kd_rank_delta(const uint64_t *binom, uint64_t from, uint64_t to, int k0)
-{
-    uint64_t r = 0;
-    for (int k = k0 + 1; to; ++k) {
-        const int p2 = __ffsll((long long)to) - 1, p1 = __ffsll((long long)from) - 1;
-        to &= to - 1;
-        from &= from - 1;
-        r += binom[p2 * kKondoTab + k] - binom[p1 * kKondoTab + k];
-    }
-    return r;
-}
-
 template <bool REALX>
 __global__ __launch_bounds__(kMfKondoBlock) void k_mf_kondo(MfKondo t, MfVec a)
 {

@@ -1,6 +1,7 @@
 // qbh_kondo.hpp -- what the Kondo-lattice generators share: the word packing, the ranking and the terms of one row, used by
 // qbh_kondo.hip (the full sector, qbh_gen_kondo and qbh_mf_kondo) and by the momentum sectors in qbh_sector.hpp / qbh_sector.hip
-// (qbh_gen_kondo_repr) and qbh_sector_mf_kondo.hip (qbh_mf_kondo_repr, which also finds a word's place in the basis from kd_rank).
+// (qbh_gen_kondo_repr) and qbh_sector_mf_kondo.hip (qbh_mf_kondo_repr, which also finds a word's place in the basis from kd_rank),
+// and by the all-pair correlation pass in qbh_corr_kondo.hip (qbh_corr_kondo_dev: kd_unrank, kd_rank, kd_rank_delta).
 //
 // A site carries a conduction-electron orbital and a localized spin-1/2.  A word is three n-bit fields
 //     w = u | d << n | s << 2n      u, d: sites occupied by an up / down electron;  s: sites whose local spin is DOWN
@@ -60,6 +61,19 @@ __device__ __forceinline__ uint64_t kd_rank_k(const uint64_t *binom, uint64_t bi
         const int p = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
         r += binom[p * kKondoTab + k];
+    }
+    return r;
+}
+
+// rank(to) - rank(from) (mod 2^64) of two patterns with the same popcount that stand above k0 set bits
+__device__ __forceinline__ uint64_t kd_rank_delta(const uint64_t *binom, uint64_t from, uint64_t to, int k0)
+{
+    uint64_t r = 0;
+    for (int k = k0 + 1; to; ++k) {
+        const int p2 = __ffsll((long long)to) - 1, p1 = __ffsll((long long)from) - 1;
+        to &= to - 1;
+        from &= from - 1;
+        r += binom[p2 * kKondoTab + k] - binom[p1 * kKondoTab + k];
     }
     return r;
 }

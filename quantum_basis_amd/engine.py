@@ -398,10 +398,14 @@ class csr_mat:
         kondo.Terms(hops, kz, kxy, sbonds) replaces all three lists (anisotropic couplings, complex hops, observables).
         Basis: quantum_basis_amd.kondo.words(n_sites, n_elec, two_sz).  rows=(r0, r1): that row block only.
 
-        An observable needs no entry point of its own: <psi| S_i . s_i |psi> is
+        Observables: kondo_correlations(n, n_elec, two_sz, psi.ptr) measures every one- and two-site expectation value
+        (<S_i . s_j>, <S_i . S_j>, <c+_i c_j>, densities, S_tot^2) in one pass over the state and without a second vector,
+        which is the only route next to a state that fills most of the memory.  A single observable can also be built as an
+        operator, <psi| S_i . s_i |psi> is
             O = csr_mat.kondo(n, n_elec, two_sz, [], terms=kondo.local_singlet_terms(n, i))
             O.spmv(psi.ptr, tmp.ptr); value = O.dotc(psi.ptr, tmp.ptr)
-        with psi, tmp DeviceVec: an operator with no hops, applied through the same SpMV as the Hamiltonian."""
+        with psi, tmp DeviceVec: an operator with no hops, applied through the same SpMV as the Hamiltonian, at the cost of
+        the temporary and of one apply per observable."""
         _lib.require_gpu()
         opts = opts if opts is not None else make_opts()
         keep, hop, rest = cls._kondo_args(n_sites, bonds, t, J_K, J_RKKY, terms)
