@@ -477,7 +477,8 @@ int qbh_mopr_flip_repr_dev(int n_sites, int n_dn_old, int kind, int n_trans, con
  * measure_full_static, src/model.cc:1660-1694, applies the operators of one product one after another into sector-sized
  * temporaries, one pair of sites per call).  Handle-free, like qbh_mopr_spin_dev.  d_vec (complex128) or d_vec_re (the packed real
  * parts of a real state) -- exactly one of them -- is the WHOLE sector on the device in the generators' order; rows are 64-bit
- * throughout, so the dimension may exceed 2^31.  Row shards and communicators are out of scope: a sharded state has to be
+ * throughout, so the dimension may exceed 2^31.  (A spin-1/2 state of a momentum sector, indexed by orbit representatives, has
+ * its own call: qbh_corr_spin_repr_dev, last in this block.)  Row shards and communicators are out of scope: a sharded state has to be
  * gathered on one device first.  The outputs are HOST arrays, filled before the call returns, raw bilinear forms <psi| O |psi>
  * (nothing is divided by *norm2).  Any output pointer may be NULL: that group is not computed and the gathers only it needs are
  * not issued; the other outputs keep their bits.  No atomics: two calls on the same input return the same bits.
@@ -537,6 +538,29 @@ int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh_z *d_vec, 
                        double *site /* [4][N] */, double *nn /* [4][N][N] */, double *zn /* [2][N][N] */, double *zz /* [N][N] */,
                        qbh_z *hop /* [2][N][N] */, qbh_z *ee /* [N][N] */, qbh_z *ll /* [N][N] */, qbh_z *le /* [N][N] */,
                        void *stream);
+/* qbh_corr_spin_repr_dev: a spin-1/2 state held in a MOMENTUM SECTOR, indexed like the rows of qbh_gen_heisenberg_repr for the same
+ * (n_sites, n_dn, n_trans, perms, chars): all orbit representatives, ascending.  The momentum state of representative a is the
+ * normalised sum_g chi(g) T_g |a>, and the call returns what qbh_corr_spin_dev would return on the unfolded full-space state,
+ * computed from the representatives alone in one pass over them (the sector is enumerated inside the call):
+ *   norm2    = sum_a |psi_a|^2 over the representatives of nonzero norm; an entry at a zero-norm representative (the decoupled
+ *              fake rows of the sector operator) is never read
+ *   sz[i]    = sum_a |psi_a|^2 (1/|G|) sum_g s^z_{g(i)}(a)
+ *   zz[i*N+j] = sum_a |psi_a|^2 (1/|G|) sum_g s^z_{g(i)}(a) s^z_{g(j)}(a), symmetric, diagonal norm2 / 4
+ *   pm[i*N+j] = <S^+_i S^-_j> = (1/|G|) sum_a sum_{g: a has g(i) up and g(j) down} conj(psi_a) conj(chi(g*)) sqrt(|S_b|/|S_a|) psi_b,
+ *              c = a ^ bit g(i) ^ bit g(j), b = g* c its representative (skipped when b has zero norm); Hermitian, diagonal
+ *              <1/2 + S^z_i>
+ * zz and pm are constant on the orbits of ordered site pairs under the translations; the kernel accumulates one sum per orbit
+ * (an orbit and its mirror image share one: Hermiticity) and the full N x N arrays are expanded on the host.  One gather per
+ * row and unordered pair of unequal bits.  d_vec_re (packed real parts) is allowed only when every character is real (an
+ * imaginary part up to 1e-13, the rounding of exp(-i k.t) at k = pi, is dropped).  *dim_out = the number of representatives.
+ * Any output may be NULL, as above.  Checked in this order before the device is looked for: perms or chars NULL, n_sites outside
+ * 1 .. 62, n_dn outside 0 .. min(n_sites, 33), n_trans outside 1 .. 64 -> QBH_EINVAL; both or neither vector pointer -> QBH_EINVAL;
+ * translation 0 not the identity, a translation that is not a site permutation -> QBH_EINVAL; d_vec_re with a complex character ->
+ * QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP.  No shape is refused for the size of its tables: the translation tables are
+ * read from global memory when they do not fit LDS.  Row shards, communicators and the other sector families are out of scope. */
+int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars, const qbh_z *d_vec,
+                           const double *d_vec_re, double *norm2, double *sz /* [N] */, double *zz /* [N*N] */, qbh_z *pm /* [N*N] */,
+                           int64_t *dim_out, void *stream);
 
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.

@@ -1,10 +1,11 @@
 """All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev /
-qbh_corr_qudit_dev / qbh_corr_kondo_dev), and the host
+qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev), and the host
 arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
 
 The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
 reference's measure_full_static (src/model.cc:1660-1694) applies one product of operators per call into sector-sized temporaries.
-Momentum-sector states are not covered here: measure_repr_static_hubbard stays the route there.
+Of the momentum-sector states the spin-1/2 family is covered (spin_repr_correlations, from the orbit representatives alone); for
+the Hubbard, d-level and Kondo sector families measure_repr_static_hubbard and its like stay the route.
 """
 import ctypes as C
 
@@ -66,6 +67,40 @@ def spin_correlations(n_sites, n_dn, d_vec, real=False, source=None, normalize=T
     out = {"norm2": norm2, "sz": sz, "zz": zz, "pm": pm, "ss": ss}
     if normalize:
         _nonzero_norm(norm2, "spin_correlations")
+        for k in ("sz", "zz", "pm", "ss"):
+            out[k] = out[k] / norm2
+    return out
+
+
+def spin_repr_correlations(n_sites, n_dn, perms, chars, d_vec, real=False, source=None, normalize=True, stream=None):
+    """spin_correlations for a state of a MOMENTUM SECTOR: d_vec is indexed like the rows of csr_mat.heisenberg_repr for the same
+    (n_sites, n_dn, perms, chars) -- all orbit representatives, ascending -- and the result is what spin_correlations gives on
+    the unfolded full-space state, computed from the representatives in one pass (qbh_corr_spin_repr_dev).  perms [n_trans][N]
+    (translation 0 the identity), chars [n_trans] complex.  real=True: d_vec holds packed real parts; every character must be
+    real.  Entries at representatives whose norm vanishes at this momentum (the decoupled fake rows) are ignored.  source as in
+    spin_correlations.  Returns dict(norm2, sz, zz, pm, ss, dim), dim the number of representatives; structure_factor and
+    energy_from_correlations take it as it is."""
+    N = int(n_sites)
+    p = np.ascontiguousarray(perms, dtype=np.int32).reshape(-1, N)
+    ch = np.ascontiguousarray(np.asarray(chars, dtype=np.complex128).reshape(-1))
+    if ch.shape[0] != p.shape[0]:
+        raise ValueError("spin_repr_correlations: %d characters for %d translations" % (ch.shape[0], p.shape[0]))
+    addr, conv = _generator_order(d_vec, real, source)
+    try:
+        n2, dim = C.c_double(), C.c_int64()
+        sz, zz, pm = np.zeros(N), np.zeros((N, N)), np.zeros((N, N), dtype=np.complex128)
+        check(lib().qbh_corr_spin_repr_dev(N, int(n_dn), int(p.shape[0]), _p(p), _p(ch.view(np.float64)), None if real else addr,
+                                           addr if real else None, C.byref(n2), _p(sz), _p(zz), _p(pm), C.byref(dim), stream),
+              "qbh_corr_spin_repr_dev")
+    finally:
+        if conv is not None:
+            conv.free()
+    norm2 = n2.value
+    ss = zz + pm.real
+    ss[np.diag_indices(N)] = 0.75 * norm2
+    out = {"norm2": norm2, "sz": sz, "zz": zz, "pm": pm, "ss": ss, "dim": int(dim.value)}
+    if normalize:
+        _nonzero_norm(norm2, "spin_repr_correlations")
         for k in ("sz", "zz", "pm", "ss"):
             out[k] = out[k] / norm2
     return out
