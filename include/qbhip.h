@@ -561,6 +561,37 @@ int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh_z *d_vec, 
 int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars, const qbh_z *d_vec,
                            const double *d_vec_re, double *norm2, double *sz /* [N] */, double *zz /* [N*N] */, qbh_z *pm /* [N*N] */,
                            int64_t *dim_out, void *stream);
+/* qbh_corr_hubbard_repr_dev: a two-species fermion state held in a MOMENTUM SECTOR, indexed like the rows of qbh_gen_hubbard_repr
+ * for the same (n_sites, n_up, n_dn, no_double, n_trans, perms, chars): all orbit representatives of the words u | d << n_sites,
+ * ascending.  With T_g |u, d> = sgn(g, u) sgn(g, d) |g(u), g(d)> and |a, k> the normalised sum_g chi(g) T_g |a>, the call returns
+ * what qbh_corr_hubbard_dev would return on the unfolded full-space state (same layouts, raw bilinear forms, nothing divided by
+ * norm2), from the representatives alone, in one pass and without a second vector (the sector is enumerated inside the call):
+ *   norm2 = sum_a |psi_a|^2 over the representatives of nonzero norm (signed character sum over the stabiliser); an entry at a
+ *           zero-norm representative (the decoupled fake rows of the sector operator) is never read
+ *   dens[s*N+i] = sum_a |psi_a|^2 (1/|G|) sum_g n_{g(i),s}(a)
+ *   nn[(2A+B)*N*N + i*N + j] = sum_a |psi_a|^2 (1/|G|) sum_g n_{g(i),A}(a) n_{g(j),B}(a); the diagonal is included (nn[1][i][i] is
+ *           the double occupancy); nn_ud[i][j] = nn_du[j][i]
+ *   hop[s*N*N + i*N + j] = <c+_{i,s} c_{j,s}> = sum_a conj(psi_a) (O_t psi)_a, O_t the translation average of c+_{i,s} c_{j,s}: the
+ *           entries of the rows of qbh_gen_hubbard_repr, (hop sign) sigma(g*) conj(chi(g*)) sqrt(|S_b|/|S_a|) / |G| each; a target
+ *           of zero norm is skipped, and with no_double a target with a doubly occupied site; Hermitian, diagonal = dens
+ *   flip[i*N+j] = <S^+_i S^-_j> = -<(c+_{i,up} c_{j,up})(c+_{j,dn} c_{i,dn})> likewise; Hermitian, diagonal <n_{i,up} (1 - n_{i,dn})>
+ * Every array is constant on the orbits of ordered site pairs under the group; the kernel accumulates one set of sums per orbit
+ * (an orbit and its mirror image share one: Hermiticity; nn_ud keeps the two orientations apart) and the host expands the N x N
+ * arrays.  The group may contain reflections and need not act transitively.  One gather per row, species and unordered pair of
+ * unequally occupied sites (hop), one per pair of an up-only and a down-only site (flip), none for norm2, dens and nn.  A NULL
+ * group issues no gathers and leaves the bits of the other outputs unchanged; two calls return the same bits (no atomics).
+ * d_vec_re (packed real parts) is allowed only when every character is real (an imaginary part up to 1e-13 is dropped).
+ * *dim_out = the number of representatives.  Any output may be NULL.  Checked in this order before the device is looked for, each
+ * with a message that names the argument, nothing written: perms or chars NULL; n_sites outside 1 .. 31; n_up or n_dn outside
+ * 0 .. n_sites; n_trans outside 1 .. 64; no_double not 0 or 1; both or neither vector pointer; translation 0 not the identity; a
+ * translation that is not a site permutation; d_vec_re with a complex character; no_double with more particles than sites -> all
+ * QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP; then QBH_ENODEVICE.  (A sector of 2^31 representatives or more is refused
+ * with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards, communicators and the
+ * d-level and Kondo sector families are out of scope. */
+int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no_double, int n_trans, const int32_t *perms, const double *chars,
+                              const qbh_z *d_vec, const double *d_vec_re, double *norm2, double *dens /* [2][N] */,
+                              double *nn /* [4][N][N] */, qbh_z *hop /* [2][N][N] */, qbh_z *flip /* [N][N] */, int64_t *dim_out,
+                              void *stream);
 
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.

@@ -1,11 +1,12 @@
 """All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev /
-qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev), and the host
+qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev / qbh_corr_hubbard_repr_dev), and the host
 arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
 
 The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
 reference's measure_full_static (src/model.cc:1660-1694) applies one product of operators per call into sector-sized temporaries.
-Of the momentum-sector states the spin-1/2 family is covered (spin_repr_correlations, from the orbit representatives alone); for
-the Hubbard, d-level and Kondo sector families measure_repr_static_hubbard and its like stay the route.
+Of the momentum-sector states the spin-1/2 and the Hubbard / t-J / spinless families are covered (spin_repr_correlations,
+hubbard_repr_correlations: from the orbit representatives alone); for the d-level and Kondo sector families the translation-averaged
+sector operators (the like of measure_repr_static_hubbard) stay the route.
 """
 import ctypes as C
 
@@ -133,6 +134,17 @@ def hubbard_correlations(n_sites, n_up, n_dn, d_vec, real=False, source=None, no
     for k, a in (("dens", dens), ("nn", nn), ("hop", hop), ("flip", flip)):
         if a is not None:
             out[k] = a
+    _hubbard_derived(out, nn, flip, N)
+    if normalize:
+        _nonzero_norm(out["norm2"], "hubbard_correlations")
+        for k in out:
+            if k != "norm2":
+                out[k] = out[k] / out["norm2"]
+    return out
+
+
+def _hubbard_derived(out, nn, flip, N):
+    """docc, szsz, nn_total and ss of hubbard_correlations from the raw groups, each where its inputs are present"""
     if nn is not None:
         out["docc"] = np.diag(nn[1]).copy()
         out["szsz"] = 0.25 * (nn[0] - nn[1] - nn[2] + nn[3])
@@ -141,11 +153,53 @@ def hubbard_correlations(n_sites, n_up, n_dn, d_vec, real=False, source=None, no
             ss = out["szsz"] + flip.real
             ss[np.diag_indices(N)] = 3.0 * np.diag(out["szsz"])        # S_i^2 = 3 (S^z_i)^2 for a spin-1/2 or an empty / doubly occupied site
             out["ss"] = ss
+    return out
+
+
+def hubbard_repr_correlations(n_sites, n_up, n_dn, perms, chars, d_vec, real=False, source=None, normalize=True,
+                              want=("dens", "nn", "hop", "flip"), no_double=False, stream=None):
+    """hubbard_correlations for a state of a MOMENTUM SECTOR: d_vec is indexed like the rows of csr_mat.hubbard_repr (tj_repr with
+    no_double=True) for the same (n_sites, n_up, n_dn, perms, chars) -- all orbit representatives, ascending -- and the result is
+    what hubbard_correlations gives on the unfolded full-space state, computed from the representatives in one pass without a second
+    vector (qbh_corr_hubbard_repr_dev).  perms [n_trans][N] (element 0 the identity; reflections allowed), chars [n_trans] complex.
+    real=True: d_vec holds packed real parts; every character must be real.  Entries at representatives whose norm vanishes at this
+    momentum (the decoupled fake rows) are ignored.  source: the handle the vector belongs to; a device vector of a hubbard_repr_mf
+    handle is kept in the orbit order (info().basis_internal != 0) and is translated first.  want as in hubbard_correlations.
+    Returns the dict of hubbard_correlations (norm2, dens, nn, hop, flip, docc, szsz, nn_total, ss) plus dim, the number of
+    representatives; momentum_distribution, structure_factor and energy_from_correlations take the arrays as they are."""
+    N = int(n_sites)
+    want = set(want)
+    unknown = want - {"dens", "nn", "hop", "flip"}
+    if unknown:
+        raise ValueError("hubbard_repr_correlations: unknown group(s) %s" % sorted(unknown))
+    p = np.ascontiguousarray(perms, dtype=np.int32).reshape(-1, N)
+    ch = np.ascontiguousarray(np.asarray(chars, dtype=np.complex128).reshape(-1))
+    if ch.shape[0] != p.shape[0]:
+        raise ValueError("hubbard_repr_correlations: %d characters for %d translations" % (ch.shape[0], p.shape[0]))
+    addr, conv = _generator_order(d_vec, real, source)
+    try:
+        n2, dim = C.c_double(), C.c_int64()
+        dens = np.zeros((2, N)) if "dens" in want else None
+        nn = np.zeros((4, N, N)) if "nn" in want else None
+        hop = np.zeros((2, N, N), dtype=np.complex128) if "hop" in want else None
+        flip = np.zeros((N, N), dtype=np.complex128) if "flip" in want else None
+        check(lib().qbh_corr_hubbard_repr_dev(N, int(n_up), int(n_dn), int(bool(no_double)), int(p.shape[0]), _p(p), _p(ch.view(np.float64)),
+                                              None if real else addr, addr if real else None, C.byref(n2), _p(dens), _p(nn), _p(hop),
+                                              _p(flip), C.byref(dim), stream), "qbh_corr_hubbard_repr_dev")
+    finally:
+        if conv is not None:
+            conv.free()
+    out = {"norm2": n2.value}
+    for k, a in (("dens", dens), ("nn", nn), ("hop", hop), ("flip", flip)):
+        if a is not None:
+            out[k] = a
+    _hubbard_derived(out, nn, flip, N)
     if normalize:
-        _nonzero_norm(out["norm2"], "hubbard_correlations")
+        _nonzero_norm(out["norm2"], "hubbard_repr_correlations")
         for k in out:
             if k != "norm2":
                 out[k] = out[k] / out["norm2"]
+    out["dim"] = int(dim.value)
     return out
 
 

@@ -39,12 +39,12 @@
 // complex and 104 for the packed-real vector in all three shapes (256 lanes / 1024 lanes with the tables in LDS, 256 lanes with
 // the tables in global memory), four wavefronts per SIMD; the table is in DESIGN 4.5e.
 #include <algorithm>
-#include <numeric>
 #include <vector>
 
 #include "qbh_sector.hpp"
 #include "qbh_device.hpp"
 #include "qbh_corr.hpp"                                      // kCorrLdsCap, corr_uniform, corr_finish
+#include "qbh_corr_repr.hpp"                                 // repr_classes, repr_block_partials
 
 namespace qbh {
 namespace {
@@ -78,26 +78,6 @@ struct CorrRepr {
     const double *xr;
     double *partials;
 };
-
-// acc summed over the workgroup into partials[(blockIdx.x * gridDim.y + blockIdx.y) * NA ..]: every wavefront, then lane c
-// adds the wavefronts of accumulator c in order (corr_block_partials for a workgroup of BLOCK lanes)
-template <int NA, int BLOCK>
-__device__ __forceinline__ void repr_block_partials(double (&acc)[NA], double *red, double *partials)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int c = 0; c < NA; ++c) acc[c] = wave_sum(acc[c]);
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < NA; ++c) red[c * (BLOCK / 64) + wave] = acc[c];
-    }
-    __syncthreads();
-    if (tid < NA) {
-        double s = 0.0;
-        for (int w = 0; w < BLOCK / 64; ++w) s += red[tid * (BLOCK / 64) + w];
-        partials[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * NA + tid] = s;
-    }
-}
 
 template <bool REALX, int BLOCK, bool TABLDS>
 __global__ __launch_bounds__(BLOCK) void k_corr_repr(CorrRepr t)
@@ -207,88 +187,6 @@ __global__ __launch_bounds__(BLOCK) void k_corr_repr(CorrRepr t)
 }
 
 // ------------------------------------------------------------------------------------------------------ host side --
-// the classes of site pairs and the orbits of sites under the translations (see the head of the file)
-struct ReprClasses {
-    int n_cls = 0, n_orb = 0;
-    std::vector<int> cls, fwd;                   // [N * N]: class of (i, j) (-1 on the diagonal) and whether (i, j) is forward
-    std::vector<int> nu, self;                   // [n_cls]: unordered pairs in the class; the class is its own mirror
-    std::vector<std::vector<uint32_t>> pairs;    // [n_cls]: the pair words of the kernel
-    std::vector<int> orb, n_s;                   // [N]: orbit of a site; [n_orb]: its size
-    std::vector<uint64_t> mask;                  // [n_orb]
-};
-
-int uf_find(std::vector<int> &par, int v)
-{
-    while (par[(size_t)v] != v) v = par[(size_t)v] = par[(size_t)par[(size_t)v]];
-    return v;
-}
-
-// every set is named by its smallest member: rep[v]
-std::vector<int> uf_smallest(std::vector<int> &par)
-{
-    const int n = (int)par.size();
-    std::vector<int> low((size_t)n, n), rep((size_t)n);
-    for (int v = 0; v < n; ++v) {
-        const int r = uf_find(par, v);
-        low[(size_t)r] = std::min(low[(size_t)r], v);
-    }
-    for (int v = 0; v < n; ++v) rep[(size_t)v] = low[(size_t)uf_find(par, v)];
-    return rep;
-}
-
-ReprClasses repr_classes(int N, int n_trans, const int32_t *perms)
-{
-    ReprClasses K;
-    std::vector<int> pp((size_t)N * N), ps((size_t)N);
-    std::iota(pp.begin(), pp.end(), 0);
-    std::iota(ps.begin(), ps.end(), 0);
-    for (int g = 1; g < n_trans; ++g) {
-        const int32_t *pg = perms + (size_t)g * N;
-        for (int i = 0; i < N; ++i) {
-            ps[(size_t)uf_find(ps, i)] = uf_find(ps, pg[i]);
-            for (int j = 0; j < N; ++j) pp[(size_t)uf_find(pp, i * N + j)] = uf_find(pp, pg[i] * N + pg[j]);
-        }
-    }
-    const std::vector<int> orep = uf_smallest(pp), srep = uf_smallest(ps);
-    K.cls.assign((size_t)N * N, -1);
-    K.fwd.assign((size_t)N * N, 0);
-    std::vector<int> id((size_t)N * N, -1);                               // class of a key (the smaller of the two orbit names)
-    for (int i = 0; i < N; ++i)
-        for (int j = 0; j < N; ++j) {
-            if (i == j) continue;
-            const int o = orep[(size_t)i * N + j], om = orep[(size_t)j * N + i], key = std::min(o, om);
-            if (id[(size_t)key] < 0) {
-                id[(size_t)key] = K.n_cls++;
-                K.nu.push_back(0);
-                K.self.push_back(o == om ? 1 : 0);
-                K.pairs.emplace_back();
-            }
-            K.cls[(size_t)i * N + j] = id[(size_t)key];
-            K.fwd[(size_t)i * N + j] = o == key ? 1 : 0;
-        }
-    for (int p = 0; p < N; ++p)
-        for (int q = p + 1; q < N; ++q) {
-            const int c = K.cls[(size_t)p * N + q];
-            ++K.nu[(size_t)c];
-            K.pairs[(size_t)c].push_back((uint32_t)p | ((uint32_t)q << 8) | ((uint32_t)K.fwd[(size_t)p * N + q] << 16) |
-                                         ((uint32_t)K.fwd[(size_t)q * N + p] << 17));
-        }
-    K.orb.assign((size_t)N, -1);
-    std::vector<int> sid((size_t)N, -1);
-    for (int i = 0; i < N; ++i) {
-        const int r = srep[(size_t)i];
-        if (sid[(size_t)r] < 0) {
-            sid[(size_t)r] = K.n_orb++;
-            K.n_s.push_back(0);
-            K.mask.push_back(0ULL);
-        }
-        K.orb[(size_t)i] = sid[(size_t)r];
-        ++K.n_s[(size_t)sid[(size_t)r]];
-        K.mask[(size_t)sid[(size_t)r]] |= 1ULL << i;
-    }
-    return K;
-}
-
 // dynamic LDS of a launch: binomials and characters, and the translation tables when all of it fits the budget
 size_t repr_lds_small(int n_sites, int n_trans) { return ((size_t)(n_sites + 1) * kBinomRow + 2 * (size_t)n_trans) * 8; }
 bool repr_tab_lds(int n_sites, int n_trans, size_t n_tab) { return repr_lds_small(n_sites, n_trans) + n_tab * 8 <= kCorrLdsCap; }

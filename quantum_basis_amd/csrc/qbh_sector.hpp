@@ -341,10 +341,10 @@ __device__ __forceinline__ uint64_t sector_translate(const HubReprDev &R, const 
     return u | (d << R.n_sites);
 }
 
-// parity (0 / 1) of the permutation that sorts the images of the occupied sites of `occ` under translation g
-__device__ __forceinline__ int hubrepr_parity(const HubReprDev &R, int g, uint64_t occ)
+// parity (0 / 1) of the permutation that sorts the images of the occupied sites of `occ` under the translation whose images are
+// p[site] (a row of HubReprDev::perm, wherever it is kept)
+__device__ __forceinline__ int hubrepr_parity(const int8_t *p, uint64_t occ)
 {
-    const int8_t *p = R.perm + g * R.n_sites;
     uint64_t seen = 0;
     int par = 0;
     while (occ) {
@@ -355,6 +355,10 @@ __device__ __forceinline__ int hubrepr_parity(const HubReprDev &R, int g, uint64
         seen |= 1ULL << img;
     }
     return par;
+}
+__device__ __forceinline__ int hubrepr_parity(const HubReprDev &R, int g, uint64_t occ)
+{
+    return hubrepr_parity(R.perm + g * R.n_sites, occ);
 }
 __device__ __forceinline__ int sector_parity(const HubReprDev &R, int g, uint64_t s)
 {
