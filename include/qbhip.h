@@ -557,7 +557,8 @@ int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh_z *d_vec, 
  * 1 .. 62, n_dn outside 0 .. min(n_sites, 33), n_trans outside 1 .. 64 -> QBH_EINVAL; both or neither vector pointer -> QBH_EINVAL;
  * translation 0 not the identity, a translation that is not a site permutation -> QBH_EINVAL; d_vec_re with a complex character ->
  * QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP.  No shape is refused for the size of its tables: the translation tables are
- * read from global memory when they do not fit LDS.  Row shards, communicators and the other sector families are out of scope. */
+ * read from global memory when they do not fit LDS.  Row shards, communicators and the Kondo sector family are out of scope
+ * (Hubbard and d-level sectors: the two calls below). */
 int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars, const qbh_z *d_vec,
                            const double *d_vec_re, double *norm2, double *sz /* [N] */, double *zz /* [N*N] */, qbh_z *pm /* [N*N] */,
                            int64_t *dim_out, void *stream);
@@ -587,11 +588,46 @@ int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *pe
  * translation that is not a site permutation; d_vec_re with a complex character; no_double with more particles than sites -> all
  * QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP; then QBH_ENODEVICE.  (A sector of 2^31 representatives or more is refused
  * with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards, communicators and the
- * d-level and Kondo sector families are out of scope. */
+ * Kondo sector family are out of scope (d-level sectors: qbh_corr_qudit_repr_dev below). */
 int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no_double, int n_trans, const int32_t *perms, const double *chars,
                               const qbh_z *d_vec, const double *d_vec_re, double *norm2, double *dens /* [2][N] */,
                               double *nn /* [4][N][N] */, qbh_z *hop /* [2][N][N] */, qbh_z *flip /* [N][N] */, int64_t *dim_out,
                               void *stream);
+/* qbh_corr_qudit_repr_dev: a state of d-level sites held in a MOMENTUM SECTOR, indexed like the rows of qbh_gen_qudit_repr /
+ * qbh_mf_qudit_repr for the same (n_sites, d, total, n_trans, perms, chars): all orbit representatives, ascending, zero-norm
+ * representatives present as rows.  Conventions of qbh_gen_qudit_repr (the action of perms, the character, sqrt(|S_b|/|S_a|), the
+ * info byte, zero-norm targets dropped).  The call returns what qbh_corr_qudit_dev would return on the unfolded full-space state
+ * (same layouts and table meanings, raw bilinear forms, nothing divided by norm2), from the representatives alone, in one pass per
+ * launch and without a second vector (the sector is enumerated inside the call).  With w_a = |psi_a|^2 over the representatives
+ * of nonzero norm (an entry at a zero-norm representative is never read):
+ *   norm2 = sum_a w_a;   pop[s*d + l] = sum_a w_a (1/n_s) #{p in the orbit of site s: l_p = l}
+ *   dd[(a*K + b)*N*N + i*N + j] = sum_a w_a (1/|O|) sum_{(p,q) in O(i,j)} f_a(l_p) f_b(l_q), O(i,j) the orbit of the ordered pair;
+ *           the diagonal is <f_a f_b> of the site, from the site-orbit sums
+ *   str[i*N + j], i < j (mirrored; diagonal sum w h(l_i)^2) = the translation average of the index-ordered string of
+ *           qbh_corr_qudit_dev: sum_a w_a (1/|orbit(m)|) sum_{m' in orbit(m)} h(l_e1') h(l_e2') prod_{k in M'} g(l_k) with the decorated
+ *           string m = ({i, j}, {k: i < k < j}) (two end sites and the SET of middle sites) on which the group acts site by site,
+ *           evaluated on the representative word; any group (reflections, cells of several sites, tori: images of an interval need
+ *           not be intervals).  On a ring with all rotations the classes are the N - 1 string lengths, wrapped strings included.
+ *   aa[i*N + j] = <A_i A+_j> = (1/|O|) sum_a sum_{(p,q) in O(i,j): l_p >= 1, l_q <= d-2} lower[l_p] lower[l_q + 1] sqrt(|S_b|/|S_a|)
+ *           chi(g*) conj(psi_b) psi_a, c = a with l_p - 1 and l_q + 1, b = g* c (skipped when b has zero norm); Hermitian, diagonal
+ *           sum w lower[l_i + 1]^2.  A class of site pairs that is its own mirror image sums both orientations and is real.
+ * One gather per row and allowed orientation of the forward orbit of a class (one per unordered pair at most unless the class is
+ * its own mirror), none for norm2, pop, dd and str.  d_vec_re (packed real parts) only with real characters (an imaginary part up
+ * to 1e-13 is dropped); all imaginary parts are then exactly 0.  *dim_out = the number of representatives.  Any output may be
+ * NULL; a NULL group issues none of its gathers and changes no bit of the others; two calls return the same bits (no atomics).
+ * Checked in this order before the device is looked for, each with a message that names the argument, nothing written: perms or
+ * chars NULL -> QBH_EINVAL; the shape as qbh_gen_qudit_repr checks it (n_sites < 1 or d < 2 -> QBH_EINVAL, d > 8 or n_sites * bits
+ * > 64 -> QBH_EUNSUPP, total outside 0 .. n_sites (d - 1) -> QBH_EINVAL); n_trans outside 1 .. 64; both or neither vector pointer;
+ * the table checks of qbh_corr_qudit_dev in its order (n_diag, diag NULL with n_diag > 0, one string table only, dd / str / aa
+ * wanted without tables, non-finite table values); translation 0 not the identity or a non-permutation; d_vec_re with a complex
+ * character -> all QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP; then QBH_ENODEVICE.  (A sector of 2^31 representatives or more
+ * is refused with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards, communicators
+ * and the Kondo sector family are out of scope. */
+int qbh_corr_qudit_repr_dev(int n_sites, int d, int total, int n_trans, const int32_t *perms, const double *chars,
+                            const qbh_z *d_vec, const double *d_vec_re, int n_diag, const double *diag /* [n_diag][d] */,
+                            const double *string_end /* [d] */, const double *string_mid /* [d] */, const double *lower /* [d] */,
+                            double *norm2, double *pop /* [N][d] */, double *dd /* [n_diag][n_diag][N][N] */,
+                            double *str /* [N][N] */, qbh_z *aa /* [N][N] */, int64_t *dim_out, void *stream);
 
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.

@@ -1,12 +1,13 @@
 """All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev /
-qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev / qbh_corr_hubbard_repr_dev), and the host
+qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev / qbh_corr_hubbard_repr_dev / qbh_corr_qudit_repr_dev), and the host
 arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
 
 The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
 reference's measure_full_static (src/model.cc:1660-1694) applies one product of operators per call into sector-sized temporaries.
-Of the momentum-sector states the spin-1/2 and the Hubbard / t-J / spinless families are covered (spin_repr_correlations,
-hubbard_repr_correlations: from the orbit representatives alone); for the d-level and Kondo sector families the translation-averaged
-sector operators (the like of measure_repr_static_hubbard) stay the route.
+Of the momentum-sector states the spin-1/2, the Hubbard / t-J / spinless and the d-level families are covered
+(spin_repr_correlations, hubbard_repr_correlations, qudit_repr_correlations with spin_s_repr_correlations and bose_repr_correlations:
+from the orbit representatives alone); for the Kondo sector family the translation-averaged sector operators (the like of
+measure_repr_static_hubbard) stay the route.
 """
 import ctypes as C
 
@@ -256,11 +257,7 @@ def spin_s_correlations(n_sites, S, two_sz, d_vec, real=False, normalize=True):
     half-integer S (its phases are complex).  With the keys zz and pm, energy_from_correlations gives <H> of the spin-S Heisenberg
     operator."""
     from . import qudit as qd
-    two_s = qd._two_s(S)
-    d, Sv = two_s + 1, two_s / 2.0
-    m = Sv - np.arange(d)
-    lower = np.real(np.append(0.0, np.diag(qd.spin_matrices(S)[1], 1)))            # <l-1| S^+ |l>
-    string = (m, np.where(np.arange(d) % 2 == (two_s // 2) % 2, 1.0, -1.0)) if two_s % 2 == 0 else None      # (-1)^m, m = S - l
+    d, m, string, lower = _spin_s_tables(S)
     raw = qudit_correlations(n_sites, d, qd.spin_charge(n_sites, S, two_sz), d_vec, diag=(m,), string=string, lower=lower, real=real,
                              normalize=False)
     out = _spin_s_from_raw(S, raw)
@@ -295,6 +292,93 @@ def bose_correlations(n_sites, n_bosons, n_max, d_vec, real=False, normalize=Tru
             if k != "norm2":
                 out[k] = out[k] / out["norm2"]
     return out
+
+
+def qudit_repr_correlations(n_sites, d, total, perms, chars, d_vec, diag=(), string=None, lower=None, real=False, normalize=True,
+                            stream=None):
+    """qudit_correlations for a state of a MOMENTUM SECTOR: d_vec is indexed like the rows of csr_mat.qudit_repr (stored or
+    matrix_free) for the same (n_sites, d, total, perms, chars) -- all orbit representatives, ascending -- and the result is what qudit_correlations
+    gives on the unfolded full-space state, computed from the representatives in one pass without a second vector
+    (qbh_corr_qudit_repr_dev).  perms [n_trans][N] (element 0 the identity; reflections allowed), chars [n_trans] complex.
+    real=True: d_vec holds packed real parts; every character must be real.  Entries at representatives whose norm vanishes at
+    this momentum are ignored.  The string correlator str[i][j] is the average over the group of the index-ordered string of
+    qudit_correlations (on a ring: of all strings of that length, wrapped ones included).  Returns dict(norm2, pop) and, for the
+    tables that were given, dd, str, aa, plus dim, the number of representatives."""
+    N, d = int(n_sites), int(d)
+    p = np.ascontiguousarray(perms, dtype=np.int32).reshape(-1, N)
+    ch = np.ascontiguousarray(np.asarray(chars, dtype=np.complex128).reshape(-1))
+    if ch.shape[0] != p.shape[0]:
+        raise ValueError("qudit_repr_correlations: %d characters for %d translations" % (ch.shape[0], p.shape[0]))
+    f = np.ascontiguousarray(np.asarray(diag, dtype=np.float64).reshape(-1, d)) if len(diag) else None
+    K = 0 if f is None else f.shape[0]
+    h = g = None
+    if string is not None:
+        h, g = (np.ascontiguousarray(t, dtype=np.float64).reshape(d) for t in string)
+    low = np.ascontiguousarray(lower, dtype=np.float64).reshape(d) if lower is not None else None
+    addr = _addr(d_vec)
+    n2, dim = C.c_double(), C.c_int64()
+    pop = np.zeros((N, d))
+    dd = np.zeros((K, K, N, N)) if K else None
+    st = np.zeros((N, N)) if string is not None else None
+    aa = np.zeros((N, N), dtype=np.complex128) if low is not None else None
+    check(lib().qbh_corr_qudit_repr_dev(N, d, int(total), int(p.shape[0]), _p(p), _p(ch.view(np.float64)), None if real else addr,
+                                        addr if real else None, K, _p(f), _p(h), _p(g), _p(low), C.byref(n2), _p(pop), _p(dd), _p(st),
+                                        _p(aa), C.byref(dim), stream), "qbh_corr_qudit_repr_dev")
+    out = {"norm2": n2.value, "pop": pop}
+    for k, a in (("dd", dd), ("str", st), ("aa", aa)):
+        if a is not None:
+            out[k] = a
+    if normalize:
+        _nonzero_norm(out["norm2"], "qudit_repr_correlations")
+        for k in out:
+            if k != "norm2":
+                out[k] = out[k] / out["norm2"]
+    out["dim"] = int(dim.value)
+    return out
+
+
+def _spin_s_tables(S):
+    """(d, diag, string, lower) of spin_s_correlations: m = S - l, the den Nijs-Rommelse string for integer S, <l-1| S^+ |l>"""
+    from . import qudit as qd
+    two_s = qd._two_s(S)
+    d, Sv = two_s + 1, two_s / 2.0
+    m = Sv - np.arange(d)
+    lower = np.real(np.append(0.0, np.diag(qd.spin_matrices(S)[1], 1)))            # <l-1| S^+ |l>
+    string = (m, np.where(np.arange(d) % 2 == (two_s // 2) % 2, 1.0, -1.0)) if two_s % 2 == 0 else None      # (-1)^m, m = S - l
+    return d, m, string, lower
+
+
+def _normalized(out, who):
+    _nonzero_norm(out["norm2"], who)
+    for k in out:
+        if k not in ("norm2", "dim") and out[k] is not None:
+            out[k] = out[k] / out["norm2"]
+    return out
+
+
+def spin_s_repr_correlations(n_sites, S, two_sz, perms, chars, d_vec, real=False, normalize=True):
+    """spin_s_correlations for a state of a MOMENTUM SECTOR of csr_mat.spin_heisenberg's d-level form (rows of qudit_repr for the
+    charge of 2 S^z = two_sz): the same dict plus dim, from the representatives alone (qudit_repr_correlations); string is the
+    den Nijs-Rommelse correlator averaged over the group."""
+    from . import qudit as qd
+    d, m, string, lower = _spin_s_tables(S)
+    raw = qudit_repr_correlations(n_sites, d, qd.spin_charge(n_sites, S, two_sz), perms, chars, d_vec, diag=(m,), string=string,
+                                  lower=lower, real=real, normalize=False)
+    out = _spin_s_from_raw(S, raw)
+    out["dim"] = raw["dim"]
+    return _normalized(out, "spin_s_repr_correlations") if normalize else out
+
+
+def bose_repr_correlations(n_sites, n_bosons, n_max, perms, chars, d_vec, real=False, normalize=True):
+    """bose_correlations for a state of a MOMENTUM SECTOR (rows of csr_mat.bose_hubbard_repr for the same n_sites, n_bosons, n_max, perms, chars): the same
+    dict plus dim, from the representatives alone (qudit_repr_correlations)."""
+    n = np.arange(n_max + 1, dtype=np.float64)
+    raw = qudit_repr_correlations(n_sites, n_max + 1, n_bosons, perms, chars, d_vec, diag=(n,),
+                                  string=(np.ones(n_max + 1), 1.0 - 2.0 * (np.arange(n_max + 1) % 2)), lower=np.sqrt(n), real=real,
+                                  normalize=False)
+    out = _bose_from_raw(n_max, raw)
+    out["dim"] = raw["dim"]
+    return _normalized(out, "bose_repr_correlations") if normalize else out
 
 
 _KONDO_GROUPS = ("dens", "docc", "sz_local", "nn", "zn", "zz_ll", "hop", "pm_ee", "pm_ll", "pm_le")

@@ -72,10 +72,7 @@ namespace {
 constexpr int kHrAcc = 16;                                   // accumulators of a pass
 constexpr int kHrNN = kHrAcc / 4, kHrGat = kHrAcc / 2, kHrSite = (kHrAcc - 1) / 3;      // classes / classes / site orbits of a pass
 enum { kHrKindNN = 0, kHrKindHopU = 1, kHrKindHopD = 2, kHrKindFlip = 3, kHrKindSite = 4 };
-constexpr int kHrBlockS = 256, kHrBlockL = 1024;
-constexpr int kHrPerCuS = 4;                                 // workgroups of 256 lanes per CU at most
-constexpr size_t kHrLdsCu = (size_t)160 * 1024;
-constexpr size_t kHrLdsStatic = 4096;                        // the reduction scratch of a workgroup and allocation granules
+constexpr int kHrBlockS = kReprBlockS, kHrBlockL = kReprBlockL;
 constexpr int kHrBinomRow = 34;                              // HubReprDev::binom[p][0 .. 33]
 
 // The pair words of class c are pairs[cls_start[c] .. cls_start[c + 1]) (qbh_corr_repr.hpp); cls_start is padded with the total
@@ -300,14 +297,9 @@ int corr_hubrepr_run(const char *who, CorrHubRepr t, const ReprClasses &K, size_
     const int per_kind[5] = {want_nn ? n_nn : 0, want_hop ? n_gat : 0, want_hop ? n_gat : 0, want_flip ? n_gat : 0, n_site};
     int n_pass = 0;
     for (int k = 0; k < 5; ++k) t.pass_end[k] = n_pass += per_kind[k];
-    std::vector<int32_t> cls_start((size_t)K.n_cls + NA + 1, 0);
+    std::vector<int32_t> cls_start;
     std::vector<uint32_t> pairs;
-    for (int c = 0; c < K.n_cls; ++c) {
-        cls_start[(size_t)c] = (int32_t)pairs.size();
-        pairs.insert(pairs.end(), K.pairs[(size_t)c].begin(), K.pairs[(size_t)c].end());
-    }
-    for (size_t c = (size_t)K.n_cls; c < cls_start.size(); ++c) cls_start[c] = (int32_t)pairs.size();
-    if (pairs.empty()) pairs.push_back(0u);                               // one site: no pairs, and nothing reads this word
+    repr_flatten_classes(K, NA, cls_start, pairs);
     std::vector<uint64_t> site_mask((size_t)n_site * kHrSite, 0ULL);
     std::copy(K.mask.begin(), K.mask.end(), site_mask.begin());
     int32_t *d_start = nullptr;
@@ -321,11 +313,9 @@ int corr_hubrepr_run(const char *who, CorrHubRepr t, const ReprClasses &K, size_
     t.site_mask = d_mask;
     const bool tab_lds = hr_tab_lds(t.n_sites, t.n_trans, n_tab);
     const size_t lds = hr_lds_small(t.n_sites, t.n_trans) + (tab_lds ? n_tab * 8 : 0);
-    const int fit = (int)(kHrLdsCu / (lds + kHrLdsStatic));
-    const bool large = fit < 4;                                           // then one workgroup of 1024 lanes per CU
-    const int block = large ? kHrBlockL : kHrBlockS, per_cu = large ? 1 : std::min(kHrPerCuS, fit);
-    const int64_t nblk = (t.dim + block - 1) / block;
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, (int64_t)device_cu_count() * per_cu));
+    const ReprShape shape = repr_launch_shape(lds, t.dim);
+    const bool large = shape.large;                                       // then one workgroup of 1024 lanes per CU
+    const int gx = shape.gx;
     const int ncomp = n_pass * NA;
     QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * ncomp * sizeof(double)));
     pool.push_back(t.partials);
@@ -381,17 +371,7 @@ extern "C" int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no
     std::vector<uint64_t> tab;
     QBH_TRY(hubrepr_symmetry(R, tab, n_sites, n_up, n_dn, n_trans, perms, chars, who));
     R.no_double = no_double;
-    if (d_vec_re != nullptr) {
-        // a character computed as exp(-i k.t) at k = pi carries sin(pi t): an imaginary part below 1e-13 is that rounding
-        // (qbh_corr_spin_repr_dev) and is dropped, anything larger is a complex character
-        for (int g = 0; g < n_trans; ++g) {
-            if (std::fabs(R.chr[2 * g + 1]) > 1e-13) {
-                set_error("%s: d_vec_re needs real characters, and the character of translation %d is complex", who, g);
-                return QBH_EINVAL;
-            }
-            R.chr[2 * g + 1] = 0.0;
-        }
-    }
+    if (d_vec_re != nullptr) QBH_TRY(repr_real_characters(who, R.chr, n_trans));
     if (no_double && n_up + n_dn > n_sites) {
         set_error("%s: no_double with n_up + n_dn = %d particles on %d sites: the space is empty", who, n_up + n_dn, n_sites);
         return QBH_EINVAL;

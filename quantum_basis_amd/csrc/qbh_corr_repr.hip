@@ -50,11 +50,7 @@ namespace qbh {
 namespace {
 
 constexpr int kReprGroup = 8;                                // classes of a pair pass
-constexpr int kReprBlockS = 256, kReprBlockL = 1024;
-constexpr int kReprPerCuS = 4;                               // workgroups of 256 lanes per CU at most
-constexpr size_t kReprLdsCu = (size_t)160 * 1024;
-constexpr size_t kReprLdsStatic = 4096;                      // the reduction scratch of a workgroup and allocation granules
-constexpr int kBinomRow = 34;                                // HeisDev::binom[p][0 .. 33]
+constexpr int kBinomRow = 34;                               // HeisDev::binom[p][0 .. 33]
 
 template <bool REALX>
 constexpr int repr_acc() { return (REALX ? 2 : 3) * kReprGroup; }
@@ -233,11 +229,9 @@ int corr_repr_run(const char *who, CorrRepr t, const ReprClasses &K, size_t n_ta
     t.site_mask = d_mask;
     const bool tab_lds = repr_tab_lds(t.n_sites, t.n_trans, n_tab);
     const size_t lds = repr_lds_small(t.n_sites, t.n_trans) + (tab_lds ? n_tab * 8 : 0);
-    const int fit = (int)(kReprLdsCu / (lds + kReprLdsStatic));
-    const bool large = fit < 4;                                           // then one workgroup of 1024 lanes per CU
-    const int block = large ? kReprBlockL : kReprBlockS, per_cu = large ? 1 : std::min(kReprPerCuS, fit);
-    const int64_t nblk = (t.dim + block - 1) / block;
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, (int64_t)device_cu_count() * per_cu));
+    const ReprShape shape = repr_launch_shape(lds, t.dim);
+    const bool large = shape.large;                                       // then one workgroup of 1024 lanes per CU
+    const int gx = shape.gx;
     const int n_pass = n_pair_pass + n_site_pass, ncomp = n_pass * NA;
     QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * ncomp * sizeof(double)));
     pool.push_back(t.partials);
@@ -272,17 +266,7 @@ extern "C" int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const 
     ReprDev &R = rr[0];
     std::vector<uint64_t> tab;
     QBH_TRY(repr_symmetry(R, tab, n_sites, n_dn, n_trans, perms, chars, who));
-    if (d_vec_re != nullptr) {
-        // a character computed as exp(-i k.t) at k = pi carries sin(pi t): an imaginary part below 1e-13 is that rounding
-        // (qbh_mf_kondo_repr) and is dropped, anything larger is a complex character
-        for (int g = 0; g < n_trans; ++g) {
-            if (std::fabs(R.chr[2 * g + 1]) > 1e-13) {
-                set_error("%s: d_vec_re needs real characters, and the character of translation %d is complex", who, g);
-                return QBH_EINVAL;
-            }
-            R.chr[2 * g + 1] = 0.0;
-        }
-    }
+    if (d_vec_re != nullptr) QBH_TRY(repr_real_characters(who, R.chr, n_trans));
     int64_t nstates = 0;
     std::vector<uint64_t> ctab;
     QBH_TRY(sector_words(R, ctab, &nstates, who));           // every refusal comes before the device is looked for

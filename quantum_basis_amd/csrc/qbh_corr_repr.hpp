@@ -1,8 +1,10 @@
 // qbh_corr_repr.hpp -- what the momentum-sector correlation calls share (qbh_corr_repr.hip: spin-1/2; qbh_corr_hubrepr.hip:
-// two-species fermions): the classes of site pairs and the orbits of sites under the group (host), and the block reduction of a
-// workgroup of any size into partials[blockIdx.x][pass][accumulator].  Internal linkage, like qbh_sector.hpp.
+// two-species fermions; qbh_corr_quditrepr.hip: d-level sites): the classes of site pairs and the orbits of sites under the group
+// (host), the block reduction of a workgroup of any size into partials[blockIdx.x][pass][accumulator], the shape of a launch from
+// its LDS footprint and the check of the characters of a packed-real vector.  Internal linkage, like qbh_sector.hpp.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <numeric>
 #include <vector>
 
@@ -113,6 +115,58 @@ inline ReprClasses repr_classes(int N, int n_trans, const int32_t *perms)
         K.mask[(size_t)sid[(size_t)r]] |= 1ULL << i;
     }
     return K;
+}
+
+// the pair words of all classes in class order: those of class c are pairs[cls_start[c] .. cls_start[c + 1]); cls_start is padded
+// with the total for `pad` entries beyond the last class, so a pass reads the bounds of its whole group without a check
+inline void repr_flatten_classes(const ReprClasses &K, int pad, std::vector<int32_t> &cls_start, std::vector<uint32_t> &pairs)
+{
+    cls_start.assign((size_t)K.n_cls + pad + 1, 0);
+    pairs.clear();
+    for (int c = 0; c < K.n_cls; ++c) {
+        cls_start[(size_t)c] = (int32_t)pairs.size();
+        pairs.insert(pairs.end(), K.pairs[(size_t)c].begin(), K.pairs[(size_t)c].end());
+    }
+    for (size_t c = (size_t)K.n_cls; c < cls_start.size(); ++c) cls_start[c] = (int32_t)pairs.size();
+    if (pairs.empty()) pairs.push_back(0u);                               // one site: no pairs, and nothing reads this word
+}
+
+// The shape of a launch from the dynamic LDS of a workgroup: workgroups of 256 lanes while four or more fit a CU (at most four
+// are used), one of 1024 lanes otherwise; gx = the resident grid along x, at most one workgroup per piece of `block` rows.
+constexpr int kReprBlockS = 256, kReprBlockL = 1024;
+constexpr int kReprPerCuS = 4;                               // workgroups of 256 lanes per CU at most
+constexpr size_t kReprLdsCu = (size_t)160 * 1024;
+constexpr size_t kReprLdsStatic = 4096;                      // the reduction scratch of a workgroup and allocation granules
+
+struct ReprShape {
+    bool large;
+    int block, gx;
+};
+
+inline ReprShape repr_launch_shape(size_t lds, int64_t dim)
+{
+    const int fit = (int)(kReprLdsCu / (lds + kReprLdsStatic));
+    ReprShape s;
+    s.large = fit < 4;
+    s.block = s.large ? kReprBlockL : kReprBlockS;
+    const int per_cu = s.large ? 1 : std::min(kReprPerCuS, fit);
+    const int64_t nblk = (dim + s.block - 1) / s.block;
+    s.gx = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, (int64_t)device_cu_count() * per_cu));
+    return s;
+}
+
+// A packed-real vector needs real characters.  A character computed as exp(-i k.t) at k = pi carries sin(pi t): an imaginary
+// part below 1e-13 is that rounding (qbh_mf_kondo_repr) and is dropped, anything larger is a complex character.
+inline int repr_real_characters(const char *who, double *chr, int n_trans)
+{
+    for (int g = 0; g < n_trans; ++g) {
+        if (std::fabs(chr[2 * g + 1]) > 1e-13) {
+            set_error("%s: d_vec_re needs real characters, and the character of translation %d is complex", who, g);
+            return QBH_EINVAL;
+        }
+        chr[2 * g + 1] = 0.0;
+    }
+    return QBH_OK;
 }
 
 }  // namespace
