@@ -518,7 +518,8 @@ int qbh_corr_qudit_dev(int n_sites, int d, int total, const qbh_z *d_vec, const 
 /* qbh_corr_kondo_dev: the Kondo lattice (a conduction-electron orbital and a local spin-1/2 on every site), the WHOLE sector
  * (n_elec, two_sz) in the order of qbh_gen_kondo / qbh_mf_kondo (ascending words u | d << n | s << 2n).  Ranks and rank differences
  * are 64-bit: the only shape limit is n_sites <= 21 (neither the generator's 2^31 rows nor the 2^40 words of the qbh_mopr_kondo_dev
- * enumeration apply).  Row shards, communicators and momentum-sector states are out of scope.  s = 0 is up, 1 is down; S is the
+ * enumeration apply).  Row shards and communicators are out of scope (momentum-sector states: qbh_corr_kondo_repr_dev, last in
+ * this block).  s = 0 is up, 1 is down; S is the
  * local spin, s the electron's; operator order and fermion signs are those of qbh_gen_kondo and of qbh_mopr_kondo_dev ops 0 - 5.
  *   site[c*N + i]             c = 0 .. 3: <n_{i,up}>, <n_{i,dn}>, <n_{i,up} n_{i,dn}>, <S^z_i> (+1/2 where bit i of s is clear)
  *   nn[(2a + b)*N*N + i*N + j] = <n_{i,a} n_{j,b}>, the layout of qbh_corr_hubbard_dev
@@ -557,8 +558,8 @@ int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh_z *d_vec, 
  * 1 .. 62, n_dn outside 0 .. min(n_sites, 33), n_trans outside 1 .. 64 -> QBH_EINVAL; both or neither vector pointer -> QBH_EINVAL;
  * translation 0 not the identity, a translation that is not a site permutation -> QBH_EINVAL; d_vec_re with a complex character ->
  * QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP.  No shape is refused for the size of its tables: the translation tables are
- * read from global memory when they do not fit LDS.  Row shards, communicators and the Kondo sector family are out of scope
- * (Hubbard and d-level sectors: the two calls below). */
+ * read from global memory when they do not fit LDS.  Row shards and communicators are out of scope (Hubbard, d-level and Kondo
+ * sectors: the three calls below). */
 int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *perms, const double *chars, const qbh_z *d_vec,
                            const double *d_vec_re, double *norm2, double *sz /* [N] */, double *zz /* [N*N] */, qbh_z *pm /* [N*N] */,
                            int64_t *dim_out, void *stream);
@@ -587,8 +588,8 @@ int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const int32_t *pe
  * 0 .. n_sites; n_trans outside 1 .. 64; no_double not 0 or 1; both or neither vector pointer; translation 0 not the identity; a
  * translation that is not a site permutation; d_vec_re with a complex character; no_double with more particles than sites -> all
  * QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP; then QBH_ENODEVICE.  (A sector of 2^31 representatives or more is refused
- * with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards, communicators and the
- * Kondo sector family are out of scope (d-level sectors: qbh_corr_qudit_repr_dev below). */
+ * with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards and communicators are
+ * out of scope (d-level and Kondo sectors: the two calls below). */
 int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no_double, int n_trans, const int32_t *perms, const double *chars,
                               const qbh_z *d_vec, const double *d_vec_re, double *norm2, double *dens /* [2][N] */,
                               double *nn /* [4][N][N] */, qbh_z *hop /* [2][N][N] */, qbh_z *flip /* [N][N] */, int64_t *dim_out,
@@ -621,13 +622,56 @@ int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no_double, in
  * the table checks of qbh_corr_qudit_dev in its order (n_diag, diag NULL with n_diag > 0, one string table only, dd / str / aa
  * wanted without tables, non-finite table values); translation 0 not the identity or a non-permutation; d_vec_re with a complex
  * character -> all QBH_EINVAL; 2^40 words or more -> QBH_EUNSUPP; then QBH_ENODEVICE.  (A sector of 2^31 representatives or more
- * is refused with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards, communicators
- * and the Kondo sector family are out of scope. */
+ * is refused with QBH_EUNSUPP after its enumeration.)  No shape is refused for the size of its tables.  Row shards and
+ * communicators are out of scope (Kondo sectors: qbh_corr_kondo_repr_dev below). */
 int qbh_corr_qudit_repr_dev(int n_sites, int d, int total, int n_trans, const int32_t *perms, const double *chars,
                             const qbh_z *d_vec, const double *d_vec_re, int n_diag, const double *diag /* [n_diag][d] */,
                             const double *string_end /* [d] */, const double *string_mid /* [d] */, const double *lower /* [d] */,
                             double *norm2, double *pop /* [N][d] */, double *dd /* [n_diag][n_diag][N][N] */,
                             double *str /* [N][N] */, qbh_z *aa /* [N][N] */, int64_t *dim_out, void *stream);
+
+/* qbh_corr_kondo_repr_dev: a Kondo-lattice state held in a MOMENTUM SECTOR, indexed like the rows of qbh_gen_kondo_repr /
+ * qbh_mf_kondo_repr for the same (n_sites, n_elec, two_sz, n_trans, perms, chars): all orbit representatives of the words
+ * u | d << n | s << 2n, ascending, zero-norm representatives present as rows.  perms and chars mean what they mean there:
+ * T_g |u, d, s> = sgn(g, u) sgn(g, d) |g(u), g(d), g(s)> (the fermion sign sigma(g) from the two electron fields, none from s) and
+ * |a, k> the normalised sum_g chi(g) T_g |a>.  The call returns what qbh_corr_kondo_dev returns on the unfolded full-space state
+ * (same layouts, operator order and signs, raw bilinear forms, nothing divided by norm2), from the representatives alone, in one
+ * pass per launch, without a second vector and without scratch proportional to dim (the sector is enumerated inside the call).
+ * With w_a = |psi_a|^2 over the representatives of nonzero norm (an entry at a zero-norm representative is never read):
+ *   norm2 = sum_a w_a
+ *   site[c*N + i]  = sum_a w_a (1/|G|) sum_g f_c(g(i))(a), f = n_up, n_dn, n_up n_dn, S^z (+1/2 where the bit of s is clear)
+ *   nn[(2A+B)*N*N + i*N + j] = sum_a w_a (1/|G|) sum_g n_{g(i),A}(a) n_{g(j),B}(a)
+ *   zn[B*N*N + i*N + j] = sum_a w_a (1/|G|) sum_g S^z_{g(i)}(a) n_{g(j),B}(a)     zz[i*N + j] likewise with S^z_{g(i)} S^z_{g(j)}
+ *   hop, ee, ll, le: X[i][j] = (1/|G|) sum_a sum_g conj(psi_a) <a| X_{g(i) g(j)} |c> sigma(g*) conj(chi(g*)) sqrt(|S_b|/|S_a|) psi_b
+ *           over the g for which the representative word a has the pattern the operator leaves behind; c is the candidate word,
+ *           T_{g*} |c> = sigma |b>, a target b of zero norm is skipped: the entries kondo_row / qbh_mf_kondo_repr produce for the
+ *           one-term operator, averaged over the group.  <a|X|c>: hop[s] = c+_{i,s} c_{j,s}: (-1)^(particles of s between);
+ *           ee = s^+_i s^-_j: -(-1)^(particles of both species between); ll = S^+_i S^-_j: 1; le = S^+_i s^-_j: the sign of s^-_j
+ *           as in qbh_gen_kondo -- its candidate has popcount(s) + 1 and n_up + 1, another block of the sector.
+ * hop, ee and ll are Hermitian in (i, j): the kernel keeps one complex sum per CLASS of site pairs (an orbit of ordered pairs under
+ * the group together with its mirror image; the forward orientation adds the term, the backward one its conjugate, a class that
+ * is its own mirror is real) and issues one gather per row and unordered pair with the allowed pattern; nn and zz likewise
+ * without gathers.  zn and le are NOT Hermitian: one sum per ORBIT OF ORDERED PAIRS, the diagonal pairs included, so le[i][i] (the
+ * transverse Kondo term) comes out of the same pass; le is returned for ALL ordered (i, j).  site: one set of sums per orbit of
+ * sites.  The host expands every N x N array and fills the diagonals and mirrors as qbh_corr_kondo_dev does (zz[i][i] = norm2 / 4,
+ * hop[s][i][i] = site[s][i], ee[i][i] = n_up - n_up n_dn, ll[i][i] = norm2 / 2 + S^z_i, nn[i][i] from the site sums).  The group may
+ * contain reflections and need not act transitively.  All tables (translation tables, counting tables, characters, permutation
+ * bytes: at most 141,184 B) are staged in LDS; there is no global-memory table path.
+ * Any output but norm2 may be NULL; a NULL group issues none of its passes or gathers and leaves every bit of the other outputs
+ * unchanged; two calls return the same bits (no atomics).  d_vec_re (packed real parts) only with real characters (an imaginary
+ * part up to 1e-13 is dropped); all imaginary parts are then exactly 0.  *dim_out = the number of representatives.
+ * Checked in this order before the device is looked for, each with a message that names the argument, nothing written: perms or
+ * chars NULL -> QBH_EINVAL; the shape as qbh_gen_kondo checks it -> QBH_EINVAL, an empty sector -> QBH_EUNSUPP; n_trans outside
+ * 1 .. 64 -> QBH_EINVAL; both or neither vector pointer -> QBH_EINVAL; norm2 NULL -> QBH_EINVAL; translation 0 not the identity or
+ * a translation that is not a site permutation -> QBH_EINVAL; d_vec_re with a complex character -> QBH_EINVAL; 2^40 words or more
+ * -> QBH_EUNSUPP; then QBH_ENODEVICE.  (A sector of 2^31 representatives or more is refused with QBH_EUNSUPP after its
+ * enumeration.)  Row shards and communicators of the Kondo sector family are out of scope, as are a handle that keeps the
+ * enumeration and four-point functions. */
+int qbh_corr_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int n_trans, const int32_t *perms, const double *chars,
+                            const qbh_z *d_vec, const double *d_vec_re, double *norm2, double *site /* [4][N] */,
+                            double *nn /* [4][N][N] */, double *zn /* [2][N][N] */, double *zz /* [N][N] */,
+                            qbh_z *hop /* [2][N][N] */, qbh_z *ee /* [N][N] */, qbh_z *ll /* [N][N] */, qbh_z *le /* [N][N] */,
+                            int64_t *dim_out, void *stream);
 
 /* --------------------------------------------------------- checkpoints --- */
 /* The reference's checkpoint files from the C ABI, host only.

@@ -15,4 +15,4 @@ from .engine import (csr_mat, DeviceVec, lanczos, lanczos_real, eigenvec_CG, eig
 from .correlations import (spin_correlations, hubbard_correlations, structure_factor, momentum_distribution,  # noqa: F401
                            energy_from_correlations, qudit_correlations, spin_s_correlations, bose_correlations,
                            kondo_correlations, kondo_energy_from_correlations, spin_repr_correlations, hubbard_repr_correlations,
-                           qudit_repr_correlations, spin_s_repr_correlations, bose_repr_correlations)
+                           qudit_repr_correlations, spin_s_repr_correlations, bose_repr_correlations, kondo_repr_correlations)

@@ -112,7 +112,7 @@ EXPORTS = [
     "qbh_gen_kondo", "qbh_mf_kondo", "qbh_gen_kondo_repr", "qbh_gen_kondo_repr_cuts", "qbh_mf_kondo_repr", "qbh_mopr_diag_kondo_repr_dev",
     "qbh_mopr_kondo_dev", "qbh_mopr_kondo_repr_dev",
     "qbh_corr_spin_dev", "qbh_corr_hubbard_dev", "qbh_corr_qudit_dev", "qbh_corr_kondo_dev", "qbh_corr_spin_repr_dev",
-    "qbh_corr_hubbard_repr_dev", "qbh_corr_qudit_repr_dev",
+    "qbh_corr_hubbard_repr_dev", "qbh_corr_qudit_repr_dev", "qbh_corr_kondo_repr_dev",
 ]
 
 _lib = None
@@ -260,6 +260,8 @@ def lib():
     L.qbh_corr_hubbard_repr_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                             C.POINTER(i64), vp]
     L.qbh_corr_qudit_repr_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          C.POINTER(i64), vp]
+    L.qbh_corr_kondo_repr_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                           C.POINTER(i64), vp]
     L.qbh_csr_reference_order.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     _lib = L

@@ -1,13 +1,12 @@
 """All-pair static correlations of a device-resident state in one pass (qbh_corr_spin_dev / qbh_corr_hubbard_dev /
-qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev / qbh_corr_hubbard_repr_dev / qbh_corr_qudit_repr_dev), and the host
-arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
+qbh_corr_qudit_dev / qbh_corr_kondo_dev / qbh_corr_spin_repr_dev / qbh_corr_hubbard_repr_dev / qbh_corr_qudit_repr_dev /
+qbh_corr_kondo_repr_dev), and the host arithmetic that follows them: structure factor, momentum distribution, the energy as a sum of two-site expectation values.
 
 The device calls reduce over the state without a temporary vector, so they run next to a state that fills most of HBM; the
 reference's measure_full_static (src/model.cc:1660-1694) applies one product of operators per call into sector-sized temporaries.
-Of the momentum-sector states the spin-1/2, the Hubbard / t-J / spinless and the d-level families are covered
-(spin_repr_correlations, hubbard_repr_correlations, qudit_repr_correlations with spin_s_repr_correlations and bose_repr_correlations:
-from the orbit representatives alone); for the Kondo sector family the translation-averaged sector operators (the like of
-measure_repr_static_hubbard) stay the route.
+The momentum-sector states of all four families are covered (spin_repr_correlations, hubbard_repr_correlations,
+qudit_repr_correlations with spin_s_repr_correlations and bose_repr_correlations, kondo_repr_correlations: from the orbit
+representatives alone).
 """
 import ctypes as C
 
@@ -422,32 +421,70 @@ def kondo_correlations(n_sites, n_elec, two_sz, d_vec, real=False, normalize=Tru
         raise ValueError("kondo_correlations: unknown group(s) %s" % sorted(unknown))
     addr = _addr(d_vec)
     n2 = C.c_double()
-    site = np.zeros((4, N)) if want & {"dens", "docc", "sz_local"} else None
-    nn = np.zeros((4, N, N)) if "nn" in want else None
-    zn = np.zeros((2, N, N)) if "zn" in want else None
-    zz = np.zeros((N, N)) if "zz_ll" in want else None
-    hop = np.zeros((2, N, N), dtype=np.complex128) if "hop" in want else None
-    ee = np.zeros((N, N), dtype=np.complex128) if "pm_ee" in want else None
-    ll = np.zeros((N, N), dtype=np.complex128) if "pm_ll" in want else None
-    le = np.zeros((N, N), dtype=np.complex128) if "pm_le" in want else None
-    check(lib().qbh_corr_kondo_dev(N, int(n_elec), int(two_sz), None if real else addr, addr if real else None, C.byref(n2), _p(site),
-                                   _p(nn), _p(zn), _p(zz), _p(hop), _p(ee), _p(ll), _p(le), stream), "qbh_corr_kondo_dev")
-    out = {"norm2": n2.value}
+    bufs = _kondo_buffers(N, want)
+    check(lib().qbh_corr_kondo_dev(N, int(n_elec), int(two_sz), None if real else addr, addr if real else None, C.byref(n2),
+                                   *[_p(a) for a in bufs], stream), "qbh_corr_kondo_dev")
+    return _kondo_result(n2.value, bufs, want, normalize, "kondo_correlations")
+
+
+def _kondo_buffers(N, want):
+    """the output arrays of the wanted groups in the order of the C calls (site, nn, zn, zz, hop, ee, ll, le), None where not wanted"""
+    z = np.complex128
+    return (np.zeros((4, N)) if want & {"dens", "docc", "sz_local"} else None,
+            np.zeros((4, N, N)) if "nn" in want else None, np.zeros((2, N, N)) if "zn" in want else None,
+            np.zeros((N, N)) if "zz_ll" in want else None, np.zeros((2, N, N), dtype=z) if "hop" in want else None,
+            np.zeros((N, N), dtype=z) if "pm_ee" in want else None, np.zeros((N, N), dtype=z) if "pm_ll" in want else None,
+            np.zeros((N, N), dtype=z) if "pm_le" in want else None)
+
+
+def _kondo_result(norm2, bufs, want, normalize, who):
+    """the dict of kondo_correlations from the filled arrays of _kondo_buffers"""
+    site = bufs[0]
+    out = {"norm2": norm2}
     if "dens" in want:
         out["dens"] = site[0:2].copy()
     if "docc" in want:
         out["docc"] = site[2].copy()
     if "sz_local" in want:
         out["sz_local"] = site[3].copy()
-    for k, a in (("nn", nn), ("zn", zn), ("zz_ll", zz), ("hop", hop), ("pm_ee", ee), ("pm_ll", ll), ("pm_le", le)):
+    for k, a in zip(("nn", "zn", "zz_ll", "hop", "pm_ee", "pm_ll", "pm_le"), bufs[1:]):
         if a is not None:
             out[k] = a
     _kondo_derived(out)
     if normalize:
-        _nonzero_norm(out["norm2"], "kondo_correlations")
+        _nonzero_norm(out["norm2"], who)
         for k in out:
             if k != "norm2":
                 out[k] = out[k] / out["norm2"]
+    return out
+
+
+def kondo_repr_correlations(n_sites, n_elec, two_sz, perms, chars, d_vec, real=False, normalize=True, want=_KONDO_GROUPS, stream=None):
+    """kondo_correlations for a state of a MOMENTUM SECTOR: d_vec is indexed like the rows of csr_mat.kondo_repr / kondo_repr_mf for
+    the same (n_sites, n_elec, two_sz, perms, chars) -- all orbit representatives, ascending -- and the result is what
+    kondo_correlations gives on the unfolded full-space state, computed from the representatives in one pass per launch without a
+    second vector (qbh_corr_kondo_repr_dev).  perms [n_trans][N] (element 0 the identity; reflections allowed), chars [n_trans]
+    complex.  real=True: d_vec holds packed real parts; every character must be real.  Entries at representatives whose norm
+    vanishes at this momentum (the decoupled fake rows) are ignored.  want and the returned keys as in kondo_correlations, plus dim,
+    the number of representatives; kondo_energy_from_correlations, momentum_distribution and structure_factor take the arrays as
+    they are."""
+    N = int(n_sites)
+    want = set(want)
+    unknown = want - set(_KONDO_GROUPS)
+    if unknown:
+        raise ValueError("kondo_repr_correlations: unknown group(s) %s" % sorted(unknown))
+    p = np.ascontiguousarray(perms, dtype=np.int32).reshape(-1, N)
+    ch = np.ascontiguousarray(np.asarray(chars, dtype=np.complex128).reshape(-1))
+    if ch.shape[0] != p.shape[0]:
+        raise ValueError("kondo_repr_correlations: %d characters for %d translations" % (ch.shape[0], p.shape[0]))
+    addr = _addr(d_vec)
+    n2, dim = C.c_double(), C.c_int64()
+    bufs = _kondo_buffers(N, want)
+    check(lib().qbh_corr_kondo_repr_dev(N, int(n_elec), int(two_sz), int(p.shape[0]), _p(p), _p(ch.view(np.float64)),
+                                        None if real else addr, addr if real else None, C.byref(n2), *[_p(a) for a in bufs],
+                                        C.byref(dim), stream), "qbh_corr_kondo_repr_dev")
+    out = _kondo_result(n2.value, bufs, want, normalize, "kondo_repr_correlations")
+    out["dim"] = int(dim.value)
     return out
 
 

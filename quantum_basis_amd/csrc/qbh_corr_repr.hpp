@@ -1,7 +1,8 @@
 // qbh_corr_repr.hpp -- what the momentum-sector correlation calls share (qbh_corr_repr.hip: spin-1/2; qbh_corr_hubrepr.hip:
-// two-species fermions; qbh_corr_quditrepr.hip: d-level sites): the classes of site pairs and the orbits of sites under the group
-// (host), the block reduction of a workgroup of any size into partials[blockIdx.x][pass][accumulator], the shape of a launch from
-// its LDS footprint and the check of the characters of a packed-real vector.  Internal linkage, like qbh_sector.hpp.
+// two-species fermions; qbh_corr_quditrepr.hip: d-level sites; qbh_corr_kondorepr.hip: the Kondo lattice): the classes of site
+// pairs, the orbits of ordered site pairs and the orbits of sites under the group (host), the block reduction of a workgroup of
+// any size into partials[blockIdx.x][pass][accumulator], the shape of a launch from its LDS footprint and the check of the
+// characters of a packed-real vector.  Internal linkage, like qbh_sector.hpp.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -129,6 +130,57 @@ inline void repr_flatten_classes(const ReprClasses &K, int pad, std::vector<int3
     }
     for (size_t c = (size_t)K.n_cls; c < cls_start.size(); ++c) cls_start[c] = (int32_t)pairs.size();
     if (pairs.empty()) pairs.push_back(0u);                               // one site: no pairs, and nothing reads this word
+}
+
+// The orbits of ORDERED site pairs, the diagonal pairs (i, i) included (they form orbits of their own), for correlations that are
+// not Hermitian in (i, j) (qbh_corr_kondorepr.hip: <S^z_i n_j>, <S^+_i s^-_j>): value[i][j] = (sum over the pairs of the orbit of
+// (i, j)) / size.
+struct ReprOrbits {
+    int n_orb = 0;
+    std::vector<int> orb;                        // [N * N]: orbit of (i, j)
+    std::vector<int> size;                       // [n_orb]: ordered pairs in the orbit
+    std::vector<std::vector<uint32_t>> pairs;    // [n_orb]: pair words p | q << 8
+};
+
+inline ReprOrbits repr_ordered_orbits(int N, int n_trans, const int32_t *perms)
+{
+    ReprOrbits O;
+    std::vector<int> pp((size_t)N * N);
+    std::iota(pp.begin(), pp.end(), 0);
+    for (int g = 1; g < n_trans; ++g) {
+        const int32_t *pg = perms + (size_t)g * N;
+        for (int i = 0; i < N; ++i)
+            for (int j = 0; j < N; ++j) pp[(size_t)uf_find(pp, i * N + j)] = uf_find(pp, pg[i] * N + pg[j]);
+    }
+    const std::vector<int> orep = uf_smallest(pp);
+    O.orb.assign((size_t)N * N, -1);
+    std::vector<int> id((size_t)N * N, -1);
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) {
+            const int r = orep[(size_t)i * N + j];
+            if (id[(size_t)r] < 0) {
+                id[(size_t)r] = O.n_orb++;
+                O.size.push_back(0);
+                O.pairs.emplace_back();
+            }
+            const int o = id[(size_t)r];
+            O.orb[(size_t)i * N + j] = o;
+            ++O.size[(size_t)o];
+            O.pairs[(size_t)o].push_back((uint32_t)i | ((uint32_t)j << 8));
+        }
+    return O;
+}
+
+// as repr_flatten_classes, for the ordered orbits
+inline void repr_flatten_orbits(const ReprOrbits &O, int pad, std::vector<int32_t> &orb_start, std::vector<uint32_t> &pairs)
+{
+    orb_start.assign((size_t)O.n_orb + pad + 1, 0);
+    pairs.clear();
+    for (int o = 0; o < O.n_orb; ++o) {
+        orb_start[(size_t)o] = (int32_t)pairs.size();
+        pairs.insert(pairs.end(), O.pairs[(size_t)o].begin(), O.pairs[(size_t)o].end());
+    }
+    for (size_t o = (size_t)O.n_orb; o < orb_start.size(); ++o) orb_start[o] = (int32_t)pairs.size();
 }
 
 // The shape of a launch from the dynamic LDS of a workgroup: workgroups of 256 lanes while four or more fit a CU (at most four
