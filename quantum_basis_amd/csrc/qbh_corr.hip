@@ -8,13 +8,14 @@
 // (passes); a pass owns a group of site pairs (or of sites) and kCorrAcc accumulators per lane, every workgroup leaves its sums
 // at partials[blockIdx.x][pass][accumulator], and k_corr_reduce adds the workgroups in a fixed order, one lane per component: no
 // atomics, two calls on the same input return the same bits.
+// The host side of what all seven correlation calls share (qbh_corr.hpp) is defined here as well.
 #include <algorithm>
 #include <vector>
 
 #include "qbh_internal.hpp"
 #include "qbh_device.hpp"
 #include "qbh_gen_util.hpp"
-#include "qbh_corr.hpp"                                      // kCorrBlock, kCorrLdsCap, corr_block_partials, corr_uniform
+#include "qbh_corr.hpp"
 
 namespace qbh {
 namespace {
@@ -50,11 +51,8 @@ __global__ __launch_bounds__(64 * kCorrRedWaves) void k_corr_reduce(const double
 // of a site pass:  [g] = sum_s |psi_s|^2 (1/2 - bit_site),  [G] = sum_s |psi_s|^2 (read from the first site pass).
 // (One site pass over 31 sites instead of two over 16 was measured: the unrolled loop takes 186 VGPRs instead of 155, two
 // wavefronts per SIMD instead of three, and the whole launch 113 ms instead of 83 at 30 sites.)
-// A pass has to know every row's pattern again, and the unranking walk (one dependent LDS read per site) would cost a third of
-// the time of a pass of 16 pairs.  So a workgroup takes tiles of kCorrBlock * R CONSECUTIVE rows: every lane unranks one row and
-// steps to the next R - 1 patterns in order (the next larger word with as many bits), the tile's patterns go through LDS, and
-// the lanes then take them row-interleaved, so that consecutive lanes still hold consecutive rows for the gathers.  A lane's R
-// patterns are R + 1 words apart from the next lane's (an odd stride: neither the stores nor the loads meet in a bank).
+// Rows come in tiles of kCorrBlock * R (the scheme is described in qbh_corr.hpp): unranking every row in every pass would cost
+// a third of the time of a pass of 16 pairs.
 // W: the word of a pattern, of a rank and of the table entries -- 32 bits up to 32 sites (C(32, 16) < 2^32), 64 bits beyond.
 constexpr int kSpinGroup = 16;
 
@@ -134,9 +132,7 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_spin(CorrSpin t)
         const int64_t row = base + local;
         if (row >= t.dim) break;
         const W s = stage[(local / R) * (R + 1) + local % R];
-        d2 x = {0.0, 0.0};
-        if (REALX) x.x = t.xr[row];
-        else       x = t.xg[row];
+        const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
         const double w = fma(x.x, x.x, x.y * x.y);
         if (!pair_pass) {
 #pragma unroll
@@ -279,9 +275,7 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_hubbard(CorrHub t)
     for (int64_t row = (int64_t)blockIdx.x * kCorrBlock + tid; row < dim; row += stride) {
         const int64_t ru = row / t.Nd, rd = row - ru * t.Nd;
         const uint32_t u = t.cfg_u[ru], d = t.cfg_d[rd];
-        d2 x = {0.0, 0.0};
-        if (REALX) x.x = t.xr[row];
-        else       x = t.xg[row];
+        const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
         if (kind == kHubSite) {
             const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
@@ -365,7 +359,27 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_hubbard(CorrHub t)
 // ------------------------------------------------------------------------------------------------------ host side --
 }  // namespace
 
-// workgroups along x: what the LDS lets a CU hold (four at most), each walking its share of the `rows_per_block`-row pieces
+int corr_check_vectors(const char *who, const void *d_vec, const void *d_vec_re)
+{
+    if ((d_vec != nullptr) != (d_vec_re != nullptr)) return QBH_OK;
+    set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
+    return QBH_EINVAL;
+}
+
+int corr_check_norm2(const char *who, const double *norm2)
+{
+    if (norm2 != nullptr) return QBH_OK;
+    set_error("%s: norm2 is NULL", who);
+    return QBH_EINVAL;
+}
+
+int corr_check_device()
+{
+    if (qbh_device_count() > 0) return QBH_OK;
+    set_error("no HIP device visible");
+    return QBH_ENODEVICE;
+}
+
 int corr_grid(int64_t dim, size_t lds, int rows_per_block)
 {
     const int ncu = device_cu_count();
@@ -374,11 +388,29 @@ int corr_grid(int64_t dim, size_t lds, int rows_per_block)
     return (int)std::max<int64_t>(1, std::min<int64_t>(nblk, (int64_t)ncu * per_cu));
 }
 
-// second stage + download: out[ncomp] = sum over the n_parts workgroups, in the order of k_corr_reduce
-int corr_finish(double *d_partials, int n_parts, int ncomp, std::vector<double> &out, hipStream_t s)
+hipError_t corr_launch(const void *kernel, int gx, int n_pass, int block, size_t lds, hipStream_t s, const void *arg)
 {
-    double *d_out = d_partials + (size_t)n_parts * ncomp;          // the sums follow the partials in one allocation
-    QBH_TRY(launch_kernel(k_corr_reduce, (ncomp + 63) / 64, 64 * kCorrRedWaves, s, (const double *)d_partials, n_parts, ncomp, d_out));
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    void *args[] = {const_cast<void *>(arg)};
+    (void)hipLaunchKernel(kernel, dim3(gx, n_pass), dim3(block), args, lds, s);
+    return hipGetLastError();
+}
+
+size_t corr_reduce_doubles(int gx, int n_pass, int na) { return ((size_t)gx + 1) * n_pass * na; }
+
+int corr_reduce_launch_any(const char *who, const void *kernel, int gx, int n_pass, int na, int block, size_t lds, hipStream_t s,
+                       const void *arg, double **partials, std::vector<void *> &pool, std::vector<double> &out)
+{
+    const int ncomp = n_pass * na;
+    if (*partials == nullptr) {
+        QBH_HIP_WHO(who, qbh::dev_alloc(partials, corr_reduce_doubles(gx, n_pass, na) * sizeof(double)));
+        pool.push_back(*partials);
+    }
+    QBH_HIP_WHO(who, corr_launch(kernel, gx, n_pass, block, lds, s, arg));
+    // second stage + download: out[ncomp] = sum over the gx workgroups, in the order of k_corr_reduce
+    double *d_out = *partials + (size_t)gx * ncomp;
+    QBH_TRY(launch_kernel(k_corr_reduce, (ncomp + 63) / 64, 64 * kCorrRedWaves, s, (const double *)*partials, gx, ncomp, d_out));
     out.resize((size_t)ncomp);
     QBH_HIP(hipMemcpyAsync(out.data(), d_out, (size_t)ncomp * sizeof(double), hipMemcpyDeviceToHost, s));
     QBH_HIP(hipStreamSynchronize(s));
@@ -454,14 +486,23 @@ size_t corr_hub_lds(int n_sites, int n_up, int n_dn)
     return n_chunks * 64 * ((size_t)n_up + 1 + (size_t)n_dn + 1) * 4;
 }
 
-int corr_spin_run(int n_sites, int n_dn, const d2 *xg, const double *xr, bool want_zz, bool want_pm, std::vector<double> &comp,
-                  int *n_pair_pass_out, hipStream_t s, std::vector<void *> &pool)
+enum { kSpinPair = 0, kSpinSite = 1 };
+
+template <typename W, int NC>
+void (*spin_kernel(bool rx))(CorrSpin)
+{
+    return rx ? k_corr_spin<true, W, NC> : k_corr_spin<false, W, NC>;
+}
+
+int corr_spin_run(const char *who, int n_sites, int n_dn, const d2 *xg, const double *xr, bool want_zz, bool want_pm,
+                  std::vector<double> &comp, CorrPasses &sp, hipStream_t s, std::vector<void *> &pool)
 {
     const int n_chunks = (n_sites + 5) / 6, G = kSpinGroup;
     const int n_pairs = (want_zz || want_pm) ? n_sites * (n_sites - 1) / 2 : 0;
     const int NA = xr ? spin_acc<true>() : spin_acc<false>();
-    const int n_pair_pass = (n_pairs + G - 1) / G, n_site_pass = (n_sites + G - 1) / G;
-    std::vector<uint64_t> mask((size_t)n_pair_pass * G, 0ULL);          // padding: mask 0, which no row matches
+    sp.add(kSpinPair, n_pairs, G);
+    sp.add(kSpinSite, n_sites, G);
+    std::vector<uint64_t> mask((size_t)sp.count[kSpinPair] * G, 0ULL);  // padding: mask 0, which no row matches
     if (n_pairs > 0) {
         size_t q = 0;
         for (int i = 0; i < n_sites; ++i)
@@ -472,7 +513,7 @@ int corr_spin_run(int n_sites, int n_dn, const d2 *xg, const double *xr, bool wa
     t.n_sites = n_sites;
     t.n_dn = n_dn;
     t.n_chunks = n_chunks;
-    t.n_pair_pass = n_pair_pass;
+    t.n_pair_pass = sp.count[kSpinPair];
     t.want_pm = want_pm ? 1 : 0;
     t.want_zz = want_zz ? 1 : 0;
     t.dim = (int64_t)binom_u64(n_sites, n_dn);
@@ -484,53 +525,32 @@ int corr_spin_run(int n_sites, int n_dn, const d2 *xg, const double *xr, bool wa
     else     corr_spin_tables<uint64_t>(n_sites, n_dn, mask, tables, &chunk_at, &mask_at);
     const size_t lds = corr_spin_lds(n_sites, n_dn);
     const int gx = corr_grid(t.dim, lds, kCorrBlock * (w32 ? spin_rows<uint32_t>() : spin_rows<uint64_t>()));
-    const int n_pass = n_pair_pass + n_site_pass;
-    const int ncomp = n_pass * NA;
-    // one allocation: partials [gx][ncomp] | their sums [ncomp] | the tables
-    const size_t n_red = ((size_t)gx + 1) * ncomp;
-    QBH_HIP(qbh::dev_alloc(&t.partials, (n_red + tables.size()) * 8));
+    // this call alone brings its own allocation: the partials and their sums | the tables, so that they cost one allocation and
+    // one copy
+    const size_t n_red = corr_reduce_doubles(gx, sp.n_pass, NA);
+    QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, (n_red + tables.size()) * 8));
     pool.push_back(t.partials);
     const char *d_tables = reinterpret_cast<const char *>(t.partials + n_red);
-    QBH_HIP(hipMemcpy(t.partials + n_red, tables.data(), tables.size() * 8, hipMemcpyHostToDevice));
+    QBH_HIP_WHO(who, hipMemcpy(t.partials + n_red, tables.data(), tables.size() * 8, hipMemcpyHostToDevice));
     t.binom = d_tables;
     t.chunk = d_tables + chunk_at;
     t.mask = reinterpret_cast<const uint64_t *>(d_tables + mask_at);
-#define QBH_CORR_SPIN_LAUNCH(W, NC)                                                                                                         \
-    do {                                                                                                                                   \
-        if (xr != nullptr) {                                                                                                               \
-            QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_spin<true, W, NC>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds));                                                                                        \
-            hipLaunchKernelGGL((k_corr_spin<true, W, NC>), dim3(gx, n_pass), dim3(kCorrBlock), lds, s, t);                                  \
-        } else {                                                                                                                           \
-            QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_spin<false, W, NC>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds));                                                                                        \
-            hipLaunchKernelGGL((k_corr_spin<false, W, NC>), dim3(gx, n_pass), dim3(kCorrBlock), lds, s, t);                                 \
-        }                                                                                                                                  \
-    } while (0)
+    void (*kernel)(CorrSpin);
     if (w32) {                                              // 19 .. 32 sites: the re-ranking loop unrolled
         switch (n_chunks) {
-        case 4: QBH_CORR_SPIN_LAUNCH(uint32_t, 4); break;
-        case 5: QBH_CORR_SPIN_LAUNCH(uint32_t, 5); break;
-        case 6: QBH_CORR_SPIN_LAUNCH(uint32_t, 6); break;
-        default: QBH_CORR_SPIN_LAUNCH(uint32_t, 0); break;
+        case 4: kernel = spin_kernel<uint32_t, 4>(xr != nullptr); break;
+        case 5: kernel = spin_kernel<uint32_t, 5>(xr != nullptr); break;
+        case 6: kernel = spin_kernel<uint32_t, 6>(xr != nullptr); break;
+        default: kernel = spin_kernel<uint32_t, 0>(xr != nullptr); break;
         }
-    } else if (n_chunks == 6) {                             // 33 .. 36 sites
-        QBH_CORR_SPIN_LAUNCH(uint64_t, 6);
-    } else {
-        QBH_CORR_SPIN_LAUNCH(uint64_t, 0);
+    } else {                                                // 33 .. 36 sites unrolled
+        kernel = n_chunks == 6 ? spin_kernel<uint64_t, 6>(xr != nullptr) : spin_kernel<uint64_t, 0>(xr != nullptr);
     }
-#undef QBH_CORR_SPIN_LAUNCH
-    QBH_HIP(hipGetLastError());
-    *n_pair_pass_out = n_pair_pass;
-    return corr_finish(t.partials, gx, ncomp, comp, s);
+    return corr_reduce_launch(who, kernel, gx, sp.n_pass, NA, kCorrBlock, lds, s, t, t.partials, pool, comp);
 }
 
-struct HubPasses {
-    int n_pairs, first[5], count[5];             // per kind: the first pass and the number of passes
-};
-
-int corr_hub_run(int n_sites, int n_up, int n_dn, const d2 *xg, const double *xr, bool want_nn, bool want_hop, bool want_flip,
-                 std::vector<double> &comp, HubPasses &hp, hipStream_t s, std::vector<void *> &pool)
+int corr_hub_run(const char *who, int n_sites, int n_up, int n_dn, const d2 *xg, const double *xr, bool want_nn, bool want_hop,
+                 bool want_flip, std::vector<double> &comp, CorrPasses &hp, hipStream_t s, std::vector<void *> &pool)
 {
     const int n_chunks = (n_sites + 5) / 6;
     std::vector<uint32_t> cu, cd;
@@ -544,19 +564,13 @@ int corr_hub_run(int n_sites, int n_up, int n_dn, const d2 *xg, const double *xr
         for (int i = 0; i < n_sites; ++i)
             for (int j = i + 1; j < n_sites; ++j) pair[q++] = (uint32_t)i | ((uint32_t)j << 8);
     }
-    hp.n_pairs = n_pairs;
-    const int c8 = (n_pairs + 7) / 8, c16 = (n_pairs + 15) / 16;
-    hp.count[kHubNN] = want_nn ? c8 : 0;
-    hp.count[kHubHopU] = hp.count[kHubHopD] = want_hop ? c16 : 0;
-    hp.count[kHubFlip] = want_flip ? c16 : 0;
-    hp.count[kHubSite] = (n_sites + 7) / 8;
+    hp.add(kHubNN, want_nn ? n_pairs : 0, 8);
+    hp.add(kHubHopU, want_hop ? n_pairs : 0, 16);
+    hp.add(kHubHopD, want_hop ? n_pairs : 0, 16);
+    hp.add(kHubFlip, want_flip ? n_pairs : 0, 16);
+    hp.add(kHubSite, n_sites, 8);
     CorrHub t{};
-    int n_pass = 0;
-    for (int k = 0; k < 5; ++k) {
-        hp.first[k] = n_pass;
-        n_pass += hp.count[k];
-        t.pass_end[k] = n_pass;
-    }
+    for (int k = 0; k < 5; ++k) t.pass_end[k] = hp.first[k] + hp.count[k];
     t.n_sites = n_sites;
     t.n_up = n_up;
     t.n_dn = n_dn;
@@ -577,18 +591,9 @@ int corr_hub_run(int n_sites, int n_up, int n_dn, const d2 *xg, const double *xr
     t.chunk_d = d_chd;
     t.pair = d_pair;
     const size_t lds = corr_hub_lds(n_sites, n_up, n_dn);
-    const int gx = corr_grid(t.Nu * t.Nd, lds, kCorrBlock), ncomp = n_pass * kHubAcc;
-    QBH_HIP(qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * ncomp * sizeof(double)));
-    pool.push_back(t.partials);
-    if (xr != nullptr) {
-        QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_hubbard<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_corr_hubbard<true>), dim3(gx, n_pass), dim3(kCorrBlock), lds, s, t);
-    } else {
-        QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_hubbard<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_corr_hubbard<false>), dim3(gx, n_pass), dim3(kCorrBlock), lds, s, t);
-    }
-    QBH_HIP(hipGetLastError());
-    return corr_finish(t.partials, gx, ncomp, comp, s);
+    void (*kernel)(CorrHub) = xr ? k_corr_hubbard<true> : k_corr_hubbard<false>;
+    return corr_reduce_launch(who, kernel, corr_grid(t.Nu * t.Nd, lds, kCorrBlock), hp.n_pass, kHubAcc, kCorrBlock, lds, s, t,
+                              nullptr, pool, comp);
 }
 
 }  // namespace
@@ -598,58 +603,48 @@ extern "C" int qbh_corr_spin_dev(int n_sites, int n_dn, const qbh_z *d_vec, cons
                                  qbh_z *pm, void *stream)
 {
     using namespace qbh;
+    static const char *who = "qbh_corr_spin_dev";
     if (n_sites <= 0 || n_sites > 62) {
-        set_error("qbh_corr_spin_dev: n_sites = %d (1 .. 62 allowed)", n_sites);
+        set_error("%s: n_sites = %d (1 .. 62 allowed)", who, n_sites);
         return QBH_EINVAL;
     }
     if (n_dn < 0 || n_dn > n_sites || n_dn > 33) {
-        set_error("qbh_corr_spin_dev: n_dn = %d (0 .. min(n_sites, 33) allowed)", n_dn);
+        set_error("%s: n_dn = %d (0 .. min(n_sites, 33) allowed)", who, n_dn);
         return QBH_EINVAL;
     }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("qbh_corr_spin_dev: exactly one of d_vec and d_vec_re must be given");
-        return QBH_EINVAL;
-    }
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
     if (binom_u64(n_sites, n_dn) >= (1ULL << 62)) {
-        set_error("qbh_corr_spin_dev: a sector of 2^62 rows or more");
+        set_error("%s: a sector of 2^62 rows or more", who);
         return QBH_EUNSUPP;
     }
     const size_t lds = corr_spin_lds(n_sites, n_dn);
     if (lds > kCorrLdsCap) {
-        set_error("qbh_corr_spin_dev: tables (%zu bytes) do not fit LDS", lds);
+        set_error("%s: tables (%zu bytes) do not fit LDS", who, lds);
         return QBH_EUNSUPP;
     }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites, G = kSpinGroup;
     std::vector<void *> pool;
     std::vector<double> comp;
-    int npp = 0;
-    const int rc = corr_spin_run(N, n_dn, reinterpret_cast<const d2 *>(d_vec), d_vec_re, zz != nullptr, pm != nullptr, comp, &npp,
+    CorrPasses sp;
+    const int rc = corr_spin_run(who, N, n_dn, reinterpret_cast<const d2 *>(d_vec), d_vec_re, zz != nullptr, pm != nullptr, comp, sp,
                                  (hipStream_t)stream, pool);
     free_pool(pool);
     if (rc != QBH_OK) return rc;
     const bool rx = d_vec_re != nullptr;
     const int NA = rx ? spin_acc<true>() : spin_acc<false>();
-    auto site_sum = [&](int site) { return comp[(size_t)(npp + site / G) * NA + site % G]; };
-    const double n2 = comp[(size_t)npp * NA + G];
+    auto site_sum = [&](int site) { return sp.at(comp, kSpinSite, site, G, 0, NA); };
+    const double n2 = sp.at(comp, kSpinSite, 0, G, 1, NA);
     if (norm2) *norm2 = n2;
     if (sz)
         for (int i = 0; i < N; ++i) sz[i] = site_sum(i);
-    size_t q = 0;
+    int q = 0;
     for (int i = 0; i < N; ++i) {
         if (zz) zz[(size_t)i * N + i] = 0.25 * n2;
         if (pm) pm[(size_t)i * N + i] = qbh_z{0.5 * n2 + site_sum(i), 0.0};
-        for (int j = i + 1; j < N; ++j, ++q) {
-            const size_t c = (q / G) * NA + q % G;           // the pair's accumulators: present when zz or pm is asked for
-            if (zz) zz[(size_t)i * N + j] = zz[(size_t)j * N + i] = 0.25 * (n2 - 2.0 * comp[c]);
-            if (pm) {
-                const double re = comp[c + G], im = rx ? 0.0 : comp[c + 2 * G];
-                pm[(size_t)i * N + j] = qbh_z{re, im};
-                pm[(size_t)j * N + i] = qbh_z{re, -im};
-            }
+        for (int j = i + 1; j < N; ++j, ++q) {               // the pair's accumulators are present when zz or pm is asked for
+            if (zz) zz[(size_t)i * N + j] = zz[(size_t)j * N + i] = corr_zz_pair(n2, sp.at(comp, kSpinPair, q, G, 0, NA));
+            if (pm) corr_put_herm(pm, N, i, j, sp.at(comp, kSpinPair, q, G, 1, NA), rx ? 0.0 : sp.at(comp, kSpinPair, q, G, 2, NA));
         }
     }
     return QBH_OK;
@@ -659,75 +654,46 @@ extern "C" int qbh_corr_hubbard_dev(int n_sites, int n_up, int n_dn, const qbh_z
                                     double *nn, qbh_z *hop, qbh_z *flip, void *stream)
 {
     using namespace qbh;
+    static const char *who = "qbh_corr_hubbard_dev";
     if (n_sites <= 0 || n_sites > 31) {
-        set_error("qbh_corr_hubbard_dev: n_sites = %d (1 .. 31 allowed)", n_sites);
+        set_error("%s: n_sites = %d (1 .. 31 allowed)", who, n_sites);
         return QBH_EINVAL;
     }
     if (n_up < 0 || n_dn < 0 || n_up > n_sites || n_dn > n_sites) {
-        set_error("qbh_corr_hubbard_dev: (n_up, n_dn) = (%d, %d) (0 .. n_sites allowed)", n_up, n_dn);
+        set_error("%s: (n_up, n_dn) = (%d, %d) (0 .. n_sites allowed)", who, n_up, n_dn);
         return QBH_EINVAL;
     }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("qbh_corr_hubbard_dev: exactly one of d_vec and d_vec_re must be given");
-        return QBH_EINVAL;
-    }
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
     const size_t lds = corr_hub_lds(n_sites, n_up, n_dn);
     if (lds > kCorrLdsCap) {
-        set_error("qbh_corr_hubbard_dev: tables (%zu bytes) do not fit LDS", lds);
+        set_error("%s: tables (%zu bytes) do not fit LDS", who, lds);
         return QBH_EUNSUPP;
     }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites;
     const size_t NN = (size_t)N * N;
     std::vector<void *> pool;
     std::vector<double> comp;
-    HubPasses hp{};
-    const int rc = corr_hub_run(N, n_up, n_dn, reinterpret_cast<const d2 *>(d_vec), d_vec_re, nn != nullptr, hop != nullptr, flip != nullptr,
-                                comp, hp, (hipStream_t)stream, pool);
+    CorrPasses hp;
+    const int rc = corr_hub_run(who, N, n_up, n_dn, reinterpret_cast<const d2 *>(d_vec), d_vec_re, nn != nullptr, hop != nullptr,
+                                flip != nullptr, comp, hp, (hipStream_t)stream, pool);
     free_pool(pool);
     if (rc != QBH_OK) return rc;
     const bool rx = d_vec_re != nullptr;
-    auto at = [&](int kind, int item, int per_pass, int slot) {
-        return comp[(size_t)(hp.first[kind] + item / per_pass) * kHubAcc + (size_t)slot * per_pass + item % per_pass];
-    };
-    const double n2 = comp[(size_t)hp.first[kHubSite] * kHubAcc + 24];
-    if (norm2) *norm2 = n2;
-    size_t q = 0;
+    auto at = [&](int kind, int item, int per_pass, int slot) { return hp.at(comp, kind, item, per_pass, slot, kHubAcc); };
+    if (norm2) *norm2 = at(kHubSite, 0, 8, 3);
+    int q = 0;
     for (int i = 0; i < N; ++i) {
         const double nu = at(kHubSite, i, 8, 0), nd = at(kHubSite, i, 8, 1), docc = at(kHubSite, i, 8, 2);
         if (dens) {
             dens[i] = nu;
             dens[N + i] = nd;
         }
-        if (nn) {
-            nn[0 * NN + (size_t)i * N + i] = nu;          // n^2 = n
-            nn[1 * NN + (size_t)i * N + i] = docc;
-            nn[2 * NN + (size_t)i * N + i] = docc;
-            nn[3 * NN + (size_t)i * N + i] = nd;
-        }
-        if (hop) {
-            hop[0 * NN + (size_t)i * N + i] = qbh_z{nu, 0.0};
-            hop[1 * NN + (size_t)i * N + i] = qbh_z{nd, 0.0};
-        }
-        if (flip) flip[(size_t)i * N + i] = qbh_z{nu - docc, 0.0};
+        if (nn) corr_put_nn_diag(nn, N, i, nu, docc, nd);
+        corr_put_onsite_diag(hop, flip, N, i, nu, nd, docc);
         for (int j = i + 1; j < N; ++j, ++q) {
-            const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
-            if (nn) {
-                const double uu = at(kHubNN, (int)q, 8, 0), dd = at(kHubNN, (int)q, 8, 1), ud = at(kHubNN, (int)q, 8, 2),
-                             du = at(kHubNN, (int)q, 8, 3);
-                nn[0 * NN + ij] = nn[0 * NN + ji] = uu;
-                nn[3 * NN + ij] = nn[3 * NN + ji] = dd;
-                nn[1 * NN + ij] = nn[2 * NN + ji] = ud;       // <n_{i,up} n_{j,dn}> = the du entry of (j, i)
-                nn[2 * NN + ij] = nn[1 * NN + ji] = du;
-            }
-            auto herm = [&](qbh_z *out, int kind) {
-                const double re = at(kind, (int)q, 16, 0), im = rx ? 0.0 : at(kind, (int)q, 16, 1);
-                out[ij] = qbh_z{re, im};
-                out[ji] = qbh_z{re, -im};
-            };
+            if (nn) corr_put_nn_pair(nn, N, i, j, at(kHubNN, q, 8, 0), at(kHubNN, q, 8, 2), at(kHubNN, q, 8, 3), at(kHubNN, q, 8, 1));
+            auto herm = [&](qbh_z *out, int kind) { corr_put_herm(out, N, i, j, at(kind, q, 16, 0), rx ? 0.0 : at(kind, q, 16, 1)); };
             if (hop) {
                 herm(hop, kHubHopU);
                 herm(hop + NN, kHubHopD);

@@ -39,8 +39,8 @@
 //   HOPU / HOPD / FLIP  8 classes:  [g] Re C, [8+g] Im C (complex vectors only)           gathers
 //   SITE  5 site orbits:  [g] U, [5+g] D, [10+g] UD, [15] norm2 (read from the first site pass)
 // A group that is not asked for has no passes; it changes neither the grid along x nor any other accumulator, so the other
-// outputs keep their bits.  Every workgroup leaves its sums at partials[blockIdx.x][pass][accumulator] (repr_block_partials) and
-// k_corr_reduce adds the workgroups in a fixed order (corr_finish): no atomics, two calls return the same bits.
+// outputs keep their bits.  Every workgroup leaves its sums at partials[blockIdx.x][pass][accumulator] (corr_block_partials) and
+// k_corr_reduce adds the workgroups in a fixed order (corr_reduce_launch): no atomics, two calls return the same bits.
 //
 // Tables.  The binomials, the characters and the permutation bytes are always staged in LDS (at most 12 KB).  The translation
 // tables join them when everything fits kCorrLdsCap (150 KB); 62 group elements x 6 chunks (the dihedral group of a ring of 31)
@@ -63,8 +63,8 @@
 
 #include "qbh_sector.hpp"
 #include "qbh_device.hpp"
-#include "qbh_corr.hpp"                                      // kCorrLdsCap, corr_uniform, corr_finish
-#include "qbh_corr_repr.hpp"                                 // repr_classes, repr_block_partials
+#include "qbh_corr.hpp"                                      // device helpers, launch path, pass layout and host fills
+#include "qbh_corr_repr.hpp"                                 // classes and orbits of site pairs, symmetry checks
 
 namespace qbh {
 namespace {
@@ -72,7 +72,6 @@ namespace {
 constexpr int kHrAcc = 16;                                   // accumulators of a pass
 constexpr int kHrNN = kHrAcc / 4, kHrGat = kHrAcc / 2, kHrSite = (kHrAcc - 1) / 3;      // classes / classes / site orbits of a pass
 enum { kHrKindNN = 0, kHrKindHopU = 1, kHrKindHopD = 2, kHrKindFlip = 3, kHrKindSite = 4 };
-constexpr int kHrBlockS = kReprBlockS, kHrBlockL = kReprBlockL;
 constexpr int kHrBinomRow = 34;                              // HubReprDev::binom[p][0 .. 33]
 
 // The pair words of class c are pairs[cls_start[c] .. cls_start[c + 1]) (qbh_corr_repr.hpp); cls_start is padded with the total
@@ -139,16 +138,13 @@ __global__ __launch_bounds__(BLOCK) void k_corr_hubrepr(CorrHubRepr t)
         const bool no_double = t.no_double != 0;
         const uint64_t cu_count = binom[n * kHrBinomRow + t.n_up];
         int k0[GH + 1];
-#pragma unroll
-        for (int g = 0; g <= GH; ++g) k0[g] = (int)corr_uniform((uint32_t)t.cls_start[lp * GH + g]);
+        corr_group_bounds<GH>(t.cls_start, lp * GH, k0);
         for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
             const uint8_t ci = t.info[row];
             if (ci & 0x80) continue;                                      // zero norm at this momentum: its entry is never read
             const uint64_t a = t.reps[row], au = a & mlow, ad = a >> n;
             const double sa = (double)(ci & 0x7f);
-            d2 x = {0.0, 0.0};
-            if (REALX) x.x = t.xr[row];
-            else       x = t.xg[row];
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
 #pragma unroll
             for (int g = 0; g < GH; ++g) {
                 double sr = 0.0, si = 0.0;
@@ -215,14 +211,11 @@ __global__ __launch_bounds__(BLOCK) void k_corr_hubrepr(CorrHubRepr t)
         }
     } else if (kind == kHrKindNN) {
         int k0[GN + 1];
-#pragma unroll
-        for (int g = 0; g <= GN; ++g) k0[g] = (int)corr_uniform((uint32_t)t.cls_start[lp * GN + g]);
+        corr_group_bounds<GN>(t.cls_start, lp * GN, k0);
         for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
             if (t.info[row] & 0x80) continue;
             const uint64_t a = t.reps[row], au = a & mlow, ad = a >> n;
-            d2 x = {0.0, 0.0};
-            if (REALX) x.x = t.xr[row];
-            else       x = t.xg[row];
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
             const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
             for (int g = 0; g < GN; ++g) {
@@ -253,9 +246,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_hubrepr(CorrHubRepr t)
         for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
             if (t.info[row] & 0x80) continue;
             const uint64_t a = t.reps[row], au = a & mlow, ad = a >> n;
-            d2 x = {0.0, 0.0};
-            if (REALX) x.x = t.xr[row];
-            else       x = t.xg[row];
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
             const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
             for (int g = 0; g < NS; ++g) {
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_hubrepr(CorrHubRepr t)
             acc[3 * NS] += w;
         }
     }
-    repr_block_partials<NA, BLOCK>(acc, red, t.partials);
+    corr_block_partials<NA, BLOCK>(acc, red, t.partials);
 }
 
 // ------------------------------------------------------------------------------------------------------ host side --
@@ -277,29 +268,22 @@ size_t hr_lds_small(int n_sites, int n_trans)
 }
 bool hr_tab_lds(int n_sites, int n_trans, size_t n_tab) { return hr_lds_small(n_sites, n_trans) + n_tab * 8 <= kCorrLdsCap; }
 
-template <bool REALX, int BLOCK, bool TABLDS>
-hipError_t hr_launch(const CorrHubRepr &t, int gx, int n_pass, size_t lds, hipStream_t s)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_hubrepr<REALX, BLOCK, TABLDS>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_corr_hubrepr<REALX, BLOCK, TABLDS>), dim3(gx, n_pass), dim3(BLOCK), lds, s, t);
-    return hipGetLastError();
-}
-
 // the passes of the wanted groups, the launch and the two-stage reduction: comp[pass * kHrAcc + accumulator]
 template <bool REALX>
 int corr_hubrepr_run(const char *who, CorrHubRepr t, const ReprClasses &K, size_t n_tab, bool want_nn, bool want_hop, bool want_flip,
-                     std::vector<double> &comp, hipStream_t s, std::vector<void *> &pool)
+                     std::vector<double> &comp, CorrPasses &hp, hipStream_t s, std::vector<void *> &pool)
 {
     constexpr int NA = kHrAcc;
-    const int n_nn = (K.n_cls + kHrNN - 1) / kHrNN, n_gat = (K.n_cls + kHrGat - 1) / kHrGat, n_site = (K.n_orb + kHrSite - 1) / kHrSite;
-    const int per_kind[5] = {want_nn ? n_nn : 0, want_hop ? n_gat : 0, want_hop ? n_gat : 0, want_flip ? n_gat : 0, n_site};
-    int n_pass = 0;
-    for (int k = 0; k < 5; ++k) t.pass_end[k] = n_pass += per_kind[k];
+    hp.add(kHrKindNN, want_nn ? K.n_cls : 0, kHrNN);
+    hp.add(kHrKindHopU, want_hop ? K.n_cls : 0, kHrGat);
+    hp.add(kHrKindHopD, want_hop ? K.n_cls : 0, kHrGat);
+    hp.add(kHrKindFlip, want_flip ? K.n_cls : 0, kHrGat);
+    hp.add(kHrKindSite, K.n_orb, kHrSite);
+    for (int k = 0; k < 5; ++k) t.pass_end[k] = hp.first[k] + hp.count[k];
+    const int n_site = hp.count[kHrKindSite];
     std::vector<int32_t> cls_start;
     std::vector<uint32_t> pairs;
-    repr_flatten_classes(K, NA, cls_start, pairs);
+    repr_flatten(K.pairs, NA, cls_start, pairs);
     std::vector<uint64_t> site_mask((size_t)n_site * kHrSite, 0ULL);
     std::copy(K.mask.begin(), K.mask.end(), site_mask.begin());
     int32_t *d_start = nullptr;
@@ -314,17 +298,12 @@ int corr_hubrepr_run(const char *who, CorrHubRepr t, const ReprClasses &K, size_
     const bool tab_lds = hr_tab_lds(t.n_sites, t.n_trans, n_tab);
     const size_t lds = hr_lds_small(t.n_sites, t.n_trans) + (tab_lds ? n_tab * 8 : 0);
     const ReprShape shape = repr_launch_shape(lds, t.dim);
-    const bool large = shape.large;                                       // then one workgroup of 1024 lanes per CU
-    const int gx = shape.gx;
-    const int ncomp = n_pass * NA;
-    QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * ncomp * sizeof(double)));
-    pool.push_back(t.partials);
-    hipError_t e;
-    if (!tab_lds)   e = hr_launch<REALX, kHrBlockS, false>(t, gx, n_pass, lds, s);
-    else if (large) e = hr_launch<REALX, kHrBlockL, true>(t, gx, n_pass, lds, s);
-    else            e = hr_launch<REALX, kHrBlockS, true>(t, gx, n_pass, lds, s);
-    QBH_HIP_WHO(who, e);
-    return corr_finish(t.partials, gx, ncomp, comp, s);
+    const bool large = tab_lds && shape.large;                            // then one workgroup of 1024 lanes per CU
+    void (*kernel)(CorrHubRepr) = !tab_lds ? k_corr_hubrepr<REALX, kReprBlockS, false>
+                         : large  ? k_corr_hubrepr<REALX, kReprBlockL, true>
+                                  : k_corr_hubrepr<REALX, kReprBlockS, true>;
+    return corr_reduce_launch(who, kernel, shape.gx, hp.n_pass, NA, large ? kReprBlockL : kReprBlockS, lds, s, t, nullptr, pool,
+                              comp);
 }
 
 }  // namespace
@@ -342,10 +321,7 @@ extern "C" int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no
 {
     using namespace qbh;
     const char *who = "qbh_corr_hubbard_repr_dev";
-    if (!perms || !chars) {
-        set_error("%s: perms and chars must be given", who);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(repr_check_tables(who, perms, chars));
     if (n_sites < 1 || n_sites > 31) {
         set_error("%s: n_sites = %d (1 .. 31 allowed)", who, n_sites);
         return QBH_EINVAL;
@@ -354,18 +330,12 @@ extern "C" int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no
         set_error("%s: (n_up, n_dn) = (%d, %d) (0 .. n_sites allowed)", who, n_up, n_dn);
         return QBH_EINVAL;
     }
-    if (n_trans < 1 || n_trans > kReprMaxTrans) {
-        set_error("%s: n_trans = %d (1 .. %d allowed)", who, n_trans, kReprMaxTrans);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(repr_check_trans(who, n_trans));
     if (no_double != 0 && no_double != 1) {
         set_error("%s: no_double = %d (0 or 1 allowed)", who, no_double);
         return QBH_EINVAL;
     }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
     std::vector<HubReprDev> rr(1);
     HubReprDev &R = rr[0];
     std::vector<uint64_t> tab;
@@ -379,10 +349,7 @@ extern "C" int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no
     int64_t nstates = 0;
     std::vector<uint64_t> ctab;
     QBH_TRY(sector_words(R, ctab, &nstates, who));           // every refusal comes before the device is looked for
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites;
     const ReprClasses K = repr_classes(N, n_trans, perms);
     DevBufs bufs;
@@ -406,71 +373,46 @@ extern "C" int qbh_corr_hubbard_repr_dev(int n_sites, int n_up, int n_dn, int no
     t.xr = d_vec_re;
     const bool rx = d_vec_re != nullptr;
     std::vector<double> comp;
-    if (rx) QBH_TRY(corr_hubrepr_run<true>(who, t, K, tab.size(), nn != nullptr, hop != nullptr, flip != nullptr, comp, (hipStream_t)stream, bufs.pool));
-    else    QBH_TRY(corr_hubrepr_run<false>(who, t, K, tab.size(), nn != nullptr, hop != nullptr, flip != nullptr, comp, (hipStream_t)stream, bufs.pool));
+    CorrPasses hp;
+    if (rx) QBH_TRY(corr_hubrepr_run<true>(who, t, K, tab.size(), nn != nullptr, hop != nullptr, flip != nullptr, comp, hp, (hipStream_t)stream, bufs.pool));
+    else    QBH_TRY(corr_hubrepr_run<false>(who, t, K, tab.size(), nn != nullptr, hop != nullptr, flip != nullptr, comp, hp, (hipStream_t)stream, bufs.pool));
     constexpr int NA = kHrAcc, GN = kHrNN, GH = kHrGat, NS = kHrSite;
-    const int n_nn = (K.n_cls + GN - 1) / GN, n_gat = (K.n_cls + GH - 1) / GH;
-    // first pass of every kind, in the order of corr_hubrepr_run
-    const int p_nn = 0, p_hopu = nn ? n_nn : 0, p_hopd = p_hopu + (hop ? n_gat : 0), p_flip = p_hopd + (hop ? n_gat : 0);
-    const int p_site = p_flip + (flip ? n_gat : 0);
-    auto orbit_sum = [&](int o, int what) { return comp[(size_t)(p_site + o / NS) * NA + what * NS + o % NS]; };
-    const double n2 = comp[(size_t)p_site * NA + 3 * NS];
-    if (norm2) *norm2 = n2;
+    auto at = [&](int kind, int item, int per_pass, int slot) { return hp.at(comp, kind, item, per_pass, slot, NA); };
+    if (norm2) *norm2 = at(kHrKindSite, 0, NS, 3);
     if (dim_out) *dim_out = S.dim;
     std::vector<double> du((size_t)N), dd((size_t)N), dc((size_t)N);
     for (int i = 0; i < N; ++i) {
         const int o = K.orb[(size_t)i];
         const double n_s = (double)K.n_s[(size_t)o];
-        du[(size_t)i] = orbit_sum(o, 0) / n_s;
-        dd[(size_t)i] = orbit_sum(o, 1) / n_s;
-        dc[(size_t)i] = orbit_sum(o, 2) / n_s;
+        du[(size_t)i] = at(kHrKindSite, o, NS, 0) / n_s;
+        dd[(size_t)i] = at(kHrKindSite, o, NS, 1) / n_s;
+        dc[(size_t)i] = at(kHrKindSite, o, NS, 2) / n_s;
     }
     if (dens) {
         std::copy(du.begin(), du.end(), dens);
         std::copy(dd.begin(), dd.end(), dens + N);
     }
     const size_t NN = (size_t)N * N;
-    auto gathered = [&](int first_pass, int c, bool forward) {
-        const size_t at = (size_t)(first_pass + c / GH) * NA + c % GH;
-        const double two_nu = 2.0 * (double)K.nu[(size_t)c];
-        const double im = (rx || K.self[(size_t)c]) ? 0.0 : comp[at + GH] / two_nu;
-        return qbh_z{comp[at] / two_nu, forward ? im : -im};
-    };
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < N; ++j) {
             const size_t ij = (size_t)i * N + j;
             if (i == j) {
-                if (nn) {
-                    nn[ij] = du[(size_t)i];
-                    nn[NN + ij] = nn[2 * NN + ij] = dc[(size_t)i];
-                    nn[3 * NN + ij] = dd[(size_t)i];
-                }
-                if (hop) {
-                    hop[ij] = qbh_z{du[(size_t)i], 0.0};
-                    hop[NN + ij] = qbh_z{dd[(size_t)i], 0.0};
-                }
-                if (flip) flip[ij] = qbh_z{du[(size_t)i] - dc[(size_t)i], 0.0};
+                if (nn) corr_put_nn_diag(nn, N, i, du[(size_t)i], dc[(size_t)i], dd[(size_t)i]);
+                corr_put_onsite_diag(hop, flip, N, i, du[(size_t)i], dd[(size_t)i], dc[(size_t)i]);
                 continue;
             }
             const int c = K.cls[ij];
-            const bool forward = K.fwd[ij] != 0;
-            if (nn) {
-                const size_t at = (size_t)(p_nn + c / GN) * NA + c % GN;
-                const double n_u = (double)K.nu[(size_t)c];
-                const double f = comp[at + 2 * GN], b = comp[at + 3 * GN];
-                // <n_{i,up} n_{j,dn}> and, from the mirror orientation, <n_{i,dn} n_{j,up}> = <n_{j,up} n_{i,dn}>
-                const double ud = K.self[(size_t)c] ? f / (2.0 * n_u) : (forward ? f : b) / n_u;
-                const double du_ = K.self[(size_t)c] ? f / (2.0 * n_u) : (forward ? b : f) / n_u;
-                nn[ij] = comp[at] / n_u;
-                nn[NN + ij] = ud;
-                nn[2 * NN + ij] = du_;
-                nn[3 * NN + ij] = comp[at + GN] / n_u;
-            }
+            const bool forward = K.fwd[ij] != 0, self = K.self[(size_t)c] != 0;
+            const double n_u = (double)K.nu[(size_t)c];
+            auto gathered = [&](int kind) {
+                return repr_herm_value(at(kind, c, GH, 0), (rx || self) ? 0.0 : at(kind, c, GH, 1), 2.0 * n_u, forward);
+            };
+            if (nn) corr_put_nn_class(nn, N, i, j, at(kHrKindNN, c, GN, 0), at(kHrKindNN, c, GN, 1), at(kHrKindNN, c, GN, 2), at(kHrKindNN, c, GN, 3), n_u, self, forward);
             if (hop) {
-                hop[ij] = gathered(p_hopu, c, forward);
-                hop[NN + ij] = gathered(p_hopd, c, forward);
+                hop[ij] = gathered(kHrKindHopU);
+                hop[NN + ij] = gathered(kHrKindHopD);
             }
-            if (flip) flip[ij] = gathered(p_flip, c, forward);
+            if (flip) flip[ij] = gathered(kHrKindFlip);
         }
     return QBH_OK;
 }

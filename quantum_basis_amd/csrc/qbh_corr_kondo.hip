@@ -1,8 +1,8 @@
 // qbh_corr_kondo.hip -- all-pair static correlations of a resident state of the Kondo lattice (conduction electrons plus a local
 // spin-1/2 on every site; the sector (n_elec, two_sz) of qbh_gen_kondo / qbh_mf_kondo) in one pass over it: qbh_corr_kondo_dev.
-// The structure is that of qbh_corr.hip and qbh_corr_qudit.hip: a launch is a grid of (row blocks) x (passes), a pass owns a
-// fixed group of pairs or sites and a per-lane accumulator array indexed by compile-time constants only, the workgroups leave
-// their sums through corr_block_partials and k_corr_reduce adds them in a fixed order.  No atomics.
+// A launch is a grid of (row blocks) x (passes); a pass owns a fixed group of pairs or sites and a per-lane accumulator array
+// indexed by compile-time constants only.  The block reduction, the launch with its second stage
+// (corr_reduce_launch), the pass layout (CorrPasses) and the shared fills and checks are those of qbh_corr.hpp.  No atomics.
 //
 // One kernel instance per pass kind (a kind has registers of its own), one launch per kind that is asked for:
 //   DIAG  no gather, 32 accumulators; the pass's sub-kind is uniform over the workgroup:
@@ -21,9 +21,9 @@
 //                spins between the two sites only (their count of down spins above grows by one); no sign
 //           LE   S^+_i s^-_j: local spin i down, electron j up alone; the target lies in the block popcount(s) - 1, n_up - 1:
 //                kd_rank of all three fields; sign of s^-_j as in KondoSiteOp (op 5)
-// Rows: a workgroup takes tiles of 256 x kKcRows consecutive rows; a lane unranks one row (kd_unrank: a dependent LDS walk and a
-// 64-bit division) and steps to the next words with kc_next, the words go through LDS and come back row-interleaved (the scheme
-// of k_corr_spin).  kKcRows = 1 is re-unranking every row in every pass: 40 % slower for the whole call at 10 sites.
+// Rows: tiles of 256 x kKcRows consecutive rows (the scheme: qbh_corr.hpp); a lane unranks one row (kd_unrank: a dependent LDS walk and a
+// 64-bit division) and steps to the next words with kc_next.  kKcRows = 1 is re-unranking every row in every pass: 40 % slower
+// for the whole call at 10 sites.
 #include <algorithm>
 #include <vector>
 
@@ -150,9 +150,7 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_kondo(CorrKondo t)
         if (row >= t.dim) break;
         const uint64_t word = stage[(local / R) * (R + 1) + local % R];
         const uint32_t u = (uint32_t)word & fm, d = (uint32_t)(word >> n) & fm, s = (uint32_t)(word >> (2 * n));
-        d2 x = {0.0, 0.0};
-        if (REALX) x.x = t.xr[row];
-        else       x = t.xg[row];
+        const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
         if (KIND == kKcDiag) {
             const double w = fma(x.x, x.x, x.y * x.y);
             if (sub == kKcSite) {
@@ -285,26 +283,19 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_kondo(CorrKondo t)
     corr_block_partials<NA>(acc, red, t.partials);
 }
 
-struct KcPasses {
-    int first[kKcSubs], count[kKcSubs];          // the DIAG launch: per sub-kind the first pass and the number of passes
-    int hop_passes;                              // passes of one species in the HOP launch
-};
-
-template <bool REALX, int KIND>
-int corr_kondo_launch(const CorrKondo &t, int gx, int n_pass, hipStream_t s)
+template <int KIND>
+void (*kc_kernel(bool rx))(CorrKondo)
 {
-    QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_kondo<REALX, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kCorrKondoLds));
-    hipLaunchKernelGGL((k_corr_kondo<REALX, KIND>), dim3(gx, n_pass), dim3(kCorrBlock), kCorrKondoLds, s, t);
-    QBH_HIP(hipGetLastError());
-    return QBH_OK;
+    return rx ? k_corr_kondo<true, KIND> : k_corr_kondo<false, KIND>;
 }
 
-// comp[kind]: the sums of the kind's passes in pass order (empty for a kind that was not asked for)
-int corr_kondo_run(const KondoDev &K, const d2 *xg, const double *xr, const bool want_sub[kKcSubs], const bool want_kind[kKcKinds],
-                   std::vector<double> comp[kKcKinds], KcPasses &kp, hipStream_t s, std::vector<void *> &pool)
+// comp[kind]: the sums of the kind's passes in pass order (empty for a kind that was not asked for); dp: the sub-kinds of the
+// DIAG launch, hp: the two species of the HOP launch
+int corr_kondo_run(const char *who, const KondoDev &K, const d2 *xg, const double *xr, const bool want_sub[kKcSubs],
+                   const bool want_kind[kKcKinds], std::vector<double> comp[kKcKinds], CorrPasses &dp, CorrPasses &hp, hipStream_t s,
+                   std::vector<void *> &pool)
 {
-    const int N = K.n_sites;
+    const int N = K.n_sites, n_pairs = N * (N - 1) / 2;
     std::vector<uint32_t> item[kKcKinds];
     auto close_pass = [](std::vector<uint32_t> &v) { v.resize((v.size() + kKcItems - 1) / kKcItems * kKcItems, 0u); };
     auto pairs = [&](std::vector<uint32_t> &v, int per_pass, uint32_t sub) {
@@ -320,7 +311,7 @@ int corr_kondo_run(const KondoDev &K, const d2 *xg, const double *xr, const bool
         std::vector<uint32_t> &v = item[kKcDiag];
         const int per[kKcSubs] = {kKcSites, kKcQuads, kKcQuads, kKcItems};
         for (int sub = 0; sub < kKcSubs; ++sub) {
-            kp.first[sub] = (int)(v.size() / kKcItems);
+            dp.add(sub, sub == kKcSite ? N : want_sub[sub] ? n_pairs : 0, per[sub]);
             if (sub == kKcSite) {
                 for (int i = 0; i < N; ++i) {
                     v.push_back(kKcValid | (uint32_t)i | ((uint32_t)sub << 16));
@@ -330,13 +321,16 @@ int corr_kondo_run(const KondoDev &K, const d2 *xg, const double *xr, const bool
             } else if (want_sub[sub]) {
                 pairs(v, per[sub], (uint32_t)sub);
             }
-            kp.count[sub] = (int)(v.size() / kKcItems) - kp.first[sub];
         }
     }
-    if (want_kind[kKcHop]) {
-        pairs(item[kKcHop], kKcGroup, 0u);
-        kp.hop_passes = (int)(item[kKcHop].size() / kKcItems);
-        pairs(item[kKcHop], kKcGroup, 1u);
+    if (want_kind[kKcHop])
+        for (int species = 0; species < 2; ++species) {
+            hp.add(species, n_pairs, kKcGroup);
+            pairs(item[kKcHop], kKcGroup, (uint32_t)species);
+        }
+    if ((int)(item[kKcDiag].size() / kKcItems) != dp.n_pass || (int)(item[kKcHop].size() / kKcItems) != hp.n_pass) {
+        set_error("%s: internal: the pass layout and the item lists disagree", who);
+        return QBH_EHIP;
     }
     if (want_kind[kKcEE]) pairs(item[kKcEE], kKcGroup, 0u);
     if (want_kind[kKcLL]) pairs(item[kKcLL], kKcGroup, 0u);
@@ -370,18 +364,9 @@ int corr_kondo_run(const KondoDev &K, const d2 *xg, const double *xr, const bool
         uint32_t *d_item = nullptr;
         QBH_TRY(upload(item[k], &d_item, pool));
         t.item = d_item;
-        QBH_HIP(qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * n_pass * NA * sizeof(double)));
-        pool.push_back(t.partials);
-        int rc = QBH_OK;
-        switch (k) {
-        case kKcDiag: rc = rx ? corr_kondo_launch<true, kKcDiag>(t, gx, n_pass, s) : corr_kondo_launch<false, kKcDiag>(t, gx, n_pass, s); break;
-        case kKcHop:  rc = rx ? corr_kondo_launch<true, kKcHop>(t, gx, n_pass, s) : corr_kondo_launch<false, kKcHop>(t, gx, n_pass, s); break;
-        case kKcEE:   rc = rx ? corr_kondo_launch<true, kKcEE>(t, gx, n_pass, s) : corr_kondo_launch<false, kKcEE>(t, gx, n_pass, s); break;
-        case kKcLL:   rc = rx ? corr_kondo_launch<true, kKcLL>(t, gx, n_pass, s) : corr_kondo_launch<false, kKcLL>(t, gx, n_pass, s); break;
-        default:      rc = rx ? corr_kondo_launch<true, kKcLE>(t, gx, n_pass, s) : corr_kondo_launch<false, kKcLE>(t, gx, n_pass, s); break;
-        }
-        QBH_TRY(rc);
-        QBH_TRY(corr_finish(t.partials, gx, n_pass * NA, comp[k], s));
+        void (*kernel)(CorrKondo) = k == kKcDiag ? kc_kernel<kKcDiag>(rx) : k == kKcHop ? kc_kernel<kKcHop>(rx) : k == kKcEE ? kc_kernel<kKcEE>(rx)
+                             : k == kKcLL ? kc_kernel<kKcLL>(rx) : kc_kernel<kKcLE>(rx);
+        QBH_TRY(corr_reduce_launch(who, kernel, gx, n_pass, NA, kCorrBlock, kCorrKondoLds, s, t, nullptr, pool, comp[k]));
     }
     return QBH_OK;
 }
@@ -397,37 +382,32 @@ extern "C" int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh
     std::vector<KondoDev> Kv(1);
     KondoDev &K = Kv[0];
     QBH_TRY(kondo_shape(who, n_sites, n_elec, two_sz, K));         // the shape (QBH_EINVAL), then an empty sector (QBH_EUNSUPP)
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
-        return QBH_EINVAL;
-    }
-    if (norm2 == nullptr) {
-        set_error("%s: norm2 is NULL", who);
-        return QBH_EINVAL;
-    }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
+    QBH_TRY(corr_check_norm2(who, norm2));
+    QBH_TRY(corr_check_device());
     const int N = n_sites, G = kKcGroup;
     const size_t NN = (size_t)N * N;
     const bool want_sub[kKcSubs] = {true, nn != nullptr, zn != nullptr, zz != nullptr};
     const bool want_kind[kKcKinds] = {true, hop != nullptr, ee != nullptr, ll != nullptr, le != nullptr};
     std::vector<void *> pool;
     std::vector<double> comp[kKcKinds];
-    KcPasses kp{};
-    const int rc = corr_kondo_run(K, reinterpret_cast<const d2 *>(d_vec), d_vec_re, want_sub, want_kind, comp, kp, (hipStream_t)stream, pool);
+    CorrPasses dp, hp;
+    const CorrPasses lone;                                         // the layout of a launch of one kind: its passes begin at 0
+    const int rc = corr_kondo_run(who, K, reinterpret_cast<const d2 *>(d_vec), d_vec_re, want_sub, want_kind, comp, dp, hp,
+                                  (hipStream_t)stream, pool);
     free_pool(pool);
     if (rc != QBH_OK) return rc;
     const bool rx = d_vec_re != nullptr;
     const int NG = (rx ? 1 : 2) * G;                               // accumulators of a gathered pass
-    auto diag = [&](int sub, int pass, int slot) { return comp[kKcDiag][(size_t)(kp.first[sub] + pass) * 32 + slot]; };
-    auto site_v = [&](int i, int c) { return diag(kKcSite, i / kKcSites, 6 * (i % kKcSites) + c); };
-    auto gathered = [&](int kind, int pass0, int q) {
-        const size_t c = (size_t)(pass0 + q / G) * NG + q % G;
-        return qbh_z{comp[kind][c], rx ? 0.0 : comp[kind][c + G]};
+    auto diag = [&](int sub, int item, int per_pass, int per_item, int slot) {
+        return dp.at_item(comp[kKcDiag], sub, item, per_pass, per_item, slot, 32);
     };
-    const double n2 = diag(kKcSite, 0, 30);
+    auto site_v = [&](int i, int c) { return diag(kKcSite, i, kKcSites, 6, c); };
+    // part: the species in the HOP launch (layout hp), 0 in the launches of one kind (layout lone)
+    auto gathered = [&](const CorrPasses &lay, int kind, int part, int q) {
+        return qbh_z{lay.at(comp[kind], part, q, G, 0, NG), rx ? 0.0 : lay.at(comp[kind], part, q, G, 1, NG)};
+    };
+    const double n2 = site_v(0, 30);
     *norm2 = n2;
     int q = 0;
     for (int i = 0; i < N; ++i) {
@@ -439,54 +419,38 @@ extern "C" int qbh_corr_kondo_dev(int n_sites, int n_elec, int two_sz, const qbh
             site[2 * N + i] = docc;
             site[3 * N + i] = sz;
         }
-        if (nn) {
-            nn[0 * NN + ii] = nu;                                  // n^2 = n
-            nn[1 * NN + ii] = docc;
-            nn[2 * NN + ii] = docc;
-            nn[3 * NN + ii] = nd;
-        }
+        if (nn) corr_put_nn_diag(nn, N, i, nu, docc, nd);
         if (zn) {
             zn[0 * NN + ii] = site_v(i, 4);
             zn[1 * NN + ii] = site_v(i, 5);
         }
         if (zz) zz[ii] = 0.25 * n2;
-        if (hop) {
-            hop[0 * NN + ii] = qbh_z{nu, 0.0};
-            hop[1 * NN + ii] = qbh_z{nd, 0.0};
-        }
-        if (ee) ee[ii] = qbh_z{nu - docc, 0.0};
+        corr_put_onsite_diag(hop, ee, N, i, nu, nd, docc);
         if (ll) ll[ii] = qbh_z{0.5 * n2 + sz, 0.0};
         for (int j = i + 1; j < N; ++j, ++q) {
             const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
-            if (nn) {
-                const int p = q / kKcQuads, c = 4 * (q % kKcQuads);
-                nn[0 * NN + ij] = nn[0 * NN + ji] = diag(kKcNN, p, c + 0);
-                nn[1 * NN + ij] = nn[2 * NN + ji] = diag(kKcNN, p, c + 1);       // <n_{i,up} n_{j,dn}> = the du entry of (j, i)
-                nn[2 * NN + ij] = nn[1 * NN + ji] = diag(kKcNN, p, c + 2);
-                nn[3 * NN + ij] = nn[3 * NN + ji] = diag(kKcNN, p, c + 3);
-            }
+            auto quad = [&](int sub, int c) { return diag(sub, q, kKcQuads, 4, c); };
+            if (nn) corr_put_nn_pair(nn, N, i, j, quad(kKcNN, 0), quad(kKcNN, 1), quad(kKcNN, 2), quad(kKcNN, 3));
             if (zn) {
-                const int p = q / kKcQuads, c = 4 * (q % kKcQuads);
-                zn[0 * NN + ij] = diag(kKcZN, p, c + 0);
-                zn[1 * NN + ij] = diag(kKcZN, p, c + 1);
-                zn[0 * NN + ji] = diag(kKcZN, p, c + 2);
-                zn[1 * NN + ji] = diag(kKcZN, p, c + 3);
+                zn[0 * NN + ij] = quad(kKcZN, 0);
+                zn[1 * NN + ij] = quad(kKcZN, 1);
+                zn[0 * NN + ji] = quad(kKcZN, 2);
+                zn[1 * NN + ji] = quad(kKcZN, 3);
             }
-            if (zz) zz[ij] = zz[ji] = 0.25 * (n2 - 2.0 * diag(kKcZZ, q / kKcItems, q % kKcItems));
-            auto herm = [&](qbh_z *out, int kind, int pass0) {
-                const qbh_z v = gathered(kind, pass0, q);
-                out[ij] = v;
-                out[ji] = qbh_z{v.re, -v.im};
+            if (zz) zz[ij] = zz[ji] = corr_zz_pair(n2, dp.at(comp[kKcDiag], kKcZZ, q, kKcItems, 0, 32));
+            auto herm = [&](qbh_z *out, const CorrPasses &lay, int kind, int part) {
+                const qbh_z v = gathered(lay, kind, part, q);
+                corr_put_herm(out, N, i, j, v.re, v.im);
             };
             if (hop) {
-                herm(hop, kKcHop, 0);
-                herm(hop + NN, kKcHop, kp.hop_passes);
+                herm(hop, hp, kKcHop, 0);
+                herm(hop + NN, hp, kKcHop, 1);
             }
-            if (ee) herm(ee, kKcEE, 0);
-            if (ll) herm(ll, kKcLL, 0);
+            if (ee) herm(ee, lone, kKcEE, 0);
+            if (ll) herm(ll, lone, kKcLL, 0);
         }
     }
     if (le)
-        for (int k = 0; k < N * N; ++k) le[k] = gathered(kKcLE, 0, k);
+        for (int k = 0; k < N * N; ++k) le[k] = gathered(lone, kKcLE, 0, k);
     return QBH_OK;
 }

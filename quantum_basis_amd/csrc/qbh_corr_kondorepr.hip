@@ -45,8 +45,8 @@
 //   HOP (species uniform per pass), EE, LL  8 classes:  [g] Re C, [8+g] Im C (complex vectors only)
 //   LE    8 ordered orbits:  [g] Re L, [8+g] Im L
 // A group that is not asked for has no passes and no launch, so the other outputs keep their bits.  Every workgroup leaves its
-// sums at partials[blockIdx.x][pass][accumulator] (repr_block_partials) and k_corr_reduce adds the workgroups in a fixed order
-// (corr_finish): no atomics, two calls return the same bits.
+// sums at partials[blockIdx.x][pass][accumulator] (corr_block_partials) and k_corr_reduce adds the workgroups in a fixed order
+// (corr_reduce_launch): no atomics, two calls return the same bits.
 //
 // Tables.  Translation tables, A, binom, characters and permutation bytes are dynamic LDS: at most 138,816 + 1024 + 1344 B =
 // 141,184 B (64 translations of 21 sites) <= kCorrLdsCap, so there is no global-memory table path.  The footprint chooses between
@@ -71,8 +71,8 @@
 
 #include "qbh_kondo_lds.hpp"                                 // qbh_sector.hpp, kKondoTabEntries, kMfKreprLdsMax
 #include "qbh_device.hpp"
-#include "qbh_corr.hpp"                                      // kCorrLdsCap, corr_uniform, corr_finish
-#include "qbh_corr_repr.hpp"                                 // repr_classes, repr_ordered_orbits, repr_block_partials
+#include "qbh_corr.hpp"                                      // device helpers, launch path, pass layout and host fills
+#include "qbh_corr_repr.hpp"                                 // classes and orbits of site pairs, symmetry checks
 
 namespace qbh {
 namespace {
@@ -137,16 +137,13 @@ __global__ __launch_bounds__(BLOCK) void k_corr_kondorepr(CorrKondoRepr t)
         const int32_t *start = KIND == kKrLE ? t.orb_start : t.cls_start;
         const uint32_t *plist = KIND == kKrLE ? t.opairs : t.pairs;
         int k0[GH + 1];
-#pragma unroll
-        for (int g = 0; g <= GH; ++g) k0[g] = (int)corr_uniform((uint32_t)start[lp * GH + g]);
+        corr_group_bounds<GH>(start, lp * GH, k0);
         for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
             const uint8_t ci = t.info[row];
             if (ci & 0x80) continue;                                          // zero norm at this momentum: its entry is never read
             const uint64_t a = t.reps[row], au = a & mlow, ad = (a >> n) & mlow, as = a >> (2 * n);
             const double sa = (double)(ci & 0x7f);
-            d2 x = {0.0, 0.0};
-            if (REALX) x.x = t.xr[row];
-            else       x = t.xg[row];
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
 #pragma unroll
             for (int g = 0; g < GH; ++g) {
                 double sr = 0.0, si = 0.0;
@@ -238,9 +235,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_kondorepr(CorrKondoRepr t)
             for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
                 if (t.info[row] & 0x80) continue;
                 const uint64_t a = t.reps[row], au = a & mlow, ad = (a >> n) & mlow, as = a >> (2 * n);
-                d2 x = {0.0, 0.0};
-                if (REALX) x.x = t.xr[row];
-                else       x = t.xg[row];
+                const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
                 const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
                 for (int g = 0; g < NS; ++g) {
@@ -254,14 +249,11 @@ __global__ __launch_bounds__(BLOCK) void k_corr_kondorepr(CorrKondoRepr t)
         } else if (sub == kKrSubNN) {
             constexpr int GN = kKrNN;
             int k0[GN + 1];
-#pragma unroll
-            for (int g = 0; g <= GN; ++g) k0[g] = (int)corr_uniform((uint32_t)t.cls_start[lp * GN + g]);
+            corr_group_bounds<GN>(t.cls_start, lp * GN, k0);
             for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
                 if (t.info[row] & 0x80) continue;
                 const uint64_t a = t.reps[row], au = a & mlow, ad = (a >> n) & mlow;
-                d2 x = {0.0, 0.0};
-                if (REALX) x.x = t.xr[row];
-                else       x = t.xg[row];
+                const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
                 const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
                 for (int g = 0; g < GN; ++g) {
@@ -288,14 +280,11 @@ __global__ __launch_bounds__(BLOCK) void k_corr_kondorepr(CorrKondoRepr t)
         } else if (sub == kKrSubZN) {
             constexpr int GZ = kKrZN;
             int k0[GZ + 1];
-#pragma unroll
-            for (int g = 0; g <= GZ; ++g) k0[g] = (int)corr_uniform((uint32_t)t.orb_start[lp * GZ + g]);
+            corr_group_bounds<GZ>(t.orb_start, lp * GZ, k0);
             for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
                 if (t.info[row] & 0x80) continue;
                 const uint64_t a = t.reps[row], au = a & mlow, ad = (a >> n) & mlow, as = a >> (2 * n);
-                d2 x = {0.0, 0.0};
-                if (REALX) x.x = t.xr[row];
-                else       x = t.xg[row];
+                const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
                 const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
                 for (int g = 0; g < GZ; ++g) {
@@ -315,14 +304,11 @@ __global__ __launch_bounds__(BLOCK) void k_corr_kondorepr(CorrKondoRepr t)
         } else {
             constexpr int GZ = kKrZZ;
             int k0[GZ + 1];
-#pragma unroll
-            for (int g = 0; g <= GZ; ++g) k0[g] = (int)corr_uniform((uint32_t)t.cls_start[lp * GZ + g]);
+            corr_group_bounds<GZ>(t.cls_start, lp * GZ, k0);
             for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
                 if (t.info[row] & 0x80) continue;
                 const uint64_t as = t.reps[row] >> (2 * n);
-                d2 x = {0.0, 0.0};
-                if (REALX) x.x = t.xr[row];
-                else       x = t.xg[row];
+                const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
                 const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
                 for (int g = 0; g < GZ; ++g) {
@@ -337,7 +323,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_kondorepr(CorrKondoRepr t)
             }
         }
     }
-    repr_block_partials<NA, BLOCK>(acc, red, t.partials);
+    corr_block_partials<NA, BLOCK>(acc, red, t.partials);
 }
 
 // ------------------------------------------------------------------------------------------------------ host side --
@@ -347,56 +333,36 @@ size_t kr_lds_bytes(int n_sites, int n_trans, size_t n_tab)
     return (n_tab + 2 * (size_t)kKondoTabEntries + 2 * (size_t)n_trans + ((size_t)n_trans * n_sites + 7) / 8) * 8;
 }
 
-template <bool REALX, int BLOCK, int KIND>
-hipError_t kr_launch_one(const CorrKondoRepr &t, int gx, int n_pass, size_t lds, hipStream_t s)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_kondorepr<REALX, BLOCK, KIND>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_corr_kondorepr<REALX, BLOCK, KIND>), dim3(gx, n_pass), dim3(BLOCK), lds, s, t);
-    return hipGetLastError();
-}
-
 template <bool REALX, int KIND>
-hipError_t kr_launch(const CorrKondoRepr &t, const ReprShape &shape, int n_pass, size_t lds, hipStream_t s)
+void (*kr_kernel(bool large))(CorrKondoRepr)
 {
-    return shape.large ? kr_launch_one<REALX, kReprBlockL, KIND>(t, shape.gx, n_pass, lds, s)
-                       : kr_launch_one<REALX, kReprBlockS, KIND>(t, shape.gx, n_pass, lds, s);
+    return large ? k_corr_kondorepr<REALX, kReprBlockL, KIND>
+                 : k_corr_kondorepr<REALX, kReprBlockS, KIND>;
 }
 
-struct KrPasses {
-    int n_pass[kKrKinds];                                    // passes of every launch (0: no launch)
-    int first[kKrSubs];                                      // DIAG: the first pass of every sub-kind
-    int n_gat;                                               // passes of one Hermitian gathered group
-};
-
-// one launch and one two-stage reduction per kind that is asked for: comp[kind][pass * kKrAcc + accumulator]
+// one launch and one two-stage reduction per kind that is asked for: comp[kind][pass * kKrAcc + accumulator]; dp: the sub-kinds
+// of the DIAG launch, hp: the two species of the HOP launch
 template <bool REALX>
 int corr_kondorepr_run(const char *who, CorrKondoRepr t, const ReprClasses &K, const ReprOrbits &O, const bool want_sub[kKrSubs],
-                       const bool want_kind[kKrKinds], std::vector<double> comp[kKrKinds], KrPasses &kp, hipStream_t s,
+                       const bool want_kind[kKrKinds], std::vector<double> comp[kKrKinds], CorrPasses &dp, CorrPasses &hp, hipStream_t s,
                        std::vector<void *> &pool)
 {
     constexpr int NA = kKrAcc;
-    auto ceil_div = [](int a, int b) { return (a + b - 1) / b; };
-    const int n_site = ceil_div(K.n_orb, kKrSite);
-    const int per_sub[kKrSubs] = {n_site, want_sub[kKrSubNN] ? ceil_div(K.n_cls, kKrNN) : 0, want_sub[kKrSubZN] ? ceil_div(O.n_orb, kKrZN) : 0,
-                                  want_sub[kKrSubZZ] ? ceil_div(K.n_cls, kKrZZ) : 0};
-    int n_diag = 0;
-    for (int k = 0; k < kKrSubs; ++k) {
-        kp.first[k] = n_diag;
-        t.sub_end[k] = n_diag += per_sub[k];
-    }
-    kp.n_gat = ceil_div(K.n_cls, kKrGat);
-    t.hop_passes = kp.n_gat;
-    kp.n_pass[kKrDiag] = n_diag;
-    kp.n_pass[kKrHop] = want_kind[kKrHop] ? 2 * kp.n_gat : 0;
-    kp.n_pass[kKrEE] = want_kind[kKrEE] ? kp.n_gat : 0;
-    kp.n_pass[kKrLL] = want_kind[kKrLL] ? kp.n_gat : 0;
-    kp.n_pass[kKrLE] = want_kind[kKrLE] ? ceil_div(O.n_orb, kKrGat) : 0;
+    dp.add(kKrSubSite, K.n_orb, kKrSite);
+    dp.add(kKrSubNN, want_sub[kKrSubNN] ? K.n_cls : 0, kKrNN);
+    dp.add(kKrSubZN, want_sub[kKrSubZN] ? O.n_orb : 0, kKrZN);
+    dp.add(kKrSubZZ, want_sub[kKrSubZZ] ? K.n_cls : 0, kKrZZ);
+    for (int k = 0; k < kKrSubs; ++k) t.sub_end[k] = dp.first[k] + dp.count[k];
+    const int n_site = dp.count[kKrSubSite], n_gat = (K.n_cls + kKrGat - 1) / kKrGat;     // passes of one Hermitian gathered group
+    if (want_kind[kKrHop])
+        for (int species = 0; species < 2; ++species) hp.add(species, K.n_cls, kKrGat);
+    t.hop_passes = n_gat;
+    const int n_passes[kKrKinds] = {dp.n_pass, want_kind[kKrHop] ? 2 * n_gat : 0, want_kind[kKrEE] ? n_gat : 0,
+                                    want_kind[kKrLL] ? n_gat : 0, want_kind[kKrLE] ? (O.n_orb + kKrGat - 1) / kKrGat : 0};
     std::vector<int32_t> cls_start, orb_start;
     std::vector<uint32_t> pairs, opairs;
-    repr_flatten_classes(K, NA, cls_start, pairs);
-    repr_flatten_orbits(O, NA, orb_start, opairs);
+    repr_flatten(K.pairs, NA, cls_start, pairs);
+    repr_flatten(O.pairs, NA, orb_start, opairs);
     std::vector<uint64_t> site_mask((size_t)n_site * kKrSite, 0ULL);
     std::copy(K.mask.begin(), K.mask.end(), site_mask.begin());
     int32_t *d_cstart = nullptr, *d_ostart = nullptr;
@@ -420,21 +386,12 @@ int corr_kondorepr_run(const char *who, CorrKondoRepr t, const ReprClasses &K, c
     const ReprShape shape = repr_launch_shape(lds, t.dim);   // one shape for every kind: the DIAG launch stages nothing, but
     for (int k = 0; k < kKrKinds; ++k) {                     // its grid along x does not depend on what is asked for
         comp[k].clear();
-        const int n_pass = kp.n_pass[k];
-        if (n_pass == 0) continue;
-        const int ncomp = n_pass * NA;
-        QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, ((size_t)shape.gx + 1) * ncomp * sizeof(double)));
-        pool.push_back(t.partials);
-        hipError_t e;
-        switch (k) {
-        case kKrDiag: e = kr_launch<REALX, kKrDiag>(t, shape, n_pass, 0, s); break;
-        case kKrHop:  e = kr_launch<REALX, kKrHop>(t, shape, n_pass, lds, s); break;
-        case kKrEE:   e = kr_launch<REALX, kKrEE>(t, shape, n_pass, lds, s); break;
-        case kKrLL:   e = kr_launch<REALX, kKrLL>(t, shape, n_pass, lds, s); break;
-        default:      e = kr_launch<REALX, kKrLE>(t, shape, n_pass, lds, s); break;
-        }
-        QBH_HIP_WHO(who, e);
-        QBH_TRY(corr_finish(t.partials, shape.gx, ncomp, comp[k], s));
+        if (n_passes[k] == 0) continue;
+        void (*kernel)(CorrKondoRepr) = k == kKrDiag ? kr_kernel<REALX, kKrDiag>(shape.large) : k == kKrHop ? kr_kernel<REALX, kKrHop>(shape.large)
+                             : k == kKrEE ? kr_kernel<REALX, kKrEE>(shape.large) : k == kKrLL    ? kr_kernel<REALX, kKrLL>(shape.large)
+                                                                                                : kr_kernel<REALX, kKrLE>(shape.large);
+        QBH_TRY(corr_reduce_launch(who, kernel, shape.gx, n_passes[k], NA, shape.block, k == kKrDiag ? 0 : lds, s, t, nullptr, pool,
+                                   comp[k]));
     }
     return QBH_OK;
 }
@@ -457,36 +414,21 @@ extern "C" int qbh_corr_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int 
 {
     using namespace qbh;
     const char *who = "qbh_corr_kondo_repr_dev";
-    if (!perms || !chars) {
-        set_error("%s: perms and chars must be given", who);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(repr_check_tables(who, perms, chars));
     std::vector<KondoReprDev> rr(1);
     memset(rr.data(), 0, sizeof(KondoReprDev));
     KondoReprDev &R = rr[0];
     QBH_TRY(kondo_shape(who, n_sites, n_elec, two_sz, R.k));           // the shape (QBH_EINVAL), then an empty sector (QBH_EUNSUPP)
-    if (n_trans < 1 || n_trans > kReprMaxTrans) {
-        set_error("%s: n_trans = %d (1 .. %d allowed)", who, n_trans, kReprMaxTrans);
-        return QBH_EINVAL;
-    }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
-        return QBH_EINVAL;
-    }
-    if (norm2 == nullptr) {
-        set_error("%s: norm2 is NULL", who);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(repr_check_trans(who, n_trans));
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
+    QBH_TRY(corr_check_norm2(who, norm2));
     std::vector<uint64_t> tab;
     QBH_TRY(kondo_symmetry(R, tab, n_trans, perms, chars, who));
     if (d_vec_re != nullptr) QBH_TRY(repr_real_characters(who, R.chr, n_trans));
     int64_t nstates = 0;
     std::vector<uint64_t> ctab;
     QBH_TRY(sector_words(R, ctab, &nstates, who));           // every refusal comes before the device is looked for
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites;
     const ReprClasses K = repr_classes(N, n_trans, perms);
     const ReprOrbits O = repr_ordered_orbits(N, n_trans, perms);
@@ -511,23 +453,23 @@ extern "C" int qbh_corr_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int 
     const bool want_sub[kKrSubs] = {true, nn != nullptr, zn != nullptr, zz != nullptr};
     const bool want_kind[kKrKinds] = {true, hop != nullptr, ee != nullptr, ll != nullptr, le != nullptr};
     std::vector<double> comp[kKrKinds];
-    KrPasses kp{};
-    if (rx) QBH_TRY(corr_kondorepr_run<true>(who, t, K, O, want_sub, want_kind, comp, kp, (hipStream_t)stream, bufs.pool));
-    else    QBH_TRY(corr_kondorepr_run<false>(who, t, K, O, want_sub, want_kind, comp, kp, (hipStream_t)stream, bufs.pool));
+    CorrPasses dp, hp;
+    const CorrPasses lone;                                   // the layout of a launch of one kind: its passes begin at 0
+    if (rx) QBH_TRY(corr_kondorepr_run<true>(who, t, K, O, want_sub, want_kind, comp, dp, hp, (hipStream_t)stream, bufs.pool));
+    else    QBH_TRY(corr_kondorepr_run<false>(who, t, K, O, want_sub, want_kind, comp, dp, hp, (hipStream_t)stream, bufs.pool));
     constexpr int NA = kKrAcc, GH = kKrGat;
-    auto diag = [&](int sub, int pass, int slot) { return comp[kKrDiag][(size_t)(kp.first[sub] + pass) * NA + slot]; };
-    auto orbit_sum = [&](int o, int what) { return diag(kKrSubSite, o / kKrSite, what * kKrSite + o % kKrSite); };
-    const double n2 = diag(kKrSubSite, 0, NA - 1);
+    auto diag = [&](int sub, int item, int per_pass, int slot) { return dp.at(comp[kKrDiag], sub, item, per_pass, slot, NA); };
+    const double n2 = diag(kKrSubSite, 0, kKrSite, 5);
     *norm2 = n2;
     if (dim_out) *dim_out = S.dim;
     std::vector<double> nu((size_t)N), nd((size_t)N), dc((size_t)N), sz((size_t)N);
     for (int i = 0; i < N; ++i) {
         const int o = K.orb[(size_t)i];
         const double n_s = (double)K.n_s[(size_t)o];
-        nu[(size_t)i] = orbit_sum(o, 0) / n_s;
-        nd[(size_t)i] = orbit_sum(o, 1) / n_s;
-        dc[(size_t)i] = orbit_sum(o, 2) / n_s;
-        sz[(size_t)i] = orbit_sum(o, 3) / (2.0 * n_s);
+        nu[(size_t)i] = diag(kKrSubSite, o, kKrSite, 0) / n_s;
+        nd[(size_t)i] = diag(kKrSubSite, o, kKrSite, 1) / n_s;
+        dc[(size_t)i] = diag(kKrSubSite, o, kKrSite, 2) / n_s;
+        sz[(size_t)i] = diag(kKrSubSite, o, kKrSite, 3) / (2.0 * n_s);
     }
     if (site) {
         std::copy(nu.begin(), nu.end(), site);
@@ -536,60 +478,39 @@ extern "C" int qbh_corr_kondo_repr_dev(int n_sites, int n_elec, int two_sz, int 
         std::copy(sz.begin(), sz.end(), site + 3 * N);
     }
     const size_t NN = (size_t)N * N;
-    // a Hermitian gathered group: C / (2 n_u), conjugated for a backward pair, real for a class that is its own mirror
-    auto gathered = [&](int kind, int first_pass, int c, bool forward) {
-        const size_t at = (size_t)(first_pass + c / GH) * NA + c % GH;
-        const double two_nu = 2.0 * (double)K.nu[(size_t)c];
-        const double im = (rx || K.self[(size_t)c]) ? 0.0 : comp[kind][at + GH] / two_nu;
-        return qbh_z{comp[kind][at] / two_nu, forward ? im : -im};
-    };
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < N; ++j) {
             const size_t ij = (size_t)i * N + j;
             const int o = O.orb[ij];
             const double n_o = (double)O.size[(size_t)o];
             if (zn) {
-                zn[ij] = diag(kKrSubZN, o / kKrZN, o % kKrZN) / (2.0 * n_o);
-                zn[NN + ij] = diag(kKrSubZN, o / kKrZN, kKrZN + o % kKrZN) / (2.0 * n_o);
+                zn[ij] = diag(kKrSubZN, o, kKrZN, 0) / (2.0 * n_o);
+                zn[NN + ij] = diag(kKrSubZN, o, kKrZN, 1) / (2.0 * n_o);
             }
-            if (le) {
-                const size_t at = (size_t)(o / GH) * NA + o % GH;
-                le[ij] = qbh_z{comp[kKrLE][at] / n_o, rx ? 0.0 : comp[kKrLE][at + GH] / n_o};
-            }
+            if (le) le[ij] = qbh_z{lone.at(comp[kKrLE], 0, o, GH, 0, NA) / n_o, rx ? 0.0 : lone.at(comp[kKrLE], 0, o, GH, 1, NA) / n_o};
             if (i == j) {
-                if (nn) {
-                    nn[ij] = nu[(size_t)i];                                   // n^2 = n
-                    nn[NN + ij] = nn[2 * NN + ij] = dc[(size_t)i];
-                    nn[3 * NN + ij] = nd[(size_t)i];
-                }
+                if (nn) corr_put_nn_diag(nn, N, i, nu[(size_t)i], dc[(size_t)i], nd[(size_t)i]);
                 if (zz) zz[ij] = 0.25 * n2;
-                if (hop) {
-                    hop[ij] = qbh_z{nu[(size_t)i], 0.0};
-                    hop[NN + ij] = qbh_z{nd[(size_t)i], 0.0};
-                }
-                if (ee) ee[ij] = qbh_z{nu[(size_t)i] - dc[(size_t)i], 0.0};
+                corr_put_onsite_diag(hop, ee, N, i, nu[(size_t)i], nd[(size_t)i], dc[(size_t)i]);
                 if (ll) ll[ij] = qbh_z{0.5 * n2 + sz[(size_t)i], 0.0};
                 continue;
             }
             const int c = K.cls[ij];
             const bool forward = K.fwd[ij] != 0, self = K.self[(size_t)c] != 0;
             const double n_u = (double)K.nu[(size_t)c];
-            if (nn) {
-                const int p = c / kKrNN, g = c % kKrNN;
-                const double f = diag(kKrSubNN, p, 2 * kKrNN + g), b = diag(kKrSubNN, p, 3 * kKrNN + g);
-                // <n_{i,up} n_{j,dn}> and, from the mirror orientation, <n_{i,dn} n_{j,up}> = <n_{j,up} n_{i,dn}>
-                nn[ij] = diag(kKrSubNN, p, g) / n_u;
-                nn[NN + ij] = self ? f / (2.0 * n_u) : (forward ? f : b) / n_u;
-                nn[2 * NN + ij] = self ? f / (2.0 * n_u) : (forward ? b : f) / n_u;
-                nn[3 * NN + ij] = diag(kKrSubNN, p, kKrNN + g) / n_u;
-            }
-            if (zz) zz[ij] = diag(kKrSubZZ, c / kKrZZ, c % kKrZZ) / (4.0 * n_u);
+            // a Hermitian gathered group; part: the species in the HOP launch (layout hp), 0 in a launch of one kind (layout lone)
+            auto gathered = [&](const CorrPasses &lay, int kind, int part) {
+                return repr_herm_value(lay.at(comp[kind], part, c, GH, 0, NA), (rx || self) ? 0.0 : lay.at(comp[kind], part, c, GH, 1, NA),
+                                       2.0 * n_u, forward);
+            };
+            if (nn) corr_put_nn_class(nn, N, i, j, diag(kKrSubNN, c, kKrNN, 0), diag(kKrSubNN, c, kKrNN, 1), diag(kKrSubNN, c, kKrNN, 2), diag(kKrSubNN, c, kKrNN, 3), n_u, self, forward);
+            if (zz) zz[ij] = diag(kKrSubZZ, c, kKrZZ, 0) / (4.0 * n_u);
             if (hop) {
-                hop[ij] = gathered(kKrHop, 0, c, forward);
-                hop[NN + ij] = gathered(kKrHop, kp.n_gat, c, forward);
+                hop[ij] = gathered(hp, kKrHop, 0);
+                hop[NN + ij] = gathered(hp, kKrHop, 1);
             }
-            if (ee) ee[ij] = gathered(kKrEE, 0, c, forward);
-            if (ll) ll[ij] = gathered(kKrLL, 0, c, forward);
+            if (ee) ee[ij] = gathered(lone, kKrEE, 0);
+            if (ll) ll[ij] = gathered(lone, kKrLL, 0);
         }
     return QBH_OK;
 }

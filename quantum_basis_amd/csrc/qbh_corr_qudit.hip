@@ -1,7 +1,8 @@
 // qbh_corr_qudit.hip -- all-pair static correlations of a resident state of d-level sites (the sector `total` of qbh_gen_qudit)
-// in one pass over it: qbh_corr_qudit_dev.  The structure is that of qbh_corr.hip: a grid of (row blocks) x (passes), a pass owns
-// a fixed group of pairs or sites and a per-lane accumulator array indexed by compile-time constants only, the workgroups leave
-// their sums through corr_block_partials and k_corr_reduce adds them in a fixed order.  No atomics.
+// in one pass over it: qbh_corr_qudit_dev.  A launch is a grid of (row blocks) x (passes); a pass owns a fixed group of pairs or
+// sites and a per-lane accumulator array indexed by compile-time constants only.  The block
+// reduction, the launch with its second stage (corr_reduce_launch), the pass layout (CorrPasses) and the shared fills and checks
+// are those of qbh_corr.hpp.  No atomics.
 //
 // Pass kinds (NA = 32 accumulators for a packed-real vector, 48 for a complex one; the diagonal kinds use the first 32):
 //   PAIR  16 pairs i < j, consecutive in the order (0,1) (0,2) .. (0,N-1) (1,2) ..:
@@ -18,8 +19,8 @@
 //   DD    8 quads (i < j; a0, b0 in {0, 2}):  [4q + 2u + v] = sum |psi|^2 f_{a0+u}(l_i) f_{b0+v}(l_j): four table reads serve four
 //         accumulators.  K = n_diag is rounded up to an even number with zero tables; K = 2 takes one quad per pair.
 //   SITE  32 items: [0] of the first pass = sum |psi|^2, the others sum |psi|^2 [l_s = l] (compare and select, no table).
-// Rows: a workgroup takes tiles of 256 x 4 consecutive rows; a lane unranks one row (qd_unrank: a dependent LDS walk per site)
-// and steps to the next three words with qd_next, the words go through LDS and come back row-interleaved (k_corr_spin's scheme).
+// Rows: tiles of 256 x 4 consecutive rows (the scheme: qbh_corr.hpp); a lane unranks one row (qd_unrank: a dependent LDS walk per site)
+// and steps to the next three words with qd_next.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -101,9 +102,7 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_qudit(CorrQudit t)
         const int64_t row = base + local;
         if (row >= t.dim) break;
         const uint64_t s = stage[(local / R) * (R + 1) + local % R];
-        d2 x = {0.0, 0.0};
-        if (REALX) x.x = t.xr[row];
-        else       x = t.xg[row];
+        const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
         const double w = fma(x.x, x.x, x.y * x.y);
         if (kind == kQcSite) {
 #pragma unroll
@@ -217,13 +216,15 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_qudit(CorrQudit t)
     corr_block_partials<NA>(acc, red, t.partials);
 }
 
-struct QcPasses {
-    int first[3], count[3], n_pairs, half;       // half = ceil(K / 2): half^2 quads per pair
-};
+template <int KIND>
+void (*qc_kernel(bool rx))(CorrQudit)
+{
+    return rx ? k_corr_qudit<true, KIND> : k_corr_qudit<false, KIND>;
+}
 
-int corr_qudit_run(int n_sites, int d, int total, const std::vector<uint64_t> &cum_raw, int64_t dim, const d2 *xg, const double *xr,
-                   int n_diag, const double *diag, const double *hend, const double *gmid, const double *lower, bool want_pop,
-                   bool want_dd, bool want_str, bool want_aa, std::vector<double> &comp, QcPasses &qp, hipStream_t s,
+int corr_qudit_run(const char *who, int n_sites, int d, int total, const std::vector<uint64_t> &cum_raw, int64_t dim, const d2 *xg,
+                   const double *xr, int n_diag, const double *diag, const double *hend, const double *gmid, const double *lower,
+                   bool want_pop, bool want_dd, bool want_str, bool want_aa, std::vector<double> &comp, CorrPasses &qp, hipStream_t s,
                    std::vector<void *> &pool)
 {
     const int N = n_sites, bits = bits_per_level(d), tw = total + 1, tws = tw + 1;
@@ -238,20 +239,13 @@ int corr_qudit_run(int n_sites, int d, int total, const std::vector<uint64_t> &c
         if (lower && l + 1 < d) tab[kQcUp * kQcTabStride + l] = lower[l + 1];
         for (int a = 0; a < n_diag; ++a) tab[(kQcDiag + a) * kQcTabStride + l] = diag[a * d + l];
     }
-    qp.n_pairs = N * (N - 1) / 2;
-    qp.half = (n_diag + 1) / 2;
-    const int nq = qp.half * qp.half;
+    const int n_pairs = N * (N - 1) / 2, half = (n_diag + 1) / 2, nq = half * half;       // half^2 quads per pair
     const int n_site_items = 1 + (want_pop ? N * d : 0);
-    qp.count[kQcPair] = (want_str || want_aa) ? (qp.n_pairs + kQcGroup - 1) / kQcGroup : 0;
-    qp.count[kQcDD] = want_dd ? (qp.n_pairs * nq + 7) / 8 : 0;
-    qp.count[kQcSite] = (n_site_items + kQcItems - 1) / kQcItems;
+    qp.add(kQcPair, (want_str || want_aa) ? n_pairs : 0, kQcGroup);
+    qp.add(kQcDD, want_dd ? n_pairs * nq : 0, 8);
+    qp.add(kQcSite, n_site_items, kQcItems);
     CorrQudit t{};
-    int n_pass = 0;
-    for (int k = 0; k < 3; ++k) {
-        qp.first[k] = n_pass;
-        n_pass += qp.count[k];
-    }
-    std::vector<uint32_t> item((size_t)n_pass * kQcItems, 0u);
+    std::vector<uint32_t> item((size_t)qp.n_pass * kQcItems, 0u);
     {
         size_t q = 0;
         for (int i = 0; i < N; ++i)
@@ -260,9 +254,9 @@ int corr_qudit_run(int n_sites, int d, int total, const std::vector<uint64_t> &c
                     item[(size_t)(qp.first[kQcPair] + q / kQcGroup) * kQcItems + q % kQcGroup] =
                         kQcValid | (uint32_t)i | ((uint32_t)j << 6) | (j == i + 1 ? kQcNewI : 0u);
                 if (qp.count[kQcDD])
-                    for (int A = 0; A < qp.half; ++A)
-                        for (int B = 0; B < qp.half; ++B) {
-                            const size_t quad = q * nq + (size_t)A * qp.half + B;
+                    for (int A = 0; A < half; ++A)
+                        for (int B = 0; B < half; ++B) {
+                            const size_t quad = q * nq + (size_t)A * half + B;
                             item[(size_t)(qp.first[kQcDD] + quad / 8) * kQcItems + quad % 8] =
                                 kQcValid | (uint32_t)(i * bits) | ((uint32_t)(j * bits) << 6) | ((uint32_t)(2 * A) << 12) | ((uint32_t)(2 * B) << 14);
                         }
@@ -298,48 +292,22 @@ int corr_qudit_run(int n_sites, int d, int total, const std::vector<uint64_t> &c
     const size_t lds = corr_qudit_lds(N, total);
     const int NA = xr ? qc_acc<true>() : qc_acc<false>();
     const int gx = corr_grid(dim, lds, kCorrBlock * kQcRows);
-    // one launch per kind (a kind is a kernel instance with registers of its own), each with its partials [gx][count][NA] and,
-    // behind them, its sums [count][NA]; comp holds the sums of all passes in pass order
+    // one launch per kind (a kind is a kernel instance with registers of its own), each a reduced launch in its slice of one
+    // allocation; comp holds the sums of all passes in pass order
     double *d_partials = nullptr;
-    QBH_HIP(qbh::dev_alloc(&d_partials, ((size_t)gx + 1) * n_pass * NA * sizeof(double)));
+    QBH_HIP_WHO(who, qbh::dev_alloc(&d_partials, corr_reduce_doubles(gx, qp.n_pass, NA) * sizeof(double)));
     pool.push_back(d_partials);
-#define QBH_CORR_QUDIT_LAUNCH(KIND)                                                                                                          \
-    do {                                                                                                                                    \
-        if (xr != nullptr) {                                                                                                                \
-            QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_qudit<true, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds));                                                                                         \
-            hipLaunchKernelGGL((k_corr_qudit<true, KIND>), dim3(gx, qp.count[KIND]), dim3(kCorrBlock), lds, s, t);                          \
-        } else {                                                                                                                            \
-            QBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_qudit<false, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds));                                                                                         \
-            hipLaunchKernelGGL((k_corr_qudit<false, KIND>), dim3(gx, qp.count[KIND]), dim3(kCorrBlock), lds, s, t);                         \
-        }                                                                                                                                   \
-    } while (0)
     comp.clear();
     std::vector<double> part;
     for (int k = 0; k < 3; ++k) {
         if (qp.count[k] == 0) continue;
         t.item = d_item + (size_t)qp.first[k] * kQcItems;
-        t.partials = d_partials + ((size_t)gx + 1) * qp.first[k] * NA;
-        if (k == kQcPair) QBH_CORR_QUDIT_LAUNCH(kQcPair);
-        else if (k == kQcDD) QBH_CORR_QUDIT_LAUNCH(kQcDD);
-        else QBH_CORR_QUDIT_LAUNCH(kQcSite);
-        QBH_HIP(hipGetLastError());
-        QBH_TRY(corr_finish(t.partials, gx, qp.count[k] * NA, part, s));
+        t.partials = d_partials + corr_reduce_doubles(gx, qp.first[k], NA);
+        void (*kernel)(CorrQudit) = k == kQcPair ? qc_kernel<kQcPair>(xr != nullptr) : k == kQcDD ? qc_kernel<kQcDD>(xr != nullptr) : qc_kernel<kQcSite>(xr != nullptr);
+        QBH_TRY(corr_reduce_launch(who, kernel, gx, qp.count[k], NA, kCorrBlock, lds, s, t, t.partials, pool, part));
         comp.insert(comp.end(), part.begin(), part.end());
     }
-#undef QBH_CORR_QUDIT_LAUNCH
     return QBH_OK;
-}
-
-bool qc_finite(const char *name, const double *v, int first, int n)
-{
-    for (int k = first; k < n; ++k)
-        if (!std::isfinite(v[k])) {
-            set_error("qbh_corr_qudit_dev: %s[%d] is not finite", name, k);
-            return false;
-        }
-    return true;
 }
 
 }  // namespace
@@ -356,37 +324,8 @@ extern "C" int qbh_corr_qudit_dev(int n_sites, int d, int total, const qbh_z *d_
         set_error("%s: total = %d (0 .. %d allowed)", who, total, n_sites * (d - 1));
         return QBH_EINVAL;
     }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
-        return QBH_EINVAL;
-    }
-    if (n_diag < 0 || n_diag > 4) {
-        set_error("%s: n_diag = %d (0 .. 4 allowed)", who, n_diag);
-        return QBH_EINVAL;
-    }
-    if (n_diag > 0 && diag == nullptr) {
-        set_error("%s: diag is NULL with n_diag = %d", who, n_diag);
-        return QBH_EINVAL;
-    }
-    if ((string_end != nullptr) != (string_mid != nullptr)) {
-        set_error("%s: string_end and string_mid must both be given or both be NULL", who);
-        return QBH_EINVAL;
-    }
-    if (dd != nullptr && n_diag == 0) {
-        set_error("%s: dd is wanted but n_diag = 0", who);
-        return QBH_EINVAL;
-    }
-    if (str != nullptr && string_end == nullptr) {
-        set_error("%s: str is wanted but string_end and string_mid are NULL", who);
-        return QBH_EINVAL;
-    }
-    if (aa != nullptr && lower == nullptr) {
-        set_error("%s: aa is wanted but lower is NULL", who);
-        return QBH_EINVAL;
-    }
-    if ((n_diag > 0 && !qc_finite("diag", diag, 0, n_diag * d)) || (string_end && !qc_finite("string_end", string_end, 0, d)) ||
-        (string_mid && !qc_finite("string_mid", string_mid, 0, d)) || (lower && !qc_finite("lower", lower, 1, d)))
-        return QBH_EINVAL;
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
+    QBH_TRY(qudit_corr_check_tables(who, d, n_diag, diag, string_end, string_mid, lower, dd != nullptr, str != nullptr, aa != nullptr));
     const int tw = total + 1;
     std::vector<uint64_t> cum, dims;
     qudit_table(n_sites, d, tw, cum, dims);
@@ -400,63 +339,37 @@ extern "C" int qbh_corr_qudit_dev(int n_sites, int d, int total, const qbh_z *d_
         set_error("%s: tables (%zu bytes) do not fit LDS", who, lds);
         return QBH_EUNSUPP;
     }
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites, K = n_diag;
     const bool want_pop = pop || dd || str || aa;                 // the diagonals of dd, str and aa follow from pop
     std::vector<void *> pool;
     std::vector<double> comp;
-    QcPasses qp{};
-    const int rc = corr_qudit_run(N, d, total, cum, (int64_t)dims[(size_t)total], reinterpret_cast<const d2 *>(d_vec), d_vec_re, K, diag,
-                                  string_end, string_mid, lower, want_pop, dd != nullptr, str != nullptr, aa != nullptr, comp, qp,
+    CorrPasses qp;
+    const int rc = corr_qudit_run(who, N, d, total, cum, (int64_t)dims[(size_t)total], reinterpret_cast<const d2 *>(d_vec), d_vec_re, K,
+                                  diag, string_end, string_mid, lower, want_pop, dd != nullptr, str != nullptr, aa != nullptr, comp, qp,
                                   (hipStream_t)stream, pool);
     free_pool(pool);
     if (rc != QBH_OK) return rc;
     const bool rx = d_vec_re != nullptr;
     const int NA = rx ? qc_acc<true>() : qc_acc<false>(), G = kQcGroup;
-    auto site_item = [&](int k) { return comp[(size_t)(qp.first[kQcSite] + k / kQcItems) * NA + k % kQcItems]; };
-    auto popv = [&](int i, int l) { return site_item(1 + i * d + l); };
+    auto site_item = [&](int k) { return qp.at(comp, kQcSite, k, kQcItems, 0, NA); };
     if (norm2) *norm2 = site_item(0);
     const size_t NN = (size_t)N * N;
-    const int nq = qp.half * qp.half;
-    size_t q = 0;
+    const int half = (K + 1) / 2, nq = half * half;
+    std::vector<double> pi((size_t)d);
+    int q = 0;
     for (int i = 0; i < N; ++i) {
-        const size_t ii = (size_t)i * N + i;
-        if (pop)
-            for (int l = 0; l < d; ++l) pop[i * d + l] = popv(i, l);
-        if (dd)
-            for (int a = 0; a < K; ++a)
-                for (int b = 0; b < K; ++b) {
-                    double v = 0.0;
-                    for (int l = 0; l < d; ++l) v += popv(i, l) * (diag[a * d + l] * diag[b * d + l]);
-                    dd[(size_t)(a * K + b) * NN + ii] = v;
-                }
-        if (str) {
-            double v = 0.0;
-            for (int l = 0; l < d; ++l) v += popv(i, l) * (string_end[l] * string_end[l]);
-            str[ii] = v;
-        }
-        if (aa) {
-            double v = 0.0;
-            for (int l = 0; l + 1 < d; ++l) v += popv(i, l) * (lower[l + 1] * lower[l + 1]);
-            aa[ii] = qbh_z{v, 0.0};
-        }
+        for (int l = 0; want_pop && l < d; ++l) pi[(size_t)l] = site_item(1 + i * d + l);
+        if (pop) std::copy(pi.begin(), pi.end(), pop + i * d);
+        qudit_corr_put_diag(N, i, d, K, pi.data(), diag, string_end, lower, dd, str, aa);
         for (int j = i + 1; j < N; ++j, ++q) {
             const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
-            const size_t c = (size_t)(qp.first[kQcPair] + q / G) * NA + q % G;      // present when str or aa is asked for
-            if (str) str[ij] = str[ji] = comp[c];
-            if (aa) {
-                const double re = comp[c + G], im = rx ? 0.0 : comp[c + 2 * G];
-                aa[ij] = qbh_z{re, im};
-                aa[ji] = qbh_z{re, -im};
-            }
+            if (str) str[ij] = str[ji] = qp.at(comp, kQcPair, q, G, 0, NA);
+            if (aa) corr_put_herm(aa, N, i, j, qp.at(comp, kQcPair, q, G, 1, NA), rx ? 0.0 : qp.at(comp, kQcPair, q, G, 2, NA));
             if (dd)
                 for (int a = 0; a < K; ++a)
                     for (int b = 0; b < K; ++b) {
-                        const size_t quad = q * nq + (size_t)(a / 2) * qp.half + b / 2;
-                        const double v = comp[(size_t)(qp.first[kQcDD] + quad / 8) * NA + (quad % 8) * 4 + (a % 2) * 2 + b % 2];
+                        const double v = qp.at_item(comp, kQcDD, q * nq + (a / 2) * half + b / 2, 8, 4, (a % 2) * 2 + b % 2, NA);
                         dd[(size_t)(a * K + b) * NN + ij] = v;           // <f_a(i) f_b(j)> ...
                         dd[(size_t)(b * K + a) * NN + ji] = v;           // ... = <f_b(j) f_a(i)>
                     }

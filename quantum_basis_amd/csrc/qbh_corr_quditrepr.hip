@@ -38,8 +38,8 @@
 //   SITE  15 / LV site orbits x LV levels (LV = 3, 5 or 8 >= d):  [g LV + l] = sum w_a popcount(lm[l] & orbit), [15] norm2 (read
 //         from the first site pass)
 // A group that is not asked for has no passes; it changes neither the grid along x nor any other accumulator, so the other outputs
-// keep their bits.  Every workgroup leaves its sums at partials[blockIdx.x][pass][accumulator] (repr_block_partials) and
-// k_corr_reduce adds the workgroups in a fixed order (corr_finish): no atomics, two calls return the same bits.
+// keep their bits.  Every workgroup leaves its sums at partials[blockIdx.x][pass][accumulator] (corr_block_partials) and
+// k_corr_reduce adds the workgroups in a fixed order (corr_reduce_launch): no atomics, two calls return the same bits.
 //
 // Tables.  The counting table cum (at most 33 KB), the characters, the operator tables (512 B) and gpow (4160 B) are staged in LDS
 // by the passes that read them.  The translation tables join them when everything fits kCorrLdsCap (150 KB); 64 translations x 11
@@ -62,8 +62,8 @@
 
 #include "qbh_sector.hpp"
 #include "qbh_device.hpp"
-#include "qbh_corr.hpp"                                      // kCorrLdsCap, corr_uniform, corr_finish
-#include "qbh_corr_repr.hpp"                                 // repr_classes, repr_block_partials, repr_launch_shape
+#include "qbh_corr.hpp"                                      // device helpers, launch path, pass layout and host fills
+#include "qbh_corr_repr.hpp"                                 // classes and orbits of site pairs, symmetry checks
 
 namespace qbh {
 namespace {
@@ -98,15 +98,6 @@ struct CorrQuditRepr {
     double *partials;
 };
 
-template <bool REALX>
-__device__ __forceinline__ d2 qr_amp(const CorrQuditRepr &t, int64_t row)
-{
-    d2 x = {0.0, 0.0};
-    if (REALX) x.x = t.xr[row];
-    else       x = t.xg[row];
-    return x;
-}
-
 // lm[l] = the sites of word a at level l, bit s * bits for site s (F = that bit of every site).  Codes a field cannot hold for
 // this d (and levels >= d, which no word of the sector has) give 0.
 __device__ __forceinline__ void qr_level_masks(uint64_t a, int bits, uint64_t F, uint64_t (&lm)[kQuditMaxD])
@@ -126,12 +117,11 @@ __device__ __forceinline__ void qr_dd_pass(const CorrQuditRepr &t, const double 
     const int bits = t.bits;
     const uint32_t field = (1u << bits) - 1u;
     int k0[GC + 1];
-#pragma unroll
-    for (int g = 0; g <= GC; ++g) k0[g] = (int)corr_uniform((uint32_t)t.cls_start[lp * GC + g]);
+    corr_group_bounds<GC>(t.cls_start, lp * GC, k0);
     for (int64_t row = row0; row < t.dim; row += stride) {
         if (t.info[row] & 0x80) continue;
         const uint64_t a = t.reps[row];
-        const d2 x = qr_amp<REALX>(t, row);
+        const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
         const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
         for (int g = 0; g < GC; ++g) {
@@ -175,7 +165,7 @@ __device__ __forceinline__ void qr_site_pass(const CorrQuditRepr &t, int lp, int
     for (int g = 0; g < NO; ++g) mk[g] = corr_uniform(t.site_mask[lp * NO + g]);
     for (int64_t row = row0; row < t.dim; row += stride) {
         if (t.info[row] & 0x80) continue;
-        const d2 x = qr_amp<REALX>(t, row);
+        const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
         const double w = fma(x.x, x.x, x.y * x.y);
         uint64_t lm[kQuditMaxD];
         qr_level_masks(t.reps[row], t.bits, t.fields, lm);
@@ -220,14 +210,13 @@ __global__ __launch_bounds__(BLOCK) void k_corr_quditrepr(CorrQuditRepr t)
     const int64_t stride = (int64_t)gridDim.x * BLOCK, row0 = (int64_t)blockIdx.x * BLOCK + tid;
     if (kind == kQrKindPair) {
         int k0[GH + 1];
-#pragma unroll
-        for (int g = 0; g <= GH; ++g) k0[g] = (int)corr_uniform((uint32_t)t.cls_start[lp * GH + g]);
+        corr_group_bounds<GH>(t.cls_start, lp * GH, k0);
         for (int64_t row = row0; row < t.dim; row += stride) {
             const uint8_t ci = t.info[row];
             if (ci & 0x80) continue;                                      // zero norm at this momentum: its entry is never read
             const uint64_t a = t.reps[row];
             const double sa = (double)(ci & 0x7f);
-            const d2 x = qr_amp<REALX>(t, row);
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
 #pragma unroll
             for (int g = 0; g < GH; ++g) {
                 double sr = 0.0, si = 0.0;
@@ -272,12 +261,11 @@ __global__ __launch_bounds__(BLOCK) void k_corr_quditrepr(CorrQuditRepr t)
         }
     } else if (kind == kQrKindStr) {
         int k0[GS + 1];
-#pragma unroll
-        for (int g = 0; g <= GS; ++g) k0[g] = (int)corr_uniform((uint32_t)t.str_start[lp * GS + g]);
+        corr_group_bounds<GS>(t.str_start, lp * GS, k0);
         for (int64_t row = row0; row < t.dim; row += stride) {
             if (t.info[row] & 0x80) continue;
             const uint64_t a = t.reps[row];
-            const d2 x = qr_amp<REALX>(t, row);
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
             const double w = fma(x.x, x.x, x.y * x.y);
             uint64_t lm[kQuditMaxD];
             qr_level_masks(a, bits, t.fields, lm);
@@ -308,7 +296,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_quditrepr(CorrQuditRepr t)
         else if (t.lv == 5) qr_site_pass<REALX, 5>(t, lp, row0, stride, acc);
         else                qr_site_pass<REALX, 8>(t, lp, row0, stride, acc);
     }
-    repr_block_partials<NA, BLOCK>(acc, red, t.partials);
+    corr_block_partials<NA, BLOCK>(acc, red, t.partials);
 }
 
 // ------------------------------------------------------------------------------------------------------ host side --
@@ -382,39 +370,22 @@ QrStrings qr_string_classes(int N, int n_trans, const int32_t *perms)
 // dynamic LDS of a launch: counting table, characters, operator tables and gpow, and the translation tables when all of it fits
 size_t qr_lds_small(int n_cum, int n_trans) { return ((size_t)n_cum + 2 * (size_t)n_trans + kQrOps) * 8; }
 
-template <bool REALX, int BLOCK, bool TABLDS>
-hipError_t qr_launch(const CorrQuditRepr &t, int gx, int n_pass, size_t lds, hipStream_t s)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_quditrepr<REALX, BLOCK, TABLDS>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_corr_quditrepr<REALX, BLOCK, TABLDS>), dim3(gx, n_pass), dim3(BLOCK), lds, s, t);
-    return hipGetLastError();
-}
-
-struct QrPasses {
-    int first[4], gc, no;                                    // first pass of every kind; classes of a DD pass, orbits of a site pass
-};
-
 // the passes of the wanted groups, the launch and the two-stage reduction: comp[pass * kQrAcc + accumulator]
 template <bool REALX>
 int corr_quditrepr_run(const char *who, CorrQuditRepr t, const ReprClasses &K, const QrStrings &S, size_t n_tab, bool want_dd,
-                       bool want_str, bool want_aa, QrPasses &qp, std::vector<double> &comp, hipStream_t s, std::vector<void *> &pool)
+                       bool want_str, bool want_aa, CorrPasses &qp, std::vector<double> &comp, hipStream_t s, std::vector<void *> &pool)
 {
     constexpr int NA = kQrAcc;
-    qp.gc = NA / (t.kp * t.kp);
-    qp.no = (NA - 1) / t.lv;
-    const int per_kind[4] = {want_dd ? (K.n_cls + qp.gc - 1) / qp.gc : 0, want_str ? (S.n_cls + kQrStr - 1) / kQrStr : 0,
-                             want_aa ? (K.n_cls + kQrGat - 1) / kQrGat : 0, (K.n_orb + qp.no - 1) / qp.no};
-    int n_pass = 0;
-    for (int k = 0; k < 4; ++k) {
-        qp.first[k] = n_pass;
-        t.pass_end[k] = n_pass += per_kind[k];
-    }
+    const int no = (NA - 1) / t.lv;                          // site orbits of a site pass
+    qp.add(kQrKindDD, want_dd ? K.n_cls : 0, NA / (t.kp * t.kp));
+    qp.add(kQrKindStr, want_str ? S.n_cls : 0, kQrStr);
+    qp.add(kQrKindPair, want_aa ? K.n_cls : 0, kQrGat);
+    qp.add(kQrKindSite, K.n_orb, no);
+    for (int k = 0; k < 4; ++k) t.pass_end[k] = qp.first[k] + qp.count[k];
     std::vector<int32_t> cls_start, str_start((size_t)S.n_cls + NA + 1, 0);
     std::vector<uint32_t> pairs, str_ends;
     std::vector<uint64_t> str_mask;
-    repr_flatten_classes(K, NA, cls_start, pairs);
+    repr_flatten(K.pairs, NA, cls_start, pairs);
     for (int c = 0; c < S.n_cls; ++c) {
         str_start[(size_t)c] = (int32_t)str_ends.size();
         for (const auto &m : S.members[(size_t)c]) {
@@ -430,7 +401,7 @@ int corr_quditrepr_run(const char *who, CorrQuditRepr t, const ReprClasses &K, c
         str_ends.push_back(0u);
         str_mask.push_back(0ULL);
     }
-    std::vector<uint64_t> site_mask((size_t)per_kind[kQrKindSite] * qp.no, 0ULL);
+    std::vector<uint64_t> site_mask((size_t)qp.count[kQrKindSite] * no, 0ULL);
     for (int o = 0; o < K.n_orb; ++o)
         for (int k = 0; k < t.n_sites; ++k)
             if ((K.mask[(size_t)o] >> k) & 1ULL) site_mask[(size_t)o] |= 1ULL << (k * t.bits);
@@ -453,25 +424,12 @@ int corr_quditrepr_run(const char *who, CorrQuditRepr t, const ReprClasses &K, c
     const bool tab_lds = small + n_tab * 8 <= kCorrLdsCap;
     const size_t lds = small + (tab_lds ? n_tab * 8 : 0);
     const ReprShape shape = repr_launch_shape(lds, t.dim);
-    const int gx = shape.gx, ncomp = n_pass * NA;
-    QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * ncomp * sizeof(double)));
-    pool.push_back(t.partials);
-    hipError_t e;
-    if (!tab_lds)         e = qr_launch<REALX, kReprBlockS, false>(t, gx, n_pass, lds, s);
-    else if (shape.large) e = qr_launch<REALX, kReprBlockL, true>(t, gx, n_pass, lds, s);
-    else                  e = qr_launch<REALX, kReprBlockS, true>(t, gx, n_pass, lds, s);
-    QBH_HIP_WHO(who, e);
-    return corr_finish(t.partials, gx, ncomp, comp, s);
-}
-
-bool qr_finite(const char *who, const char *name, const double *v, int first, int n)
-{
-    for (int k = first; k < n; ++k)
-        if (!std::isfinite(v[k])) {
-            set_error("%s: %s[%d] is not finite", who, name, k);
-            return false;
-        }
-    return true;
+    const bool large = tab_lds && shape.large;               // then one workgroup of 1024 lanes per CU
+    void (*kernel)(CorrQuditRepr) = !tab_lds ? k_corr_quditrepr<REALX, kReprBlockS, false>
+                         : large  ? k_corr_quditrepr<REALX, kReprBlockL, true>
+                                  : k_corr_quditrepr<REALX, kReprBlockS, true>;
+    return corr_reduce_launch(who, kernel, shape.gx, qp.n_pass, NA, large ? kReprBlockL : kReprBlockS, lds, s, t, nullptr, pool,
+                              comp);
 }
 
 }  // namespace
@@ -495,50 +453,15 @@ extern "C" int qbh_corr_qudit_repr_dev(int n_sites, int d, int total, int n_tran
 {
     using namespace qbh;
     const char *who = "qbh_corr_qudit_repr_dev";
-    if (!perms || !chars) {
-        set_error("%s: perms and chars must be given", who);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(repr_check_tables(who, perms, chars));
     QBH_TRY(qudit_check_shape(who, n_sites, d));
     if (total < 0 || total > n_sites * (d - 1)) {
         set_error("%s: total = %d (0 .. %d allowed)", who, total, n_sites * (d - 1));
         return QBH_EINVAL;
     }
-    if (n_trans < 1 || n_trans > kReprMaxTrans) {
-        set_error("%s: n_trans = %d (1 .. %d allowed)", who, n_trans, kReprMaxTrans);
-        return QBH_EINVAL;
-    }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
-        return QBH_EINVAL;
-    }
-    if (n_diag < 0 || n_diag > 4) {
-        set_error("%s: n_diag = %d (0 .. 4 allowed)", who, n_diag);
-        return QBH_EINVAL;
-    }
-    if (n_diag > 0 && diag == nullptr) {
-        set_error("%s: diag is NULL with n_diag = %d", who, n_diag);
-        return QBH_EINVAL;
-    }
-    if ((string_end != nullptr) != (string_mid != nullptr)) {
-        set_error("%s: string_end and string_mid must both be given or both be NULL", who);
-        return QBH_EINVAL;
-    }
-    if (dd != nullptr && n_diag == 0) {
-        set_error("%s: dd is wanted but n_diag = 0", who);
-        return QBH_EINVAL;
-    }
-    if (str != nullptr && string_end == nullptr) {
-        set_error("%s: str is wanted but string_end and string_mid are NULL", who);
-        return QBH_EINVAL;
-    }
-    if (aa != nullptr && lower == nullptr) {
-        set_error("%s: aa is wanted but lower is NULL", who);
-        return QBH_EINVAL;
-    }
-    if ((n_diag > 0 && !qr_finite(who, "diag", diag, 0, n_diag * d)) || (string_end && !qr_finite(who, "string_end", string_end, 0, d)) ||
-        (string_mid && !qr_finite(who, "string_mid", string_mid, 0, d)) || (lower && !qr_finite(who, "lower", lower, 1, d)))
-        return QBH_EINVAL;
+    QBH_TRY(repr_check_trans(who, n_trans));
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
+    QBH_TRY(qudit_corr_check_tables(who, d, n_diag, diag, string_end, string_mid, lower, dd != nullptr, str != nullptr, aa != nullptr));
     std::vector<QuditReprDev> rr(1);
     QuditReprDev &R = rr[0];
     std::vector<uint64_t> tab;
@@ -547,10 +470,7 @@ extern "C" int qbh_corr_qudit_repr_dev(int n_sites, int d, int total, int n_tran
     int64_t nstates = 0;
     std::vector<uint64_t> cum;
     QBH_TRY(sector_words(R, cum, &nstates, who));            // every refusal comes before the device is looked for
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites, K = n_diag, bits = R.bits;
     const ReprClasses C = repr_classes(N, n_trans, perms);
     const QrStrings S = str ? qr_string_classes(N, n_trans, perms) : QrStrings{};
@@ -602,68 +522,44 @@ extern "C" int qbh_corr_qudit_repr_dev(int n_sites, int d, int total, int n_tran
     t.xr = d_vec_re;
     const bool rx = d_vec_re != nullptr;
     std::vector<double> comp;
-    QrPasses qp{};
+    CorrPasses qp;
     if (rx) QBH_TRY(corr_quditrepr_run<true>(who, t, C, S, tab.size(), dd != nullptr, str != nullptr, aa != nullptr, qp, comp, (hipStream_t)stream, bufs.pool));
     else    QBH_TRY(corr_quditrepr_run<false>(who, t, C, S, tab.size(), dd != nullptr, str != nullptr, aa != nullptr, qp, comp, (hipStream_t)stream, bufs.pool));
     constexpr int NA = kQrAcc, GH = kQrGat;
-    const int KK = t.kp * t.kp;
+    const int KK = t.kp * t.kp, gc = NA / KK, no = (NA - 1) / t.lv;      // classes of a DD pass, site orbits of a site pass
     const size_t NN = (size_t)N * N;
-    if (norm2) *norm2 = comp[(size_t)qp.first[kQrKindSite] * NA + NA - 1];
+    if (norm2) *norm2 = qp.at_item(comp, kQrKindSite, 0, no, t.lv, NA - 1, NA);
     if (dim_out) *dim_out = Sec.dim;
     std::vector<double> popv((size_t)N * d);
     for (int i = 0; i < N; ++i) {
         const int o = C.orb[(size_t)i];
-        for (int l = 0; l < d; ++l)
-            popv[(size_t)i * d + l] = comp[(size_t)(qp.first[kQrKindSite] + o / qp.no) * NA + (o % qp.no) * t.lv + l] / (double)C.n_s[(size_t)o];
+        for (int l = 0; l < d; ++l) popv[(size_t)i * d + l] = qp.at_item(comp, kQrKindSite, o, no, t.lv, l, NA) / (double)C.n_s[(size_t)o];
     }
     if (pop) std::copy(popv.begin(), popv.end(), pop);
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < N; ++j) {
             const size_t ij = (size_t)i * N + j;
             if (i == j) {                                    // the diagonals follow from pop, as in qbh_corr_qudit_dev
-                const double *pi = popv.data() + (size_t)i * d;
-                if (dd)
-                    for (int a = 0; a < K; ++a)
-                        for (int b = 0; b < K; ++b) {
-                            double v = 0.0;
-                            for (int l = 0; l < d; ++l) v += pi[l] * (diag[a * d + l] * diag[b * d + l]);
-                            dd[(size_t)(a * K + b) * NN + ij] = v;
-                        }
-                if (str) {
-                    double v = 0.0;
-                    for (int l = 0; l < d; ++l) v += pi[l] * (string_end[l] * string_end[l]);
-                    str[ij] = v;
-                }
-                if (aa) {
-                    double v = 0.0;
-                    for (int l = 0; l + 1 < d; ++l) v += pi[l] * (lower[l + 1] * lower[l + 1]);
-                    aa[ij] = qbh_z{v, 0.0};
-                }
+                qudit_corr_put_diag(N, i, d, K, popv.data() + (size_t)i * d, diag, string_end, lower, dd, str, aa);
                 continue;
             }
             const int c = C.cls[ij];
             const bool forward = C.fwd[ij] != 0, self = C.self[(size_t)c] != 0;
             const double n_o = (self ? 2.0 : 1.0) * (double)C.nu[(size_t)c];      // the size of the forward orbit
-            if (dd) {
-                const size_t at = (size_t)(qp.first[kQrKindDD] + c / qp.gc) * NA + (size_t)(c % qp.gc) * KK;
+            if (dd)
                 for (int a = 0; a < K; ++a)
                     for (int b = 0; b < K; ++b) {
                         // the mirror orientation: <f_a(i) f_b(j)> = <f_b(j) f_a(i)>, (j, i) forward.  A class that is its own mirror
                         // has summed the same terms into [a][b] and [b][a] in another order: one of the two serves both, so that
                         // dd[a][b][i][j] and dd[b][a][j][i] carry the same bits there as everywhere else
                         const bool direct = self ? a <= b : forward;
-                        dd[(size_t)(a * K + b) * NN + ij] = comp[at + (direct ? a * t.kp + b : b * t.kp + a)] / n_o;
+                        dd[(size_t)(a * K + b) * NN + ij] = qp.at_item(comp, kQrKindDD, c, gc, KK, direct ? a * t.kp + b : b * t.kp + a, NA) / n_o;
                     }
-            }
             if (str) {
                 const int sc = S.cls[(size_t)std::min(i, j) * N + std::max(i, j)];
-                str[ij] = comp[(size_t)(qp.first[kQrKindStr] + sc / kQrStr) * NA + sc % kQrStr] / (double)S.members[(size_t)sc].size();
+                str[ij] = qp.at(comp, kQrKindStr, sc, kQrStr, 0, NA) / (double)S.members[(size_t)sc].size();
             }
-            if (aa) {
-                const size_t at = (size_t)(qp.first[kQrKindPair] + c / GH) * NA + c % GH;
-                const double im = (rx || self) ? 0.0 : comp[at + GH] / n_o;
-                aa[ij] = qbh_z{comp[at] / n_o, forward ? im : -im};
-            }
+            if (aa) aa[ij] = repr_herm_value(qp.at(comp, kQrKindPair, c, GH, 0, NA), (rx || self) ? 0.0 : qp.at(comp, kQrKindPair, c, GH, 1, NA), n_o, forward);
         }
     return QBH_OK;
 }

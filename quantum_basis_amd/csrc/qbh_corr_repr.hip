@@ -43,8 +43,8 @@
 
 #include "qbh_sector.hpp"
 #include "qbh_device.hpp"
-#include "qbh_corr.hpp"                                      // kCorrLdsCap, corr_uniform, corr_finish
-#include "qbh_corr_repr.hpp"                                 // repr_classes, repr_block_partials
+#include "qbh_corr.hpp"                                      // device helpers, launch path, pass layout and host fills
+#include "qbh_corr_repr.hpp"                                 // classes and orbits of site pairs, symmetry checks
 
 namespace qbh {
 namespace {
@@ -99,8 +99,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_repr(CorrRepr t)
     const int64_t stride = (int64_t)gridDim.x * BLOCK;
     if (pass < t.n_pair_pass) {
         int k0[G + 1], nu[G];
-#pragma unroll
-        for (int g = 0; g <= G; ++g) k0[g] = (int)corr_uniform((uint32_t)t.slot_start[pass * G + g]);
+        corr_group_bounds<G>(t.slot_start, pass * G, k0);
 #pragma unroll
         for (int g = 0; g < G; ++g) nu[g] = (int)corr_uniform((uint32_t)t.slot_nu[pass * G + g]);
         for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
@@ -108,9 +107,7 @@ __global__ __launch_bounds__(BLOCK) void k_corr_repr(CorrRepr t)
             if (ci & 0x80) continue;                                      // zero norm at this momentum: its entry is never read
             const uint64_t a = t.reps[row];
             const double sa = (double)(ci & 0x7f);
-            d2 x = {0.0, 0.0};
-            if (REALX) x.x = t.xr[row];
-            else       x = t.xg[row];
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
             const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -170,16 +167,14 @@ __global__ __launch_bounds__(BLOCK) void k_corr_repr(CorrRepr t)
         for (int64_t row = (int64_t)blockIdx.x * BLOCK + tid; row < t.dim; row += stride) {
             if (t.info[row] & 0x80) continue;
             const uint64_t a = t.reps[row];
-            d2 x = {0.0, 0.0};
-            if (REALX) x.x = t.xr[row];
-            else       x = t.xg[row];
+            const d2 x = corr_load_x<REALX>(t.xg, t.xr, row);
             const double w = fma(x.x, x.x, x.y * x.y);
 #pragma unroll
             for (int g = 0; g < NS; ++g) acc[g] += w * (0.5 * (double)__popcll(mk[g]) - (double)__popcll(a & mk[g]));
             acc[NS] += w;
         }
     }
-    repr_block_partials<NA, BLOCK>(acc, red, t.partials);
+    corr_block_partials<NA, BLOCK>(acc, red, t.partials);
 }
 
 // ------------------------------------------------------------------------------------------------------ host side --
@@ -187,22 +182,16 @@ __global__ __launch_bounds__(BLOCK) void k_corr_repr(CorrRepr t)
 size_t repr_lds_small(int n_sites, int n_trans) { return ((size_t)(n_sites + 1) * kBinomRow + 2 * (size_t)n_trans) * 8; }
 bool repr_tab_lds(int n_sites, int n_trans, size_t n_tab) { return repr_lds_small(n_sites, n_trans) + n_tab * 8 <= kCorrLdsCap; }
 
-template <bool REALX, int BLOCK, bool TABLDS>
-hipError_t repr_launch(const CorrRepr &t, int gx, int n_pass, size_t lds, hipStream_t s)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_corr_repr<REALX, BLOCK, TABLDS>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_corr_repr<REALX, BLOCK, TABLDS>), dim3(gx, n_pass), dim3(BLOCK), lds, s, t);
-    return hipGetLastError();
-}
+enum { kReprPair = 0, kReprSite = 1 };
 
 template <bool REALX>
 int corr_repr_run(const char *who, CorrRepr t, const ReprClasses &K, size_t n_tab, bool want_pairs, std::vector<double> &comp,
-                  int *n_pair_pass_out, hipStream_t s, std::vector<void *> &pool)
+                  CorrPasses &rp, hipStream_t s, std::vector<void *> &pool)
 {
     constexpr int G = kReprGroup, NA = repr_acc<REALX>(), NS = NA - 1;
-    const int n_pair_pass = want_pairs ? (K.n_cls + G - 1) / G : 0, n_site_pass = (K.n_orb + NS - 1) / NS;
+    rp.add(kReprPair, want_pairs ? K.n_cls : 0, G);
+    rp.add(kReprSite, K.n_orb, NS);
+    const int n_pair_pass = rp.count[kReprPair], n_site_pass = rp.count[kReprSite];
     std::vector<int32_t> slot_start((size_t)n_pair_pass * G + 1, 0), slot_nu((size_t)n_pair_pass * G + 1, 0);
     std::vector<uint32_t> pairs;
     for (int c = 0; c < n_pair_pass * G; ++c) {
@@ -230,18 +219,12 @@ int corr_repr_run(const char *who, CorrRepr t, const ReprClasses &K, size_t n_ta
     const bool tab_lds = repr_tab_lds(t.n_sites, t.n_trans, n_tab);
     const size_t lds = repr_lds_small(t.n_sites, t.n_trans) + (tab_lds ? n_tab * 8 : 0);
     const ReprShape shape = repr_launch_shape(lds, t.dim);
-    const bool large = shape.large;                                       // then one workgroup of 1024 lanes per CU
-    const int gx = shape.gx;
-    const int n_pass = n_pair_pass + n_site_pass, ncomp = n_pass * NA;
-    QBH_HIP_WHO(who, qbh::dev_alloc(&t.partials, ((size_t)gx + 1) * ncomp * sizeof(double)));
-    pool.push_back(t.partials);
-    hipError_t e;
-    if (!tab_lds)   e = repr_launch<REALX, kReprBlockS, false>(t, gx, n_pass, lds, s);
-    else if (large) e = repr_launch<REALX, kReprBlockL, true>(t, gx, n_pass, lds, s);
-    else            e = repr_launch<REALX, kReprBlockS, true>(t, gx, n_pass, lds, s);
-    QBH_HIP_WHO(who, e);
-    *n_pair_pass_out = n_pair_pass;
-    return corr_finish(t.partials, gx, ncomp, comp, s);
+    const bool large = tab_lds && shape.large;                            // then one workgroup of 1024 lanes per CU
+    void (*kernel)(CorrRepr) = !tab_lds ? k_corr_repr<REALX, kReprBlockS, false>
+                         : large  ? k_corr_repr<REALX, kReprBlockL, true>
+                                  : k_corr_repr<REALX, kReprBlockS, true>;
+    return corr_reduce_launch(who, kernel, shape.gx, rp.n_pass, NA, large ? kReprBlockL : kReprBlockS, lds, s, t, nullptr, pool,
+                              comp);
 }
 
 }  // namespace
@@ -258,10 +241,7 @@ extern "C" int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const 
         set_error("%s: invalid argument (1 .. 62 sites, n_dn in 0 .. min(n_sites, 33), 1 .. %d translations)", who, kReprMaxTrans);
         return QBH_EINVAL;
     }
-    if ((d_vec != nullptr) == (d_vec_re != nullptr)) {
-        set_error("%s: exactly one of d_vec and d_vec_re must be given", who);
-        return QBH_EINVAL;
-    }
+    QBH_TRY(corr_check_vectors(who, d_vec, d_vec_re));
     std::vector<ReprDev> rr(1);
     ReprDev &R = rr[0];
     std::vector<uint64_t> tab;
@@ -270,10 +250,7 @@ extern "C" int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const 
     int64_t nstates = 0;
     std::vector<uint64_t> ctab;
     QBH_TRY(sector_words(R, ctab, &nstates, who));           // every refusal comes before the device is looked for
-    if (qbh_device_count() <= 0) {
-        set_error("no HIP device visible");
-        return QBH_ENODEVICE;
-    }
+    QBH_TRY(corr_check_device());
     const int N = n_sites;
     const ReprClasses K = repr_classes(N, n_trans, perms);
     DevBufs bufs;
@@ -297,16 +274,18 @@ extern "C" int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const 
     t.xr = d_vec_re;
     const bool rx = d_vec_re != nullptr, want_pairs = zz != nullptr || pm != nullptr;
     std::vector<double> comp;
-    int npp = 0;
-    if (rx) QBH_TRY(corr_repr_run<true>(who, t, K, tab.size(), want_pairs, comp, &npp, (hipStream_t)stream, bufs.pool));
-    else    QBH_TRY(corr_repr_run<false>(who, t, K, tab.size(), want_pairs, comp, &npp, (hipStream_t)stream, bufs.pool));
+    CorrPasses rp;
+    if (rx) QBH_TRY(corr_repr_run<true>(who, t, K, tab.size(), want_pairs, comp, rp, (hipStream_t)stream, bufs.pool));
+    else    QBH_TRY(corr_repr_run<false>(who, t, K, tab.size(), want_pairs, comp, rp, (hipStream_t)stream, bufs.pool));
     const int G = kReprGroup, NA = rx ? repr_acc<true>() : repr_acc<false>(), NS = NA - 1;
-    auto orbit_sum = [&](int o) { return comp[(size_t)(npp + o / NS) * NA + o % NS]; };
-    const double n2 = comp[(size_t)npp * NA + NS];
+    const double n2 = rp.at(comp, kReprSite, 0, NS, 1, NA);
     if (norm2) *norm2 = n2;
     if (dim_out) *dim_out = S.dim;
     std::vector<double> szv((size_t)N);
-    for (int i = 0; i < N; ++i) szv[(size_t)i] = orbit_sum(K.orb[(size_t)i]) / (double)K.n_s[(size_t)K.orb[(size_t)i]];
+    for (int i = 0; i < N; ++i) {
+        const int o = K.orb[(size_t)i];
+        szv[(size_t)i] = rp.at(comp, kReprSite, o, NS, 0, NA) / (double)K.n_s[(size_t)o];
+    }
     if (sz) std::copy(szv.begin(), szv.end(), sz);
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < N; ++j) {
@@ -317,14 +296,11 @@ extern "C" int qbh_corr_spin_repr_dev(int n_sites, int n_dn, int n_trans, const 
                 continue;
             }
             const int c = K.cls[ij];
-            const size_t at = (size_t)(c / G) * NA + c % G;
             const double n_u = (double)K.nu[(size_t)c];
-            if (zz) zz[ij] = comp[at] / n_u;
-            if (pm) {
-                const double re = comp[at + G] / (2.0 * n_u);
-                const double im = (rx || K.self[(size_t)c]) ? 0.0 : comp[at + 2 * G] / (2.0 * n_u);
-                pm[ij] = qbh_z{re, K.fwd[ij] ? im : -im};
-            }
+            if (zz) zz[ij] = rp.at(comp, kReprPair, c, G, 0, NA) / n_u;
+            if (pm)
+                pm[ij] = repr_herm_value(rp.at(comp, kReprPair, c, G, 1, NA), (rx || K.self[(size_t)c]) ? 0.0 : rp.at(comp, kReprPair, c, G, 2, NA),
+                                         2.0 * n_u, K.fwd[ij] != 0);
         }
     return QBH_OK;
 }

@@ -1,8 +1,7 @@
-// qbh_corr_repr.hpp -- what the momentum-sector correlation calls share (qbh_corr_repr.hip: spin-1/2; qbh_corr_hubrepr.hip:
-// two-species fermions; qbh_corr_quditrepr.hip: d-level sites; qbh_corr_kondorepr.hip: the Kondo lattice): the classes of site
-// pairs, the orbits of ordered site pairs and the orbits of sites under the group (host), the block reduction of a workgroup of
-// any size into partials[blockIdx.x][pass][accumulator], the shape of a launch from its LDS footprint and the check of the
-// characters of a packed-real vector.  Internal linkage, like qbh_sector.hpp.
+// qbh_corr_repr.hpp -- what the momentum-sector correlation calls share on top of qbh_corr.hpp (qbh_corr_repr.hip: spin-1/2;
+// qbh_corr_hubrepr.hip: two-species fermions; qbh_corr_quditrepr.hip: d-level sites; qbh_corr_kondorepr.hip: the Kondo lattice):
+// the classes of site pairs, the orbits of ordered site pairs and the orbits of sites under the group, and the checks of the
+// symmetry arguments; all of it host code.  Internal linkage, like qbh_sector.hpp, which comes first.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -13,26 +12,6 @@
 
 namespace qbh {
 namespace {
-
-// acc summed over the workgroup into partials[(blockIdx.x * gridDim.y + blockIdx.y) * NA ..]: every wavefront, then lane c
-// adds the wavefronts of accumulator c in order (corr_block_partials for a workgroup of BLOCK lanes)
-template <int NA, int BLOCK>
-__device__ __forceinline__ void repr_block_partials(double (&acc)[NA], double *red, double *partials)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int c = 0; c < NA; ++c) acc[c] = wave_sum(acc[c]);
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < NA; ++c) red[c * (BLOCK / 64) + wave] = acc[c];
-    }
-    __syncthreads();
-    if (tid < NA) {
-        double s = 0.0;
-        for (int w = 0; w < BLOCK / 64; ++w) s += red[tid * (BLOCK / 64) + w];
-        partials[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * NA + tid] = s;
-    }
-}
 
 // Two ordered site pairs are in one orbit when a group element carries one to the other; a class is an orbit together with its
 // mirror image (q, p).  One orbit of every class is called forward.  The orbits are found by union-find, so groups with
@@ -65,20 +44,23 @@ inline std::vector<int> uf_smallest(std::vector<int> &par)
     return rep;
 }
 
+// the orbits of the ordered site pairs under the group: [i * N + j] = the smallest member of the orbit of (i, j)
+inline std::vector<int> repr_pair_orbits(int N, int n_trans, const int32_t *perms)
+{
+    std::vector<int> pp((size_t)N * N);
+    std::iota(pp.begin(), pp.end(), 0);
+    for (int g = 1; g < n_trans; ++g) {
+        const int32_t *pg = perms + (size_t)g * N;
+        for (int i = 0; i < N; ++i)
+            for (int j = 0; j < N; ++j) pp[(size_t)uf_find(pp, i * N + j)] = uf_find(pp, pg[i] * N + pg[j]);
+    }
+    return uf_smallest(pp);
+}
+
 inline ReprClasses repr_classes(int N, int n_trans, const int32_t *perms)
 {
     ReprClasses K;
-    std::vector<int> pp((size_t)N * N), ps((size_t)N);
-    std::iota(pp.begin(), pp.end(), 0);
-    std::iota(ps.begin(), ps.end(), 0);
-    for (int g = 1; g < n_trans; ++g) {
-        const int32_t *pg = perms + (size_t)g * N;
-        for (int i = 0; i < N; ++i) {
-            ps[(size_t)uf_find(ps, i)] = uf_find(ps, pg[i]);
-            for (int j = 0; j < N; ++j) pp[(size_t)uf_find(pp, i * N + j)] = uf_find(pp, pg[i] * N + pg[j]);
-        }
-    }
-    const std::vector<int> orep = uf_smallest(pp), srep = uf_smallest(ps);
+    const std::vector<int> orep = repr_pair_orbits(N, n_trans, perms);
     K.cls.assign((size_t)N * N, -1);
     K.fwd.assign((size_t)N * N, 0);
     std::vector<int> id((size_t)N * N, -1);                               // class of a key (the smaller of the two orbit names)
@@ -105,7 +87,7 @@ inline ReprClasses repr_classes(int N, int n_trans, const int32_t *perms)
     K.orb.assign((size_t)N, -1);
     std::vector<int> sid((size_t)N, -1);
     for (int i = 0; i < N; ++i) {
-        const int r = srep[(size_t)i];
+        const int r = orep[(size_t)i * N + i] / (N + 1);                  // the orbit of (i, i) is that of site i: its smallest site
         if (sid[(size_t)r] < 0) {
             sid[(size_t)r] = K.n_orb++;
             K.n_s.push_back(0);
@@ -118,18 +100,18 @@ inline ReprClasses repr_classes(int N, int n_trans, const int32_t *perms)
     return K;
 }
 
-// the pair words of all classes in class order: those of class c are pairs[cls_start[c] .. cls_start[c + 1]); cls_start is padded
-// with the total for `pad` entries beyond the last class, so a pass reads the bounds of its whole group without a check
-inline void repr_flatten_classes(const ReprClasses &K, int pad, std::vector<int32_t> &cls_start, std::vector<uint32_t> &pairs)
+// the pair words of all classes (or ordered orbits) in order: those of list c are words[start[c] .. start[c + 1]); start is padded
+// with the total for `pad` entries beyond the last list, so a pass reads the bounds of its whole group without a check
+inline void repr_flatten(const std::vector<std::vector<uint32_t>> &lists, int pad, std::vector<int32_t> &start, std::vector<uint32_t> &words)
 {
-    cls_start.assign((size_t)K.n_cls + pad + 1, 0);
-    pairs.clear();
-    for (int c = 0; c < K.n_cls; ++c) {
-        cls_start[(size_t)c] = (int32_t)pairs.size();
-        pairs.insert(pairs.end(), K.pairs[(size_t)c].begin(), K.pairs[(size_t)c].end());
+    start.assign(lists.size() + pad + 1, 0);
+    words.clear();
+    for (size_t c = 0; c < lists.size(); ++c) {
+        start[c] = (int32_t)words.size();
+        words.insert(words.end(), lists[c].begin(), lists[c].end());
     }
-    for (size_t c = (size_t)K.n_cls; c < cls_start.size(); ++c) cls_start[c] = (int32_t)pairs.size();
-    if (pairs.empty()) pairs.push_back(0u);                               // one site: no pairs, and nothing reads this word
+    for (size_t c = lists.size(); c < start.size(); ++c) start[c] = (int32_t)words.size();
+    if (words.empty()) words.push_back(0u);                               // one site has no classes, and nothing reads this word
 }
 
 // The orbits of ORDERED site pairs, the diagonal pairs (i, i) included (they form orbits of their own), for correlations that are
@@ -145,14 +127,7 @@ struct ReprOrbits {
 inline ReprOrbits repr_ordered_orbits(int N, int n_trans, const int32_t *perms)
 {
     ReprOrbits O;
-    std::vector<int> pp((size_t)N * N);
-    std::iota(pp.begin(), pp.end(), 0);
-    for (int g = 1; g < n_trans; ++g) {
-        const int32_t *pg = perms + (size_t)g * N;
-        for (int i = 0; i < N; ++i)
-            for (int j = 0; j < N; ++j) pp[(size_t)uf_find(pp, i * N + j)] = uf_find(pp, pg[i] * N + pg[j]);
-    }
-    const std::vector<int> orep = uf_smallest(pp);
+    const std::vector<int> orep = repr_pair_orbits(N, n_trans, perms);
     O.orb.assign((size_t)N * N, -1);
     std::vector<int> id((size_t)N * N, -1);
     for (int i = 0; i < N; ++i)
@@ -171,40 +146,27 @@ inline ReprOrbits repr_ordered_orbits(int N, int n_trans, const int32_t *perms)
     return O;
 }
 
-// as repr_flatten_classes, for the ordered orbits
-inline void repr_flatten_orbits(const ReprOrbits &O, int pad, std::vector<int32_t> &orb_start, std::vector<uint32_t> &pairs)
+// A Hermitian gathered group of a class: value[i][j] = C / div for (i, j) forward, its conjugate otherwise (the caller passes
+// im = 0 for a packed-real vector and for a class that is its own mirror)
+inline qbh_z repr_herm_value(double re, double im, double div, bool forward)
 {
-    orb_start.assign((size_t)O.n_orb + pad + 1, 0);
-    pairs.clear();
-    for (int o = 0; o < O.n_orb; ++o) {
-        orb_start[(size_t)o] = (int32_t)pairs.size();
-        pairs.insert(pairs.end(), O.pairs[(size_t)o].begin(), O.pairs[(size_t)o].end());
-    }
-    for (size_t o = (size_t)O.n_orb; o < orb_start.size(); ++o) orb_start[o] = (int32_t)pairs.size();
+    const double v = im / div;
+    return qbh_z{re / div, forward ? v : -v};
 }
 
-// The shape of a launch from the dynamic LDS of a workgroup: workgroups of 256 lanes while four or more fit a CU (at most four
-// are used), one of 1024 lanes otherwise; gx = the resident grid along x, at most one workgroup per piece of `block` rows.
-constexpr int kReprBlockS = 256, kReprBlockL = 1024;
-constexpr int kReprPerCuS = 4;                               // workgroups of 256 lanes per CU at most
-constexpr size_t kReprLdsCu = (size_t)160 * 1024;
-constexpr size_t kReprLdsStatic = 4096;                      // the reduction scratch of a workgroup and allocation granules
-
-struct ReprShape {
-    bool large;
-    int block, gx;
-};
-
-inline ReprShape repr_launch_shape(size_t lds, int64_t dim)
+// the refusals of the symmetry arguments (QBH_EINVAL); qbh_corr_spin_repr_dev has one message of its own for all its arguments
+inline int repr_check_tables(const char *who, const int32_t *perms, const double *chars)
 {
-    const int fit = (int)(kReprLdsCu / (lds + kReprLdsStatic));
-    ReprShape s;
-    s.large = fit < 4;
-    s.block = s.large ? kReprBlockL : kReprBlockS;
-    const int per_cu = s.large ? 1 : std::min(kReprPerCuS, fit);
-    const int64_t nblk = (dim + s.block - 1) / s.block;
-    s.gx = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, (int64_t)device_cu_count() * per_cu));
-    return s;
+    if (perms && chars) return QBH_OK;
+    set_error("%s: perms and chars must be given", who);
+    return QBH_EINVAL;
+}
+
+inline int repr_check_trans(const char *who, int n_trans)
+{
+    if (n_trans >= 1 && n_trans <= kReprMaxTrans) return QBH_OK;
+    set_error("%s: n_trans = %d (1 .. %d allowed)", who, n_trans, kReprMaxTrans);
+    return QBH_EINVAL;
 }
 
 // A packed-real vector needs real characters.  A character computed as exp(-i k.t) at k = pi carries sin(pi t): an imaginary

@@ -430,6 +430,27 @@ int launch_mf_qudit(const MfQudit &t, const MfVec &a, hipStream_t s, int *nparts
     return QBH_OK;
 }
 
+int qudit_corr_check_tables(const char *who, int d, int n_diag, const double *diag, const double *string_end, const double *string_mid,
+                            const double *lower, bool want_dd, bool want_str, bool want_aa)
+{
+    auto refuse = [&](const char *fmt, auto... a) {
+        set_error(fmt, who, a...);
+        return QBH_EINVAL;
+    };
+    if (n_diag < 0 || n_diag > 4) return refuse("%s: n_diag = %d (0 .. 4 allowed)", n_diag);
+    if (n_diag > 0 && diag == nullptr) return refuse("%s: diag is NULL with n_diag = %d", n_diag);
+    if ((string_end != nullptr) != (string_mid != nullptr)) return refuse("%s: string_end and string_mid must both be given or both be NULL");
+    if (want_dd && n_diag == 0) return refuse("%s: dd is wanted but n_diag = 0");
+    if (want_str && string_end == nullptr) return refuse("%s: str is wanted but string_end and string_mid are NULL");
+    if (want_aa && lower == nullptr) return refuse("%s: aa is wanted but lower is NULL");
+    const struct { const char *name; const double *v; int first, n; } tabs[4] = {
+        {"diag", diag, 0, n_diag * d}, {"string_end", string_end, 0, d}, {"string_mid", string_mid, 0, d}, {"lower", lower, 1, d}};
+    for (const auto &tb : tabs)
+        for (int k = tb.first; tb.v && k < tb.n; ++k)
+            if (!std::isfinite(tb.v[k])) return refuse("%s: %s[%d] is not finite", tb.name, k);
+    return QBH_OK;
+}
+
 }  // namespace qbh
 
 using qbh::d2;

@@ -151,4 +151,34 @@ int qudit_check_shape(const char *who, int n_sites, int d);
 int qudit_merge_terms(const char *who, int n_sites, int d, int n_pairs, const int32_t *pair_sites, const qbh_z *pair_mat,
                       int n_single, const int32_t *single_sites, const double *single_diag, QuditTerms &T);
 
+
+// what the two d-level correlation calls (qbh_corr_qudit.hip, qbh_corr_quditrepr.hip) share
+// the table checks of the two d-level calls, in the order of qbh_corr_qudit_dev
+int qudit_corr_check_tables(const char *who, int d, int n_diag, const double *diag, const double *string_end, const double *string_mid,
+                            const double *lower, bool want_dd, bool want_str, bool want_aa);
+
+// the diagonals of the d-level outputs (a NULL array is skipped) follow from the populations pi[l] of site i
+inline void qudit_corr_put_diag(int N, int i, int d, int K, const double *pi, const double *diag, const double *string_end,
+                                const double *lower, double *dd, double *str, qbh_z *aa)
+{
+    const size_t NN = (size_t)N * N, ii = (size_t)i * N + i;
+    if (dd)
+        for (int a = 0; a < K; ++a)
+            for (int b = 0; b < K; ++b) {
+                double v = 0.0;
+                for (int l = 0; l < d; ++l) v += pi[l] * (diag[a * d + l] * diag[b * d + l]);
+                dd[(size_t)(a * K + b) * NN + ii] = v;
+            }
+    if (str) {
+        double v = 0.0;
+        for (int l = 0; l < d; ++l) v += pi[l] * (string_end[l] * string_end[l]);
+        str[ii] = v;
+    }
+    if (aa) {
+        double v = 0.0;
+        for (int l = 0; l + 1 < d; ++l) v += pi[l] * (lower[l + 1] * lower[l + 1]);
+        aa[ii] = qbh_z{v, 0.0};
+    }
+}
+
 }  // namespace qbh
