@@ -47,7 +47,7 @@ static void parse_debug(const char *e, DebugSw &d)
                         {"mf_window", &d.mf_window, nullptr}, {"kronc_abl", &d.kronc_abl, nullptr}, {"kronc_far_chunk", &d.kronc_far_chunk, nullptr},
                         {"kronc_far_ng", &d.kronc_far_ng, nullptr}, {"kronc_far_nt", &d.kronc_far_nt, nullptr}, {"no_far_align", &d.no_far_align, nullptr}, {"far_cols8", &d.far_cols8, nullptr},
                         {"far_vals8", &d.far_vals8, nullptr},
-                        {"near_lens", &d.near_lens, nullptr}, {"near_len_cap", &d.near_len_cap, nullptr},
+                        {"near_lens", &d.near_lens, nullptr}, {"near_vals", &d.near_vals, nullptr}, {"near_len_cap", &d.near_len_cap, nullptr},
                         {"no_defer", &d.no_defer, nullptr}, {"pipe_nospec", &d.pipe_nospec, nullptr}, {"host_delay_us", &d.host_delay_us, nullptr},
                         {"side_noprio", &d.side_noprio, nullptr}, {"comm_reserve", &d.comm_reserve, nullptr}, {"comm_far_cap", &d.comm_far_cap, nullptr}};
     const std::string all(e);
@@ -957,7 +957,7 @@ extern "C" int qbh_csr_get_info(const qbh_csr *A, qbh_csr_info *info)
         info->bytes_matrix = (A->nrows + 1) * 16 + ((K.sliced ? K.n_groups : A->nrows) + 1) * 8 + (K.n_xrows + 1) * (K.xrow ? 12 : 8) +
                              (K.own_far ? nnz + K.far_slots : nnz) * 20 + (K.nwb_n + K.nwb_f + K.nwb_x + 6) * 16;
         // columns as they are held: the int32 array while anything lives in it, 2 bytes per entry of a converted part
-        info->bytes_matrix += (A->d_ja ? 0 : -4 * nnz) + 2 * (K.c16_n ? K.nnz_n : 0) + 2 * (K.c16_f ? K.far_slots : 0) + 2 * (K.c8_f ? K.far_slots / 8 + 64 : 0) + 16 * (K.v8_f ? K.far_slots / 8 + 64 : 0) + (K.len_n ? A->nrows + 64 : 0) + ((!A->d_ja && K.own_x) ? 4 * K.nnz_x : 0);
+        info->bytes_matrix += (A->d_ja ? 0 : -4 * nnz) + 2 * (K.c16_n ? K.nnz_n : 0) + 2 * (K.c16_f ? K.far_slots : 0) + 2 * (K.c8_f ? K.far_slots / 8 + 64 : 0) + 16 * (K.v8_f ? K.far_slots / 8 + 64 : 0) + (K.len_n ? A->nrows + 64 : 0) + (K.vp_n ? 16 * (K.pat_n + 64) + 9 * (A->nrows + 64) : 0) + ((!A->d_ja && K.own_x) ? 4 * K.nnz_x : 0);
         info->kron_cols16 = (K.c16_n ? 1 : 0) | (K.c16_f ? 2 : 0);
         info->kron_classes = K.map.nc;
         info->kron_cross_nnz = K.nnz_x;

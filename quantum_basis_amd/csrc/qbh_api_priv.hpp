@@ -42,6 +42,7 @@ int wave_geometry_for(qbh_csr *A, const int64_t *ia, int64_t nr, int64_t nnz, do
 int kron_geometry(qbh_csr *A);
 int kron_short_cols(qbh_csr *A);
 int kron_near_lens(qbh_csr *A);
+int kron_near_vals(qbh_csr *A);
 int kron_build(qbh_csr *A);
 int kron_restore(qbh_csr *A);
 void kronc_release(qbh_csr *A);

@@ -40,6 +40,7 @@ struct DebugSw {
     int far_cols8 = -1;       // 0: the sliced far pass keeps reading its 2-byte columns slot by slot (no grouped copy, KronSplit::c8_f; A/B only)
     int far_vals8 = -1;       // 0: the sliced far pass keeps reading its values slot by slot (no grouped copy, KronSplit::v8_f; A/B only).  far_cols8=0 implies it
     int near_lens = -1;       // 0: the near pass keeps reading its row pointers (no length array, KronSplit::len_n; A/B only)
+    int near_vals = -1;       // 0: the near pass keeps reading its values entry by entry (no shared pattern, KronSplit::vp_n / dg_n / dp_n; A/B only)
     int near_len_cap = 0;     // > 0: the longest near row the length array takes (default 255: one byte); a lower cap lets a test reach the fallback
     int no_defer = 0;         // Lanczos: read <u, w> back every step instead of keeping it on the device
     int host_delay_us = 0;    // Lanczos: the host spins this long after every read-back of a step's scalars (models a slow / descheduled host)
@@ -146,6 +147,16 @@ struct SpmvArgs {
     // entries (the tail zero); a block's row offsets are the prefix sums of its rows' lengths, formed across the lanes.  ia stays
     // the stored form and is still read for a row longer than the tile.  nullptr: ia is read.
     const uint8_t *len8;
+    // one-class near part of 1 (x) T' + D (k_spmv_wave2<.., VP = true>, only beside ja16): the off-diagonal values of a near
+    // row are the same bits in every major index, so the pass reads them from the pattern of the FIRST major index -- valp, kK entries
+    // (+ 64 zeroed), entry (k - major * kK) for near entry k -- which stays cached, and the one entry that differs, the row's diagonal,
+    // from diag (one double per row: the real part as stored; the form is taken only where every imaginary part is +0.0) at position
+    // dpos8 (one byte per row) inside its row.  val stays the stored form and is
+    // still read for a row longer than the tile.  nullptr: val is read.
+    const d2      *valp;
+    const double  *diag;
+    const uint8_t *dpos8;
+    int64_t        kK;
     // k_spmv_wave2 under the dynamic walk, passes with the fused epilogue: one slot of three sums per chunk of blocks
     // (wave2_chunk_slots(n_wb) slots; never nullptr for those launches), added up in a fixed order by launch_reduce_chunks
     double *chunk_red;
@@ -325,6 +336,7 @@ int launch_kron_c8_far(const uint16_t *c16, int64_t slots, uint16_t *out, int *f
 int launch_kron_v8_far(const d2 *val, int64_t slots, d2 *out, int *flag, hipStream_t s);
 // near row lengths as bytes (out[r] = ia[r + 1] - ia[r]); *flag is raised when a row is longer than cap, or when the lengths of a
 // wave block's rows do not add up to the block's span of entries
+int launch_kron_near_vals(const int64_t *ia, const uint16_t *c16, const d2 *val, int64_t nrows, int64_t S, int64_t K, d2 *vp, double *dg, uint8_t *dp, int *flag, hipStream_t s);
 int launch_kron_near_lens(const int64_t *ia, int64_t nrows, const WaveDesc *wd, int64_t n_wb, int cap, uint8_t *out, int *flag, hipStream_t s);
 int launch_kron_check2(const int64_t *ia, const int32_t *ja, int64_t nrows, int64_t S, int64_t U0, int *d_flag, hipStream_t s);
 // qbh_opts.basis_kind (qbh_reorder.hip): re-express the plain CSR of A in the library's internal order, keep the vector map
@@ -808,6 +820,12 @@ struct qbh_csr {
         uint16_t *c8_f = nullptr;       // c16_f once per 8 slots, where the 8 are equal throughout: what the far pass reads (derived; lives and dies with c16_f)
         qbh::d2 *v8_f = nullptr;        // val_f once per 8 slots (+ 64 zeroed), where the 8 are the same bits throughout: what the far pass reads (derived, only beside c8_f; val_f stays the stored form)
         uint8_t *len_n = nullptr;       // ia_n[r + 1] - ia_n[r], one byte per near row (+ 64 zeroed): what the one-class near pass reads (derived; ia_n stays the stored form)
+        // the near values once per pattern of S rows (derived, only beside c16_n; val_n stays the stored form): the near
+        // values of the first local major index (pat_n of them), every row's diagonal value, and its position inside the row
+        qbh::d2 *vp_n = nullptr;
+        double  *dg_n = nullptr;        // real parts: the pattern is taken only where every stored diagonal has the imaginary part +0.0
+        uint8_t *dp_n = nullptr;
+        int64_t  pat_n = 0;
         qbh::d2 *val_n = nullptr, *val_f = nullptr;
         qbh::WaveDesc *wd_n = nullptr, *wd_f = nullptr;
         int64_t  nwb_n = 0, nwb_f = 0;

@@ -363,7 +363,64 @@ __global__ __launch_bounds__(kBlock) void k_kron_near_lens_check(const WaveDesc 
     if (bad) *flag = 1;
 }
 
+// The near values once per pattern of S rows (1 (x) T' + D: a hop inside the minor index has the amplitude and sign it has in every
+// major index; only the diagonal entry differs).  8 lanes per row; row r = (u, d) is compared with row d of the first major index:
+// the same length and offset inside its major index, one diagonal entry (2-byte column mod S == d: near entries stay inside the
+// row's major index) at the same position, at most 255, and every other value the same BITS (both doubles as 64-bit integers, as in
+// k_kron_v8_far).  The diagonal is kept as ONE double per row, so its imaginary part must be +0.0 as bits (a Hermitian operator's is;
+// -0.0 would change the sign of a zero in the product).  Writes the pattern (the values of the first major index as they are), every
+// row's diagonal value and its position.
+__global__ __launch_bounds__(kBlock) void k_kron_near_vals(const int64_t *ia, const uint16_t *c16, const d2 *val, int64_t nrows, int64_t S, int64_t K, d2 *vp,
+                                                           double *dg, uint8_t *dp, int *flag)
+{
+    const int sub = threadIdx.x & 7;
+    const int64_t ia0 = ia[0];
+    bool bad = false;
+    for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; r < ((nrows + 7) / 8) * 8; r += ((int64_t)gridDim.x * blockDim.x) >> 3) {
+        int nd = 0, pos = 0;
+        if (r < nrows) {
+            const int64_t u = r / S, d = r - u * S;
+            const int64_t s = ia[r], e = ia[r + 1], s0 = ia[d], e0 = ia[d + 1];
+            const bool same = e - s == e0 - s0 && s - u * K == s0;
+            bad = bad || !same;
+            for (int64_t k = s + sub; same && k < e; k += 8) {
+                const int64_t k0 = s0 + (k - s);
+                const bool diag = (int64_t)c16[k] % S == d, diag0 = (int64_t)c16[k0] % S == d;
+                const d2 v = val[k];
+                if (diag) {
+                    ++nd;
+                    pos = (int)(k - s);
+                    dg[r] = v.x;
+                    bad = bad || __double_as_longlong(v.y) != 0;
+                } else {
+                    const d2 w = val[k0];
+                    bad = bad || __double_as_longlong(v.x) != __double_as_longlong(w.x) || __double_as_longlong(v.y) != __double_as_longlong(w.y);
+                }
+                bad = bad || diag != diag0;
+                if (u == 0 && k - ia0 < K) vp[k - ia0] = v;
+            }
+        }
+        for (int off = 4; off > 0; off >>= 1) {
+            nd += __shfl_xor(nd, off, 64);
+            pos += __shfl_xor(pos, off, 64);              // one diagonal entry: the other lanes add 0
+        }
+        if (sub == 0 && r < nrows) {
+            bad = bad || nd != 1 || pos > 255;
+            dp[r] = (uint8_t)pos;
+        }
+    }
+    if (bad) *flag = 1;
+}
+
 }  // namespace
+
+int launch_kron_near_vals(const int64_t *ia, const uint16_t *c16, const d2 *val, int64_t nrows, int64_t S, int64_t K, d2 *vp, double *dg, uint8_t *dp, int *flag,
+                          hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kron_near_vals, dim3(8192), dim3(kBlock), 0, s, ia, c16, val, nrows, S, K, vp, dg, dp, flag);
+    QBH_HIP(hipGetLastError());
+    return QBH_OK;
+}
 
 int launch_kron_near_lens(const int64_t *ia, int64_t nrows, const WaveDesc *wd, int64_t n_wb, int cap, uint8_t *out, int *flag, hipStream_t s)
 {

@@ -1,5 +1,5 @@
 // qbh_split.cpp -- the Kronecker split of a product-basis operator, built IN PLACE (complex128: kron_build as a sequence of named
-// steps over one KronBuild, the derived streams of kron_short_cols / kron_near_lens, kron_restore) and its sibling for the library's
+// steps over one KronBuild, the derived streams of kron_short_cols / kron_near_lens / kron_near_vals, kron_restore) and its sibling for the library's
 // default coded format (kronc_build, kronc_build_sliced, kronc_table_route).  What the builds share: temporaries are DevPtr owners,
 // every device-side check is one flag_verdict (qbh_api_priv.hpp), every derived stream one try_derived, and one macro pair
 // (KRON_HIP / KRON_TRY) says that out of memory leaves the operator unsplit.
@@ -78,7 +78,7 @@ void kron_free_aux(qbh_csr *A)
 {
     qbh_csr::KronSplit &K = A->kron;
     for (void *q : {(void *)K.ia_n, (void *)K.ia_f, (void *)K.wd_n, (void *)K.wd_f, (void *)K.d_xt, (void *)K.d_far, (void *)K.ia_x, (void *)K.xrow,
-                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.v8_f, (void *)K.len_n, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
+                    (void *)K.wd_x, (void *)K.d_cls, (void *)K.c16_n, (void *)K.c16_f, (void *)K.c8_f, (void *)K.v8_f, (void *)K.len_n, (void *)K.vp_n, (void *)K.dg_n, (void *)K.dp_n, (void *)K.d_chunk_red, (void *)K.d_need, (void *)K.d_send_list, (void *)K.d_vsend, (void *)K.d_vrecv})
         if (q) (void)hipFree(q);
     if (K.own_far) {
         if (K.ja_f) (void)hipFree(K.ja_f);
@@ -269,6 +269,53 @@ int kron_near_lens(qbh_csr *A)
     const int cap = (dbg.near_len_cap > 0 && dbg.near_len_cap < 255) ? dbg.near_len_cap : 255;
     K.len_n = try_derived<uint8_t>(
         A, A->nrows, [&](uint8_t *l, int *flag) { return qbh::launch_kron_near_lens(K.ia_n, A->nrows, K.wd_n, K.nwb_n, cap, l, flag, A->stream); });
+    return QBH_OK;
+}
+
+// 1 (x) T' + D: a hop inside the minor index has the same amplitude and fermion sign in every major index wherever the generator
+// orders all up operators before all down operators, so the off-diagonal values of a near row are the same bits in all NU major
+// indices and three quarters of what the near pass reads is repetition.  The pass then takes them from the pattern of the FIRST local
+// major index (vp_n: K = ia_n[S] - ia_n[0] values, a few MB that stay cached; k_spmv_wave2's VP) and the one entry per row that
+// differs, the diagonal, from dg_n (its real part as stored, one double: every imaginary part must be +0.0) at position dp_n inside the row.  Derived arrays only: val_n stays what
+// download, restore, merge, shards, k_kron_need and checkpoints read, and what the pass itself reads for a row longer than the tile.
+// Taken for one class, beside c16_n only (with the row lengths len_n or without them: the length array's own A/B knob compares
+// operators that both hold the pattern), and for K >= 1024: a block of 512 slots and its lead of <= 7 entries then wraps the pattern
+// at most once.  The operator or shard consists of whole major indices (map_two_species).  The diagonal entry is the one whose
+// 2-byte column mod S is the row's minor index: near entries stay inside the row's major index, so the int32 columns are not needed.
+// One row that differs from the first major index's in length, diagonal position or the bits of a value, a row without exactly one
+// diagonal entry at a position <= 255, a diagonal with an imaginary part other than +0.0, no room, or any error: the whole operator keeps reading val_n.  QBH_DEBUG=near_vals=0 skips
+// it (A/B of the two forms from one build).
+int kron_near_vals(qbh_csr *A)
+{
+    qbh_csr::KronSplit &K = A->kron;
+    if (K.vp_n || K.map.nc != 1 || !K.c16_n || !K.ia_n || !K.val_n || qbh::debug_sw().near_vals == 0) return QBH_OK;
+    const int64_t S = K.t.S, n = A->nrows;
+    if (S <= 0 || n < S || n % S != 0) return QBH_OK;
+    int64_t first = 0, next = 0;
+    if (hipMemcpy(&first, K.ia_n, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&next, K.ia_n + S, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return QBH_OK;
+    }
+    const int64_t pat = next - first;
+    if (pat < 1024 || pat >= ((int64_t)1 << 30)) return QBH_OK;
+    DevPtr<d2> vp;
+    DevPtr<double> dg;
+    DevPtr<uint8_t> dp;
+    if (vp.alloc((size_t)pat + 64) != hipSuccess || dg.alloc((size_t)n + 64) != hipSuccess || dp.alloc((size_t)n + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        return QBH_OK;
+    }
+    (void)derive_into(A, vp, pat, [&](d2 *p, int *flag) -> int {
+        if (hipMemsetAsync(dg.get() + n, 0, 64 * sizeof(double), A->stream) != hipSuccess || hipMemsetAsync(dp.get() + n, 0, 64, A->stream) != hipSuccess)
+            return QBH_EHIP;
+        return qbh::launch_kron_near_vals(K.ia_n, K.c16_n, K.val_n, n, S, pat, p, dg.get(), dp.get(), flag, A->stream);
+    });
+    if (!vp.get()) return QBH_OK;                        // the two others go with their owners
+    K.vp_n = vp.release();
+    K.dg_n = dg.release();
+    K.dp_n = dp.release();
+    K.pat_n = pat;
     return QBH_OK;
 }
 }  // namespace qbhapi
@@ -623,6 +670,7 @@ struct KronBuild {
         KRON_TRY(kron_geometry(A));
         KRON_TRY(kron_short_cols(A));
         KRON_TRY(kron_near_lens(A));
+        KRON_TRY(kron_near_vals(A));
         if (qbh::debug_sw().print_ptrs)
             fprintf(stderr, "qbhip kron arrays: ia %p ja %p val %p | ia_n %p fp %p | ja_f %p val_f %p | wd_n %p wd_f %p | far %p | nnz_n %lld far_slots %lld\n", (void *)A->d_ia,
                     (void *)A->d_ja, (void *)A->d_val, (void *)K.ia_n, (void *)K.ia_f, (void *)K.ja_f, (void *)K.val_f, (void *)K.wd_n, (void *)K.wd_f, (void *)K.d_far,

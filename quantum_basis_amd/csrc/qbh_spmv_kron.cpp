@@ -323,6 +323,12 @@ int near_args(const KronCall &c, qbh::SpmvArgs *out)
     nr.ja = K.ja_n;
     nr.ja16 = K.c16_n;
     nr.len8 = K.len_n;                                       // one class only (kron_near_lens): pass forms 1 and 2
+    if (K.vp_n && K.c16_n) {                                 // the values once per pattern of S rows (kron_near_vals): only beside the 2-byte columns
+        nr.valp = K.vp_n;
+        nr.diag = K.dg_n;
+        nr.dpos8 = K.dp_n;
+        nr.kK = K.pat_n;
+    }
     nr.val = K.val_n;
     nr.wd = K.wd_n;
     nr.n_wb = K.nwb_n;

@@ -276,7 +276,16 @@ int launch_build_wavedesc(const int64_t *d_ia, int64_t nrows, int64_t window, Wa
 // row loop takes its row's (offset, length) from the owning lane, so a block with more rows than one pass takes (6 % of the
 // headline's) loads no pointers behind the next block's stream.  A block with more than 64 rows takes a further round of 64 lengths
 // inside the loop.  The epilogue operands of the later passes are still loaded there, as before.
-template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false, bool NL = false, bool V8 = false>
+// VP (the one-class near passes, only beside C16; with NL or without): the off-diagonal values of a near row are the same bits in every major index
+// (1 (x) T' + D, verified at creation) and a.valp holds those of the first major index, a.kK entries that stay cached: the eight value
+// loads of a block read the pattern at (entry - major index of the block's first row * kK), wrapped once where the block reaches into
+// the next major index (or its lead into the one before) -- plain loads, not non-temporal ones: the lines are meant to stay.  The one
+// entry per row that differs, the diagonal, enters the row sum at its own slot: its position inside the row comes with the row's
+// length (a.dpos8; NL: bits 24-31 of the packed word, else loaded beside the row's pointers), its value (a.diag) with the row's other epilogue operands, and the product the
+// row loop takes there is cmul({diag, +0.0}, x[row]) -- x[row] is what the slot gathered (2-byte columns: xg == xl).  The operands of every
+// product and the order of every sum are those of the per-entry stream.  (The other form -- a sentinel in the pattern and a
+// predicated load of diag[column] beside the gathers -- was not needed: this one keeps 2 wavefronts per SIMD without a spill.)
+template <int TPR, int OPS, bool DYN, bool C16 = false, bool G8 = false, bool NL = false, bool V8 = false, bool VP = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES, (OPS == 0 || OPS == 3) ? QBH_FAR_WAVES : QBH_NEAR_WAVES))) void k_spmv_wave2(SpmvArgs a)
 {
     spmv_args_resolve(a);
@@ -284,6 +293,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
     static_assert(!G8 || (C16 && OPS == 3), "grouped columns: the sliced far pass with 2-byte columns");
     static_assert(!NL || OPS == 1 || OPS == 2, "row lengths: the one-class near passes");
     static_assert(!V8 || G8, "grouped values: only beside the grouped columns");
+    static_assert(!VP || (C16 && (OPS == 1 || OPS == 2)), "shared value pattern: the one-class near passes with 2-byte columns");
     constexpr int NW = 512, RP = 64 / TPR;
     constexpr bool EPI = OPS == 1 || OPS == 2 || OPS == 4, FAR = OPS == 2 || OPS == 4;      // OPS 1: the fused epilogue WITHOUT a far addend
     // The fused reductions under the ordered dynamic walk: which wavefront takes which chunk depends on the run, so per-wavefront
@@ -323,6 +333,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
         int cls;                 // OPS 4: class of the block's first row
         int64_t xb;              // C16: element of the gather source that column value 0 of this block names
         int lead;                // entries between p0 and the block's first entry (they belong to the block before: loaded, never used)
+        int ve;                  // VP: entry of the value pattern that p0 names (negative: a lead that begins in the major index before)
     };
     // far result of one row (OPS 2 / 4)
     // (rows and minor sizes are below 2^31 -- int32 columns -- so the index arithmetic of a row's far slot is 32-bit: a 64-bit
@@ -360,9 +371,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
         b.nr = __builtin_amdgcn_readlane(dq, 6) - b.r0;
         b.cls = MULTI ? __builtin_amdgcn_readlane(dq, 3) : 0;
         b.xb = 0;
+        b.ve = 0;
         if constexpr (C16) {
             const int64_t pad = (uint32_t)__builtin_amdgcn_readlane(dq, 3);
             b.xb = OPS == 3 ? (pad >> 1) * 8 * a.kNU : pad * a.kS;
+            if constexpr (VP) {
+                // a sentinel descriptor names major index 0 beside the END of the part: whatever is not an entry of the block's own
+                // major index (or a lead in front of it) reads the pattern from its start
+                const int64_t ve = b.p0 - pad * a.kK;
+                b.ve = (ve >= -8 && ve < a.kK) ? (int)ve : 0;
+            }
         }
         b.cont0 = OPS == 3 && (__builtin_amdgcn_readlane(dq, 3) & 1);
         b.cont1 = OPS == 3 && (__builtin_amdgcn_readlane(dq, 7) & 1);
@@ -373,6 +391,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
     struct Ops {
         int s, e;                // OPS 3: s = the group pointer of group `lane` of the block, relative to the block's first slot
         d2 yo, xi, fr;
+        int dp;                  // VP: position of the diagonal entry inside row `lane` of the block
+        double dg;               // VP: the row's diagonal value (real: its imaginary part is +0.0, checked at creation)
     };
     // OPS 3: a block overlaps at most 64 groups (a group holds 8 slots or more), so ONE load per lane, issued with the block's
     // stream, brings every group pointer the block needs; the reduction passes read them by cross-lane moves.  (A load
@@ -423,6 +443,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
                 const int l = (lane >> 3) + 8 * u;
                 v[u] = ntload(a.val8 + (base >> 3) + (l < lm ? l : lm));
             }
+        } else if constexpr (VP) {
+            // slot i of the block is entry ve + i of the pattern: past the end of the major index of the block's first row it is the
+            // next one's (- kK), a lead in front of its start the one before's (+ kK); kK >= 1024 > 7 + 512, so once is enough
+            const int kk = (int)a.kK, e0 = b.n > 0 ? b.ve : 0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = lane + u * 64;
+                int e = e0 + (i < nn ? i : nm1);
+                e = e >= kk ? e - kk : e;
+                e = e < 0 ? e + kk : e;
+                v[u] = a.valp[e];
+            }
         } else {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -444,12 +476,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
             const int last = b.nr > 0 ? b.nr - 1 : 0;
             o.s = a.len8[(int64_t)b.r0 + (lane < last ? lane : last)];
             o.e = 0;
+            if constexpr (VP) o.dp = a.dpos8[(int64_t)b.r0 + (lane < last ? lane : last)];
         } else {
             const bool mine = rloc < b.nr;
             const int64_t row = mine ? (int64_t)b.r0 + rloc : 0;
             o.s = (int)(a.ia[row] - base);
             o.e = (int)(a.ia[row + 1] - base);
             if (!mine) o.s = o.e = 0;
+            if constexpr (VP) o.dp = a.dpos8[row];
         }
     };
     // epilogue operands of the CURRENT block's first pass: issued after its gathers and before the next block's stream (they
@@ -461,6 +495,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
             o.yo = a.yin[row];
             o.xi = a.xl[row];
             o.fr = FAR ? far_at(row, b.cls) : d2{0.0, 0.0};
+            if constexpr (VP) o.dg = a.diag[row];
             if (!need_y) o.yo = d2{0.0, 0.0};
         }
     };
@@ -635,9 +670,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
             open_block(first_row, nrows_blk, b0.cont0, true);
             // NL: lane l keeps (offset from p0 | length << 16) of row l of the current round of 64 rows; the offsets are the exclusive
             // prefix sums of the lengths from the end of the round before on (first round: the descriptor's lead).  An offset is at
-            // most the tile's 512, a length at most 255.
+            // most the tile's 512, a length at most 255.  VP: the position of the row's diagonal entry rides in bits 24-31.
             int pk = 0, round_end = b0.lead;
-            auto lens_round = [&](int len_raw, int rb) {
+            auto lens_round = [&](int len_raw, int dp_raw, int rb) {
                 const int len = rb + lane < b0.nr ? len_raw : 0;
                 // inclusive prefix sum over the wavefront by data-parallel moves (no LDS traffic): shifts inside the rows of 16 lanes,
                 // then lane 15 of a row into the next row, lane 31 into the upper half; a lane without a source adds 0
@@ -649,45 +684,73 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
                 inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);       // row_bcast:15 into rows 1 and 3
                 inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);       // row_bcast:31 into rows 2 and 3
                 pk = (round_end + inc - len) | (len << 16);
+                if constexpr (VP) pk |= dp_raw << 24;
                 round_end += __builtin_amdgcn_readlane(inc, 63);
             };
-            if constexpr (NL) lens_round(oA.s, 0);
+            if constexpr (NL) lens_round(oA.s, VP ? oA.dp : 0, 0);
             for (int rbase = 0; rbase < nrows_blk; rbase += RP) {
                 const int row = rbase + rloc;
                 int s_ = oA.s, e_ = oA.e;
                 bool clip = false;
                 d2 yo = oA.yo, xi = oA.xi, fr = oA.fr;
+                double dg = 0.0;
+                int dk = -1;                                         // VP: the tile slot of the row's diagonal entry
+                if constexpr (VP) dg = oA.dg;
                 if (OPS == 3) {
                     group_range(b0, oA.s, row, s_, e_, clip);        // every lane takes part in the cross-lane moves
                     if (row >= nrows_blk) s_ = e_ = 0;
                 } else if constexpr (NL) {
                     if (rbase > 0 && (rbase & 63) == 0) {            // more than 64 rows: the next 64 lengths, loaded here (correctness path)
                         const int last = b0.nr - rbase - 1;
-                        lens_round(a.len8[(int64_t)b0.r0 + rbase + (lane < last ? lane : last)], rbase);
+                        const int64_t at = (int64_t)b0.r0 + rbase + (lane < last ? lane : last);
+                        lens_round(a.len8[at], VP ? a.dpos8[at] : 0, rbase);
                     }
                     const int q = __shfl(pk, row & 63, 64);           // every lane takes part in the cross-lane moves
                     s_ = q & 0xffff;
-                    e_ = s_ + (q >> 16);
-                    if (row >= nrows_blk) s_ = e_ = 0;
-                    if (EPI && rbase > 0 && sub == 0 && row < nrows_blk) {
-                        yo = need_y ? a.yin[b0.r0 + row] : d2{0.0, 0.0};
-                        xi = a.xl[b0.r0 + row];
-                        if (FAR) fr = far_at((int64_t)b0.r0 + row, b0.cls);
+                    if constexpr (VP) {
+                        e_ = s_ + ((q >> 16) & 0xff);
+                        dk = s_ + (int)((uint32_t)q >> 24);
+                    } else {
+                        e_ = s_ + (q >> 16);
                     }
-                } else if (rbase > 0) {
-                    s_ = e_ = 0;
-                    if (row < nrows_blk) {
-                        s_ = (int)(a.ia[b0.r0 + row] - b0.p0);
-                        e_ = (int)(a.ia[b0.r0 + row + 1] - b0.p0);
-                        if (EPI && sub == 0) {
+                    if (row >= nrows_blk) s_ = e_ = 0;
+                    // VP: every lane of a row needs x[row] and the diagonal value -- whichever of them sums the diagonal's slot
+                    if (EPI && rbase > 0 && (VP || sub == 0) && row < nrows_blk) {
+                        if (sub == 0) {
                             yo = need_y ? a.yin[b0.r0 + row] : d2{0.0, 0.0};
-                            xi = a.xl[b0.r0 + row];
                             if (FAR) fr = far_at((int64_t)b0.r0 + row, b0.cls);
                         }
+                        xi = a.xl[b0.r0 + row];
+                        if constexpr (VP) dg = a.diag[b0.r0 + row];
                     }
+                } else {
+                    int dp = 0;
+                    if constexpr (VP) dp = oA.dp;
+                    if (rbase > 0) {
+                        s_ = e_ = 0;
+                        if (row < nrows_blk) {
+                            s_ = (int)(a.ia[b0.r0 + row] - b0.p0);
+                            e_ = (int)(a.ia[b0.r0 + row + 1] - b0.p0);
+                            if constexpr (VP) dp = a.dpos8[b0.r0 + row];
+                            if (EPI && (VP || sub == 0)) {
+                                if (sub == 0) {
+                                    yo = need_y ? a.yin[b0.r0 + row] : d2{0.0, 0.0};
+                                    if (FAR) fr = far_at((int64_t)b0.r0 + row, b0.cls);
+                                }
+                                xi = a.xl[b0.r0 + row];
+                                if constexpr (VP) dg = a.diag[b0.r0 + row];
+                            }
+                        }
+                    }
+                    if constexpr (VP) dk = s_ + dp;
                 }
                 d2 sum = {0.0, 0.0};
-                for (int k = s_ + sub * RSTRIDE; k < e_; k += TPR * RSTRIDE) sum += prod[k];
+                if constexpr (VP) {
+                    const d2 dprod = cmul(d2{dg, 0.0}, xi);                   // the product of the per-entry stream at that slot, operand for operand
+                    for (int k = s_ + sub; k < e_; k += TPR) sum += k == dk ? dprod : prod[k];
+                } else {
+                    for (int k = s_ + sub * RSTRIDE; k < e_; k += TPR * RSTRIDE) sum += prod[k];
+                }
 #pragma unroll
                 for (int off = TPR / 2; off > 0; off >>= 1) {
                     sum.x += __shfl_xor(sum.x, off, 64);
@@ -725,6 +788,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((OPS == 
         }
         oA.s = oB.s;
         oA.e = oB.e;
+        if constexpr (VP) oA.dp = oB.dp;
         b0 = b1;
         b1 = decode(dq2);
         if constexpr (dyn) {
@@ -809,35 +873,42 @@ int64_t wave2_chunk_slots(int64_t n_wb)
 
 // instance table of k_spmv_wave2: every tpr other than 2 and 4 takes the 8 form, every pass form other than 0, 1, 3 and 4 is 2;
 // 2-byte columns (c16) exist for the one-class near passes and the sliced far pass only, grouped ones (g8) for the latter only,
-// row lengths (nl) for the one-class near passes only; grouped values (v8) only beside grouped columns
-template <int OPS, bool C16, bool G8 = false, bool NL = false, bool V8 = false>
+// row lengths (nl) for the one-class near passes only; grouped values (v8) only beside grouped columns; the shared value pattern
+// (vp) for the one-class near passes beside 2-byte columns only, with or without the row lengths
+template <int OPS, bool C16, bool G8 = false, bool NL = false, bool V8 = false, bool VP = false>
 static SpmvKernel wave2_kernel_tpr(int tpr, bool dyn)
 {
     switch (tpr) {
-    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8, NL, V8> : k_spmv_wave2<2, OPS, false, C16, G8, NL, V8>;
-    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8, NL, V8> : k_spmv_wave2<4, OPS, false, C16, G8, NL, V8>;
-    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8, NL, V8> : k_spmv_wave2<8, OPS, false, C16, G8, NL, V8>;
+    case 2:  return dyn ? k_spmv_wave2<2, OPS, true, C16, G8, NL, V8, VP> : k_spmv_wave2<2, OPS, false, C16, G8, NL, V8, VP>;
+    case 4:  return dyn ? k_spmv_wave2<4, OPS, true, C16, G8, NL, V8, VP> : k_spmv_wave2<4, OPS, false, C16, G8, NL, V8, VP>;
+    default: return dyn ? k_spmv_wave2<8, OPS, true, C16, G8, NL, V8, VP> : k_spmv_wave2<8, OPS, false, C16, G8, NL, V8, VP>;
     }
 }
 
 template <int OPS, bool C16>
-static SpmvKernel wave2_kernel_nl(int tpr, bool dyn, bool nl)
+static SpmvKernel wave2_kernel_nl(int tpr, bool dyn, bool nl, bool vp = false)
 {
+    if constexpr (C16) {
+        if (vp) return nl ? wave2_kernel_tpr<OPS, true, false, true, false, true>(tpr, dyn) : wave2_kernel_tpr<OPS, true, false, false, false, true>(tpr, dyn);
+    } else {
+        if (vp) return nullptr;
+    }
     return nl ? wave2_kernel_tpr<OPS, C16, false, true>(tpr, dyn) : wave2_kernel_tpr<OPS, C16>(tpr, dyn);
 }
 
-static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8, bool nl, bool v8)
+static SpmvKernel wave2_kernel(int tpr, int ops, bool dyn, bool c16, bool g8, bool nl, bool v8, bool vp)
 {
     if (nl && ops != 1 && ops != 2) return nullptr;
     if (v8 && !g8) return nullptr;
+    if (vp && !c16) return nullptr;
     if (g8) {
         if (!c16 || ops != 3) return nullptr;
         return v8 ? wave2_kernel_tpr<3, true, true, false, true>(tpr, dyn) : wave2_kernel_tpr<3, true, true>(tpr, dyn);
     }
     if (c16) {
         switch (ops) {
-        case 1:  return wave2_kernel_nl<1, true>(tpr, dyn, nl);
-        case 2:  return wave2_kernel_nl<2, true>(tpr, dyn, nl);
+        case 1:  return wave2_kernel_nl<1, true>(tpr, dyn, nl, vp);
+        case 2:  return wave2_kernel_nl<2, true>(tpr, dyn, nl, vp);
         case 3:  return wave2_kernel_tpr<3, true>(tpr, dyn);
         default: return nullptr;
         }
@@ -859,10 +930,10 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
         set_error("launch_spmv_wave2: the dynamic walk of an epilogue pass needs its chunk-partial slots");
         return QBH_EINVAL;
     }
-    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr, a.len8 != nullptr, a.val8 != nullptr);
+    const SpmvKernel k = wave2_kernel(tpr, ops, a.swizzle == 3, a.ja16 != nullptr, a.ja8 != nullptr, a.len8 != nullptr, a.val8 != nullptr, a.valp != nullptr);
     if (k == nullptr) {
-        set_error("launch_spmv_wave2: 2-byte%s columns%s%s with pass form %d", a.ja8 ? " grouped" : "", a.len8 ? " / row lengths" : "",
-                  a.val8 ? " / grouped values" : "", ops);
+        set_error("launch_spmv_wave2: %s%s columns%s%s%s with pass form %d", a.ja16 ? "2-byte" : "int32", a.ja8 ? " grouped" : "", a.len8 ? " / row lengths" : "",
+                  a.val8 ? " / grouped values" : "", a.valp ? " / shared value pattern" : "", ops);
         return QBH_EINVAL;
     }
     return launch_kernel(k, grid, kBlock, s, a);
@@ -871,7 +942,7 @@ int launch_spmv_wave2(const SpmvArgs &a_in, int tpr, int ops, int grid, hipStrea
 // asks about the ordered dynamic walk with int32 columns (DYN = true, C16 = false) whatever the launch will use: kept as found
 int wave2_kernel_occupancy(int tpr, int ops)
 {
-    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false, false, false));
+    return kernel_occupancy(wave2_kernel(tpr, ops, true, false, false, false, false, false));
 }
 
 }  // namespace qbh
